@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the hot path: queries/sec at recall@10 on a SIFT1M-shaped base (+ build time).
 
-    python bench.py --gpus 1 --steps 20 --warmup 3
+    python bench.py --gpus 1 --steps 20 --warmup 3 [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -579,6 +579,35 @@ def big_base(args, n_rows, seed0, device):
     return base
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SAMPLE_SEED = 20_240_611
+
+
+def dump_outputs(directory, arrays):
+    """--dump-outputs: the arrays a caller of the timed path receives from its last step, as
+    DIR/<name>.npy -- ids as float64 (exact for every int32), float results as float32.  All
+    arrays share their row count (one row per query); when together they exceed 64 MB, the same
+    fixed, seeded sample of rows is written from each, and its row numbers as sample_rows.npy.
+    With the same arguments the inputs, the searched graph and so the dump are the same every
+    run: on one GPU a dumping run searches a graph built with the deterministic sym schedule
+    (run_single); without --dump-outputs the default build's graph is searched, as always."""
+    os.makedirs(directory, exist_ok=True)
+    host = {}
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+        host[name] = a.astype(np.float32 if a.dtype.kind == "f" and a.itemsize <= 4 else np.float64)
+    n_rows = next(iter(host.values())).shape[0]
+    row_bytes = sum(a[:1].nbytes for a in host.values())
+    budget = DUMP_LIMIT_BYTES - 4096 * (len(host) + 1)   # .npy headers included
+    if n_rows * row_bytes > budget:
+        keep = budget // (row_bytes + 8)
+        rows = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n_rows, keep, replace=False))
+        host = {name: a[rows] for name, a in host.items()}
+        host["sample_rows"] = rows.astype(np.float64)
+    for name, a in host.items():
+        np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(a))
+
+
 def timed(fn, steps, sync):
     """wall time per call of fn() over `steps` calls, bracketed by sync()"""
     sync()
@@ -663,6 +692,22 @@ def run_single(args, device, ggnn):
     torch.cuda.synchronize()
     build_wall_s = time.perf_counter() - t0
     build_kernel_s = eng.last_timing_ms()["build_ms"] / 1000.0
+    searched_graph = {"build": "default schedule (the graph timed above)"}
+    if args.dump_outputs:
+        # comparison runs: the default schedule's sym races like the reference's, so its graph --
+        # and every result searched on it -- differs a little from run to run.  The timed steps
+        # of a dumping run search a graph built with the deterministic sym schedule instead
+        # (ggnn_set_build_hooks), the same graph every run for the same arguments; the build
+        # figures above stay the default schedule's.
+        eng = ggnn.GGNN()
+        eng.set_base_reference(base)
+        eng.set_return_results_on_gpu(True)
+        eng.set_build_hooks(deterministic_sym=True)
+        t0 = time.perf_counter()
+        eng.build(args.k_build, args.tau_build, args.refine, measure)
+        torch.cuda.synchronize()
+        searched_graph = {"build": "deterministic sym schedule (--dump-outputs)",
+                          "wall_s": time.perf_counter() - t0}
 
     def step():
         return eng.query(query, args.k, args.tau_query, args.max_iters, measure)
@@ -684,6 +729,8 @@ def run_single(args, device, ggnn):
         kernel_ms.append(eng.last_timing_ms()["query_ms"])
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"ids": ids, "dists": dists})
 
     recall = recall_at_k(ids, gt)
     c1 = (ids[:, 0] == gt[:, 0]).float().mean().item()
@@ -844,6 +891,7 @@ def run_single(args, device, ggnn):
         "recall_at_10": recall, "recall_at_10_heldout_queries": recall_heldout, "c_at_1": c1,
         "base_local_intrinsic_dimension": lid,
         "graph_build_s": build_kernel_s, "graph_build_wall_s": build_wall_s,
+        "searched_graph": searched_graph,
         "bf_query_ms": bf_ms,
         "bf_query": bf_block(args, bf_ms, bf_rescanned),
         "query_kernel_ms": avg_kernel_ms,
@@ -971,7 +1019,7 @@ def exchange_group(args, device, world, rank, cpu_group):
     return group, info
 
 
-def sharded_case(args, device, world, rank, spg, cpu_group, xgroup=None):
+def sharded_case(args, device, world, rank, spg, cpu_group, xgroup=None, dump_dir=None):
     """One base of TOTAL_SHARDS x args.n_base points partitioned over the ranks (one process per
     GPU): blocking 10k-query steps (the contract's timed region), a saturating 100k-query batch
     and two batches in flight.  Times are the MAX over ranks."""
@@ -1015,6 +1063,8 @@ def sharded_case(args, device, world, rank, spg, cpu_group, xgroup=None):
         ids, dists = step()
     barrier()
     elapsed, = max_over_ranks(time.perf_counter() - t0)
+    if dump_dir:
+        dump_outputs(dump_dir, {"ids": ids, "dists": dists})
     blocking_parts = sharded.last_query_parts
     # the same steps as ONE batch each (the blocking mode of rounds 1-3; also the source of the
     # kernel time: the half-batches of the split run on the asynchronous lanes, which are not timed)
@@ -1154,6 +1204,8 @@ def run_in_process(args, ggnn):
     for _ in range(max(2, args.warmup)):
         ids, dists = step()
     el, (ids, dists) = timed(step, args.steps, torch.cuda.synchronize)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"ids": ids, "dists": dists})
     out = {"form": "one handle, set_gpus(%s), shard size %d" % (gpus, args.n_base),
            "exchange": eng.last_exchange(), "rccl_ranks": eng.rccl_ranks(),
            "queries_per_s": args.n_query / el,
@@ -1250,7 +1302,9 @@ def run_sharded(args, device, ggnn, world, rank):
                            f"{args.optional_budget_s + 90:.0f} s")
             break
         args.n_base, args.dim = n_base, dim
-        case = sharded_case(args, device, world, rank, spg, cpu_group, xgroup)
+        dump_dir = (args.dump_outputs if rank == 0 and (n_base, dim) == (main_base, main_dim)
+                    else None)
+        case = sharded_case(args, device, world, rank, spg, cpu_group, xgroup, dump_dir)
         case["dim"] = dim
         # the one-GPU point of the series on the SAME base, measured by rank 0 while the others wait
         one = None
@@ -1387,7 +1441,15 @@ def main():
                          "group of N ranks cannot be created")
     ap.add_argument("--single-device", action="store_true",
                     help="testing only: every rank uses GPU 0 (needs --backend gloo)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the results of the last one (ids, dists) "
+                         "as DIR/<name>.npy (float64 / float32, at most 64 MB: a fixed, seeded "
+                         "sample of rows beyond that); on one GPU the timed steps then search a "
+                         "graph built with the deterministic sym schedule, so that the same "
+                         "arguments give the same dump every run")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.lean:
         args.no_cpu_baseline = args.no_datasets = True
         args.no_build_roofline = args.no_scaling_reference = args.no_pipelined = True

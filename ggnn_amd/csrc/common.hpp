@@ -229,8 +229,13 @@ struct SymLaunch {
   uint32_t ps_Dc{0};
   // optional [N_layer x 4]: distance evaluations, float rows, code rows, pops per point
   uint32_t* n_work{nullptr};
+  // optional [N_layer x (KBuild - KBuild / 2) x KBuild / 2]: deterministic mode (sym.hip), the
+  // slots are then handed out by launch_sym_assign
+  int32_t* requests{nullptr};
 };
 void launch_sym(const SymLaunch& a, hipStream_t stream);
+void launch_sym_assign(uint32_t KBuild, uint32_t N_layer, const int32_t* requests,
+                       uint32_t* sym_atomic, int32_t* sym_buffer, hipStream_t stream);
 
 void launch_select(const ggnn_graph_config& cfg, uint32_t layer, const float* nn1_dist_buffer,
                    const float* rng, int32_t* translation_all, int32_t* selection_all,

@@ -442,7 +442,7 @@ struct ggnn_handle {
   // deterministic-build hooks (ggnn_set_build_hooks): injected selection random numbers
   // ([layers-1][N_shard], shard-local) and sym launched one point at a time in ascending order
   std::vector<float> hook_rng;
-  bool hook_serial_sym{false};
+  int hook_serial_sym{0};  // 1: one point per sym launch, 2: deterministic sym (sym.hip)
 
   // base as handed over by the caller
   const void* base_src{nullptr};

@@ -12,6 +12,10 @@ void ggnn_handle::build_device(DeviceCtx& ctx, float tau_build, uint32_t refinem
   DeviceBuffer nn1_dist(static_cast<size_t>(N) * 4), graph_buffer(static_cast<size_t>(N) * K * 4),
       rng(static_cast<size_t>(N) * 4), sym_buffer(static_cast<size_t>(N) * KF * 4),
       sym_atomic(static_cast<size_t>(N) * 4), stats_scratch(3 * kStatsBlocks * 4);
+  // deterministic sym (hook_serial_sym == 2): the candidate slots of every search
+  DeviceBuffer sym_requests;
+  if (hook_serial_sym == 2)
+    sym_requests.alloc(static_cast<size_t>(N) * (K - KF) * KF * 4);
   ctx.build_ms = 0.f;
   uint64_t rng_calls = static_cast<uint64_t>(ctx.first_shard) << 16;
   // diagnostic mode (collect_counters): per-point work counters and an own HIP-event time of
@@ -152,7 +156,13 @@ void ggnn_handle::build_device(DeviceCtx& ctx, float tau_build, uint32_t refinem
         s.ps_params = sh.ps_params.as<float>();
         s.ps_Dc = prescreen_code_dim(pad_D);
       }
-      if (hook_serial_sym) {
+      if (hook_serial_sym == 2) {
+        GGNN_HIP_CHECK(hipMemsetAsync(sym_requests.p, 0xff,
+                                      static_cast<size_t>(cfg.Ns[layer]) * (K - KF) * KF * 4,
+                                      stream));
+        s.requests = sym_requests.as<int32_t>();
+      }
+      if (hook_serial_sym == 1) {
         // the reference's sym races through atomics and cross-block reads of sym_buffer
         // (sym_query_layer.cu:102-104 vs :133-136); one point per launch in ascending order is
         // the one schedule that is comparable with a CPU restatement
@@ -170,6 +180,9 @@ void ggnn_handle::build_device(DeviceCtx& ctx, float tau_build, uint32_t refinem
       }
       else
         launch_sym(s, stream);
+      if (hook_serial_sym == 2)
+        launch_sym_assign(K, cfg.Ns[layer], sym_requests.as<int32_t>(), sym_atomic.as<uint32_t>(),
+                          sym_buffer.as<int32_t>(), stream);
       launch_sym_buffer_merge(K, cfg.Ns[layer], sym_buffer.as<int32_t>(),
                               sym_atomic.as<uint32_t>(), layer_graph(layer), stream);
     };

@@ -292,7 +292,9 @@ ggnn_status ggnn_set_build_hooks(ggnn_t* h, const float* rng, uint64_t n_rng, in
   return guarded(h, [&] {
     GGNN_REQUIRE(rng != nullptr || n_rng == 0, GGNN_INVALID_ARGUMENT, "rng is null");
     h->hook_rng.assign(rng, rng + n_rng);
-    h->hook_serial_sym = serial_sym != 0;
+    GGNN_REQUIRE(serial_sym >= 0 && serial_sym <= 2, GGNN_INVALID_ARGUMENT,
+                 "serial_sym must be 0, 1 or 2");
+    h->hook_serial_sym = serial_sym;
   });
 }
 

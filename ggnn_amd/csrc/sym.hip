@@ -14,6 +14,10 @@ struct SymArgs {
   const float* nn1_stats;
   int32_t* sym_buffer;   // [N_layer x KF]
   uint32_t* sym_atomic;  // [N_layer]
+  // deterministic mode (optional [N_layer x KL x KF]): the searches do not read the inverse links
+  // requested in this pass, and a point that is not found writes its candidate slots here
+  // instead of claiming one; sym_assign_kernel then hands the slots out in ascending order
+  int32_t* requests;
   uint4* n_work;  // optional [N_layer]: distance evaluations, float rows, code rows, pops per point
   uint32_t D, KBuild, N_layer, sorted, first_n, count;
   float tau;
@@ -293,8 +297,9 @@ __global__ void __launch_bounds__(kWave)
           if (lane < (int)kKBlock && k2 < K) {
             other_id = (k2 < KL)
                            ? a.graph[static_cast<size_t>(static_cast<uint32_t>(anchor)) * K + k2]
-                           : a.sym_buffer[static_cast<size_t>(static_cast<uint32_t>(anchor)) * KF +
-                                          (k2 - KL)];
+                           : a.requests ? kEmptyKey
+                                        : a.sym_buffer[static_cast<size_t>(static_cast<uint32_t>(anchor)) * KF +
+                                                       (k2 - KL)];
           }
           if (__any(lane < (int)kKBlock && k2 < K && other_id == n)) {
             found = true;
@@ -304,7 +309,15 @@ __global__ void __launch_bounds__(kWave)
         }
       }
 
-      if (!found) {
+      if (a.requests) {
+        int32_t* req = a.requests + (static_cast<size_t>(un) * KL + i + k) * KF;
+        for (uint32_t i3 = 0; i3 < KF; ++i3) {
+          const int other = found ? kEmptyKey : sl.key_at(i3);
+          if (lane == 0)
+            req[i3] = other;
+        }
+      }
+      else if (!found) {
         // request an inverse link at the nearest point with a free slot, sym_query_layer.cu:121-141
         for (uint32_t i3 = 0; i3 < KF; ++i3) {
           const int other = sl.key_at(i3);
@@ -360,6 +373,62 @@ static void launch_sym_cfg(const SymArgs& args, bool use_ps, ggnn_measure measur
     launch_sym_r<BaseT, LPR, NCH, kCos, NoPrescreen>(args, stream);
 }
 
+// deterministic mode, second step: the requests of launch_sym in ascending order (point, then its
+// local neighbour), each at the first of its candidates whose slot counter is below KF -- the
+// schedule of one point per launch, without the in-pass reads.  A request whose point already
+// holds a slot at that candidate (an earlier search of the same point asked there) is satisfied
+// by it: the searches of the racy schedule would mostly have found that pending link.  One wave:
+// 64 request rows are read at once, the rows of found searches are skipped by ballot.
+__global__ void __launch_bounds__(kWave) sym_assign_kernel(const int32_t* requests, uint32_t N_layer,
+                                                           uint32_t KL, uint32_t KF,
+                                                           uint32_t* sym_atomic,
+                                                           int32_t* sym_buffer)
+{
+  const int lane = threadIdx.x;
+  const size_t n_req = static_cast<size_t>(N_layer) * KL;
+  for (size_t r0 = 0; r0 < n_req; r0 += kWave) {
+    const size_t r = r0 + lane;
+    const int first = r < n_req ? requests[r * KF] : kEmptyKey;
+    unsigned long long m = __ballot(first != kEmptyKey);
+    if (lane != 0)
+      continue;
+    while (m) {
+      const int j = __ffsll(static_cast<long long>(m)) - 1;
+      m &= m - 1;
+      const size_t rj = r0 + j;
+      const int n = static_cast<int>(rj / KL);
+      for (uint32_t i3 = 0; i3 < KF; ++i3) {
+        const int other = requests[rj * KF + i3];
+        if (other < 0 || static_cast<uint32_t>(other) >= N_layer)
+          break;
+        int32_t* row = sym_buffer + static_cast<size_t>(static_cast<uint32_t>(other)) * KF;
+        const uint32_t pos = sym_atomic[other];
+        bool held = false;
+        for (uint32_t p = 0; p < pos && p < KF && !held; ++p)
+          held = row[p] == n;
+        if (held)
+          break;
+        sym_atomic[other] = pos + 1;
+        if (pos < KF) {
+          sym_buffer[static_cast<size_t>(static_cast<uint32_t>(other)) * KF + pos] = n;
+          break;
+        }
+      }
+    }
+  }
+}
+
+void launch_sym_assign(uint32_t KBuild, uint32_t N_layer, const int32_t* requests,
+                       uint32_t* sym_atomic, int32_t* sym_buffer, hipStream_t stream)
+{
+  const uint32_t KF = KBuild / 2, KL = KBuild - KF;
+  if (!N_layer || !KL || !KF)
+    return;
+  hipLaunchKernelGGL(sym_assign_kernel, dim3(1), dim3(kWave), 0, stream, requests, N_layer, KL, KF,
+                     sym_atomic, sym_buffer);
+  GGNN_HIP_CHECK(hipGetLastError());
+}
+
 void launch_sym(const SymLaunch& a, hipStream_t stream)
 {
   check_vector_layout(a.base, a.D, a.dtype);
@@ -370,6 +439,7 @@ void launch_sym(const SymLaunch& a, hipStream_t stream)
   args.nn1_stats = a.nn1_stats;
   args.sym_buffer = a.sym_buffer;
   args.sym_atomic = a.sym_atomic;
+  args.requests = a.requests;
   args.n_work = reinterpret_cast<uint4*>(a.n_work);
   args.D = a.D;
   args.KBuild = a.KBuild;

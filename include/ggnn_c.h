@@ -204,7 +204,12 @@ ggnn_status ggnn_set_prescreen(ggnn_t* h, int enable);
  * + n] instead of the engine's generator; `serial_sym` != 0 launches the sym kernel one point
  * at a time in ascending order.  With both, ggnn_build follows one fixed serialisation of
  * GraphConstructionImpl::build/refine (graph_construction.cu:128-147) that a CPU restatement can
- * be compared with bit for bit.  Slow; off by default. */
+ * be compared with bit for bit.  Slow; off by default.  `serial_sym` = 2 instead: the sym
+ * searches of a pass run concurrently but do not read the inverse links requested in that pass,
+ * and the slots are then handed out in ascending order of the requesting point (one wave; a
+ * point already holding a slot at a candidate is not given a second) -- a build that is the
+ * same on every run (with the engine's own seeded generator), not the reference's schedule.
+ * Also slow: the hand-out is serial (bench.py uses it only for --dump-outputs runs). */
 ggnn_status ggnn_set_build_hooks(ggnn_t* h, const float* rng, uint64_t n_rng, int serial_sym);
 /* shard layout chosen by ggnn_build / ggnn_load (GGNNImpl::prepare, ggnn.cu:154-203): total
  * number of shards, shards per GPU (the width factor of results returned on the GPU,

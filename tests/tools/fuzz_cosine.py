@@ -2,7 +2,7 @@
 near-ties for random shapes / element types; the traversal must stay finite and reasonably
 accurate (unstructured Gaussian rows are hard: recall 0.8-0.9 at tau 1.0 / 400 is expected)."""
 import os, sys
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import numpy as np, torch
 import ggnn_amd as ggnn
 ggnn.set_log_level(-1)
