@@ -114,6 +114,7 @@ SIGNATURES = {
     "ggnn_set_log_level": (None, [_int]),
     "ggnn_graph_config_init": (_int, [_u32, _u32, _u32, _cfgp]),
     "ggnn_query_sizing": (_int, [_u32, _u32, _u32, C.POINTER(_u32), C.POINTER(_u32)]),
+    "ggnn_op_dist_layout": (_int, [_u32, _int, C.POINTER(_u32), C.POINTER(_u32)]),
     "ggnn_op_query": (_int, [_vp, _int, _u32, _u32, _vp, _u32, _vp, _u32, _vp, _u32, _vp, _u32,
                              _f32, _u32, _int, _u32, _u32, _vp, _vp, _vp, _vp, _vp]),
     "ggnn_prescreen_sizes": (_int, [_u32, _u32, _int, C.POINTER(_u32), C.POINTER(_sz),

@@ -1,6 +1,7 @@
 // extern "C" entry points of libggnn_amd.so (include/ggnn_c.h): handle API and operator seam.
 // Every call is guarded: exceptions become status codes + ggnn_last_error().
 #include "engine.hpp"
+#include "traversal.hpp"
 
 namespace {
 thread_local std::string g_create_error;
@@ -446,6 +447,18 @@ ggnn_status ggnn_query_sizing(uint32_t D, uint32_t k_query, uint32_t max_iterati
                               uint32_t* cache_size, uint32_t* sorted_size)
 {
   return guarded(nullptr, [&] { query_sizing(D, k_query, max_iterations, cache_size, sorted_size); });
+}
+
+ggnn_status ggnn_op_dist_layout(uint32_t D, ggnn_dtype dtype, uint32_t* lanes_per_row,
+                                uint32_t* chunks_per_lane)
+{
+  return guarded(nullptr, [&] {
+    GGNN_REQUIRE(dtype == GGNN_F32 || dtype == GGNN_U8, GGNN_INVALID_ARGUMENT, "unknown dtype");
+    GGNN_REQUIRE(lanes_per_row && chunks_per_lane, GGNN_INVALID_ARGUMENT, "null output pointer");
+    const DistConfig dc = pick_dist_config(D, dtype);
+    *lanes_per_row = static_cast<uint32_t>(dc.lpr);
+    *chunks_per_lane = static_cast<uint32_t>(dc.nch);
+  });
 }
 
 ggnn_status ggnn_op_query(const void* base, ggnn_dtype dtype, uint32_t N_base, uint32_t D,

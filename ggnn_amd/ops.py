@@ -65,6 +65,16 @@ def query_sizing(D, k_query, max_iterations):
     return cache.value, sorted_.value
 
 
+def dist_layout(D, dtype):
+    """(lanes per row, 16-byte chunks per lane) of the distance kernels for rows of D elements of
+    `dtype` (torch.float32 / torch.uint8)"""
+    import ctypes as C
+    code = {torch.float32: _lib.F32, torch.uint8: _lib.U8}[dtype]
+    lpr, nch = C.c_uint32(), C.c_uint32()
+    check(lib().ggnn_op_dist_layout(D, code, C.byref(lpr), C.byref(nch)))
+    return lpr.value, nch.value
+
+
 def prescreen_sizes(N, D, measure=EUCLIDEAN):
     import ctypes as C
     dc, pf, sf = C.c_uint32(), C.c_size_t(), C.c_size_t()

@@ -300,6 +300,10 @@ ggnn_status ggnn_graph_config_init(uint32_t N, uint32_t D, uint32_t KBuild,
 /* host sizing of the query kernel, src/ggnn/query/query_kernels.cu:55-110 */
 ggnn_status ggnn_query_sizing(uint32_t D, uint32_t k_query, uint32_t max_iterations,
                               uint32_t* cache_size, uint32_t* sorted_size);
+/* row layout of every distance kernel for rows of D elements of `dtype` (pure host, test entry):
+ * *lanes_per_row lanes hold *chunks_per_lane 16-byte chunks each (pick_dist_config) */
+ggnn_status ggnn_op_dist_layout(uint32_t D, ggnn_dtype dtype, uint32_t* lanes_per_row,
+                                uint32_t* chunks_per_lane);
 
 /* QueryKernels::query  query_kernels.cu:50-186 -> query_layer.cu:39-97 (one shard).
  * graph0 [N_base x KBuild], start [num_start] (= translation[L-1]), nn1_stats [2].

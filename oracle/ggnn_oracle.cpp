@@ -1685,6 +1685,13 @@ void orc_wave_model_script(uint32_t BEST, uint32_t SORTED, uint32_t CACHE, float
 }  // extern "C"
 
 extern "C" {
+// the row layout the wave-order distances use (wave_layout), for the comparison with the engine's
+// pick_dist_config (tests/test_layout_coverage.py)
+void orc_wave_layout(int dtype, uint32_t D, uint32_t* lpr, uint32_t* nch)
+{
+  uint32_t epc;
+  wave_layout(dtype, D, *lpr, *nch, epc);
+}
 uint32_t orc_bit_ceil(uint32_t v)
 {
   return bit_ceil_u32(v);

@@ -82,6 +82,13 @@ def graph_config(N, D, K):
     return cfg
 
 
+def wave_layout(D, dtype):
+    """(lanes per row, 16-byte chunks per lane) the wave-order distances assume; dtype F32 / U8"""
+    lpr, nch = C.c_uint32(), C.c_uint32()
+    lib().orc_wave_layout(int(dtype), C.c_uint32(D), C.byref(lpr), C.byref(nch))
+    return lpr.value, nch.value
+
+
 def query_sizing(D, KQuery, max_iters):
     s = QuerySizing()
     rc = lib().orc_query_sizing(C.c_uint32(D), C.c_uint32(KQuery), C.c_uint32(max_iters),

@@ -78,3 +78,35 @@ def assert_order_tolerance(d_wave, d_ref, same, D, measure, what=""):
     a, b = d_wave[same], d_ref[same]
     fin = np.isfinite(a) & np.isfinite(b)
     assert np.all(np.abs(a[fin] - b[fin]) <= RTOL * np.abs(b[fin]) + atol), what
+
+
+def assert_rows_consistent(base, q, ids, d, measure, what=""):
+    """Float64 check of returned rows, independent of any oracle (traversal outputs included):
+    every id is a base index or -1 with +inf, ids are distinct within a row, distances are
+    non-decreasing, and each distance is within RTOL * |d64| + atol of the float64 distance of its
+    own id.  Squared L2 on integer-valued data whose exact distance stays below 2^24 is exact in
+    every summation order: the tolerance is then 0."""
+    N, D = base.shape
+    ids, d = np.asarray(ids), np.asarray(d)
+    assert ids.shape == d.shape and ids.shape[0] == q.shape[0], what
+    valid = ids >= 0
+    assert np.all(ids < N), what
+    assert np.all(ids[~valid] == -1) and np.all(np.isposinf(d[~valid])), what
+    assert np.all(np.diff(np.where(valid, d, np.inf), axis=1) >= 0), what
+    for r in range(ids.shape[0]):
+        v = ids[r][valid[r]]
+        assert len(np.unique(v)) == len(v), (what, r)
+    t = true_distances(base, q, measure)
+    rows = np.broadcast_to(np.arange(ids.shape[0])[:, None], ids.shape)
+    t_g, d_g = t[rows[valid], ids[valid]], d[valid].astype(np.float64)
+    if measure == 0:
+        # (the float64 expanded form is exact on integers; otherwise its own error is about
+        # 1e-16 * |x|^2, covered by the absolute term)
+        integral = np.array_equal(base, np.round(base)) and np.array_equal(q, np.round(q))
+        exact = integral & (t_g < 2.0 ** 24)
+        rtol = np.where(exact, 0.0, RTOL)
+        atol = np.where(exact, 0.0, 1e-9 * float(np.abs(t_g).max(initial=0.0)))
+    else:
+        atol, rtol = cos_atol(D), RTOL
+    bad = np.abs(d_g - t_g) > rtol * np.abs(t_g) + atol
+    assert not bad.any(), (what, int(bad.sum()), float(np.abs(d_g - t_g)[bad].max()))

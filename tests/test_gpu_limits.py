@@ -8,6 +8,8 @@ operator seam of the C-ABI (ggnn_op_*)."""
 import numpy as np
 import pytest
 
+from parity_helpers import assert_rows_consistent
+
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
@@ -126,6 +128,7 @@ def test_d4096_query_top_merge(ops, orc, dtype, measure, ps):
         o_ids, o_d, o_nd, o_np = orc.query(g["base"], q, graph0, start_points(g), g["stats"], 10,
                                            0.7, 300, measure, counters=True)
         assert np.array_equal(ids.cpu().numpy(), o_ids) and np.array_equal(d.cpu().numpy(), o_d)
+        assert_rows_consistent(g["base"], q, ids.cpu().numpy(), d.cpu().numpy(), measure)
         assert np.array_equal(nd.cpu().numpy().astype(np.uint32), o_nd)
         assert np.array_equal(npop.cpu().numpy().astype(np.uint32), o_np)
         if ps:

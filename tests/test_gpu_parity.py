@@ -5,12 +5,16 @@ import numpy as np
 import pytest
 
 from conftest import make_int_data, make_uni_data
-from parity_helpers import assert_topk_parity, cos_atol
+from parity_helpers import assert_rows_consistent, assert_topk_parity, cos_atol
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
 RTOL = 1e-4
+# Least share of positions where the reference-order oracle returns the same id as the kernel in
+# test_query_float_tolerance / test_query_cosine.  Measured with the CPU oracle (wave order against
+# reference order) on their seeds: 1.0 in both; the floor leaves room for a few near-ties.
+SAME_FLOOR = 0.95
 
 
 @pytest.fixture(scope="module")
@@ -374,7 +378,9 @@ def test_query_float_tolerance(ops, orc):
     # the reference's own (restated) cub::BlockReduce order: distances of common ids within 1e-4
     r_ids, r_d = orc.query(base, q, graph[:N], start, stats, 10, 0.6, 400)
     same = r_ids == o_ids
+    assert same.mean() >= SAME_FLOOR, same.mean()
     np.testing.assert_allclose(o_d[same], r_d[same], rtol=RTOL)
+    assert_rows_consistent(base, q, ids.cpu().numpy(), d.cpu().numpy(), 0)
 
 
 def test_query_cosine(ops, orc):
@@ -390,7 +396,9 @@ def test_query_cosine(ops, orc):
     assert np.array_equal(d.cpu().numpy(), o_d)
     r_ids, r_d = orc.query(base, q, graph[:N], start, stats, 10, 0.6, 400, 1)
     same = r_ids == o_ids
+    assert same.mean() >= SAME_FLOOR, same.mean()
     np.testing.assert_allclose(o_d[same], r_d[same], rtol=RTOL, atol=cos_atol(D))
+    assert_rows_consistent(base, q, ids.cpu().numpy(), d.cpu().numpy(), 1)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -616,6 +624,7 @@ def test_config_matrix_query_top_merge(ops, orc, dtype, D, K, measure):
     orc.set_wave_order(not exact)
     o_ids, o_d = orc.query(g["base"], q, graph0, start_points(g), g["stats"], 10, 0.7, 300, measure)
     assert np.array_equal(ids.cpu().numpy(), o_ids) and np.array_equal(d.cpu().numpy(), o_d)
+    assert_rows_consistent(g["base"], q, ids.cpu().numpy(), d.cpu().numpy(), measure)
     # top (layer 0 and 1)
     for layer in (0, 1):
         tr_l = None if layer == 0 else g["tr"][c.STs_offsets[layer]:c.STs_offsets[layer] + c.Ns[layer]]
