@@ -5,7 +5,8 @@ nanobind module (src/ggnn/python/nanobind.cu:131-301), implemented over the C-AB
     g = ggnn.GGNN(); g.set_base(base); g.build(24, 0.5)
     indices, dists = g.query(query, 10, 0.64, 400)
 
-Inputs may be numpy arrays or torch tensors (CPU or CUDA), C-contiguous 2-D float32/uint8;
+Inputs may be numpy arrays or torch tensors (CPU or CUDA), C-contiguous 2-D float32/uint8/
+float16/bfloat16 (bfloat16 through torch only: numpy has no such type);
 results are torch tensors like the reference's (nb::pytorch ndarrays), int32 ids and float32
 SQUARED L2 (or |1-cos|) distances.
 """
@@ -58,12 +59,23 @@ def _loc(t):
     return _lib.CPU, 0
 
 
+_DTYPE_CODES = {torch.float32: _lib.F32, torch.uint8: _lib.U8, torch.float16: _lib.F16,
+                torch.bfloat16: _lib.BF16}
+
+
 def _dtype_code(t):
-    if t.dtype == torch.float32:
-        return _lib.F32
-    if t.dtype == torch.uint8:
-        return _lib.U8
-    raise TypeError("unsupported datatype (float32 and uint8 are supported)")
+    code = _DTYPE_CODES.get(t.dtype)
+    if code is None:
+        raise TypeError("unsupported datatype (float32, uint8, float16 and bfloat16 are supported)")
+    return code
+
+
+def _host_rows(t):
+    """numpy rows of a CPU tensor; 16-bit rows widened to float32 (exact; numpy has no
+    bfloat16)"""
+    if t.dtype in (torch.float16, torch.bfloat16):
+        t = t.float()
+    return t.numpy()
 
 
 # ---------------------------------------------------------------------------------------------
@@ -549,7 +561,7 @@ class Evaluator:
             return  # duplicates unknown (eval.cpp:93-102)
         if base_t.dtype != query_t.dtype:
             raise RuntimeError("base and query need to have the same data type")
-        b, q = base_t.numpy(), query_t.numpy()
+        b, q = _host_rows(base_t), _host_rows(query_t)
         Nq, gtD, K = q.shape[0], self.gt.shape[1], self.k_query
         eps = np.float32(0.000001)
         # distances of all ground-truth entries, [Nq, gtD]

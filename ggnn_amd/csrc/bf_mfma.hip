@@ -299,6 +299,60 @@ struct TileStage<uint8_t> {
   }
 };
 
+// float16 / bfloat16: CW/8 chunks of 16 bytes per row, 32 rows -> at most 512 chunks, two per
+// thread (unconditional clamped loads as above); widened exactly to float32 in the tile, no shift
+template <typename T16>
+struct TileStage16 {
+  uint4 r[2];
+  float bn;
+  uint32_t rows;
+  float bn_pad;
+  GGNN_DEV void load(const T16* base, uint32_t D, uint32_t row0, uint32_t end, uint32_t col0,
+                     uint32_t CW, const float* bnorm, float bn_pad_)
+  {
+    const uint32_t last = end - 1;
+    rows = end > row0 ? end - row0 : 0u;
+    bn_pad = bn_pad_;
+    bn = bnorm[min(row0 + (threadIdx.x & 31u), last)];
+    const uint32_t cpr = CW / 8;
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+      const uint32_t idx = threadIdx.x + 256 * e;
+      const uint32_t row = idx / cpr, col = col0 + 8 * (idx % cpr);
+      r[e] = *reinterpret_cast<const uint4*>(base + static_cast<size_t>(min(row0 + row, last)) * D +
+                                             min(col, D - 8));
+    }
+  }
+  GGNN_DEV float norm() const { return threadIdx.x < rows ? bn : bn_pad; }  // threads 0..31
+  GGNN_DEV void store_shifted(float* tile, uint32_t DP, uint32_t CW, const float*, uint32_t) const
+  {
+    if (threadIdx.x < (uint32_t)kBfTileRows)
+      tile[threadIdx.x * DP + CW] = threadIdx.x < rows ? bn : bn_pad;
+    const uint32_t cpr = CW / 8;
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+      const uint32_t idx = threadIdx.x + 256 * e;
+      const uint32_t row = idx / cpr, c = idx % cpr;
+      if (row < (uint32_t)kBfTileRows) {
+        float* dst = tile + row * DP + 8 * c;
+#pragma unroll
+        for (int w = 0; w < 2; ++w) {
+          float4 f;
+          f.x = ChunkOf<T16>::get(r[e], 4 * w + 0);
+          f.y = ChunkOf<T16>::get(r[e], 4 * w + 1);
+          f.z = ChunkOf<T16>::get(r[e], 4 * w + 2);
+          f.w = ChunkOf<T16>::get(r[e], 4 * w + 3);
+          *reinterpret_cast<float4*>(dst + 4 * w) = f;
+        }
+      }
+    }
+  }
+};
+template <>
+struct TileStage<f16_t> : TileStage16<f16_t> {};
+template <>
+struct TileStage<bf16_t> : TileStage16<bf16_t> {};
+
 // A operand of one chunk: aq[kk] = q[col0 + h*Dh + kk] (0 outside the row / the query set)
 // (float32 squared L2: `query` is the shifted copy made by shift_rows_kernel)
 // (predicated on purpose: with unconditional loads the scheduler hoists all sixteen pieces of the
@@ -346,6 +400,31 @@ GGNN_DEV void load_query_chunk(float (&aq)[64], const uint8_t* qrow, bool qvalid
     for (int e = 0; e < 16; ++e)
       aq[16 * t + e] = ChunkOf<uint8_t>::get(v, e);
   }
+}
+// float16 / bfloat16 query chunk: eight chunks of 8 elements, widened exactly
+template <typename T16>
+GGNN_DEV void load_query_chunk16(float (&aq)[64], const T16* qrow, bool qvalid, uint32_t D,
+                                 uint32_t Dh, uint32_t col_h)
+{
+#pragma unroll
+  for (int t = 0; t < 8; ++t) {
+    uint4 v = make_uint4(0u, 0u, 0u, 0u);
+    if (qvalid && static_cast<uint32_t>(8 * t) < Dh && col_h + 8 * t < D)
+      v = *reinterpret_cast<const uint4*>(qrow + col_h + 8 * t);
+#pragma unroll
+    for (int e = 0; e < 8; ++e)
+      aq[8 * t + e] = ChunkOf<T16>::get(v, e);
+  }
+}
+GGNN_DEV void load_query_chunk(float (&aq)[64], const f16_t* qrow, bool qvalid, uint32_t D,
+                               uint32_t Dh, uint32_t col_h)
+{
+  load_query_chunk16(aq, qrow, qvalid, D, Dh, col_h);
+}
+GGNN_DEV void load_query_chunk(float (&aq)[64], const bf16_t* qrow, bool qvalid, uint32_t D,
+                               uint32_t Dh, uint32_t col_h)
+{
+  load_query_chunk16(aq, qrow, qvalid, D, Dh, col_h);
 }
 
 // Rare path of the epilogue: stable insertion of the tile's distances that beat a list's worst
@@ -507,13 +586,19 @@ __global__ void __launch_bounds__(256) pack_query_kernel(const BaseT* query, uin
     const uint64_t q = (r >> 2) * kBfQueriesPerBlock + w * 32 + (lane & 31);
     const uint32_t col = c * 128 + (lane >> 5) * 64 + 4 * t;
     float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (q < Nq && col < D) {  // (D is a multiple of 4 / 16: all four columns exist)
+    if (q < Nq && col < D) {  // (D is a multiple of 4 / 8 / 16: all four columns exist)
       if constexpr (std::is_same<BaseT, float>::value)
         v = *reinterpret_cast<const float4*>(query + q * D + col);
-      else {
+      else if constexpr (std::is_same<BaseT, uint8_t>::value) {
         const uint32_t b = *reinterpret_cast<const uint32_t*>(query + q * D + col);
         v = make_float4(static_cast<float>(b & 0xffu), static_cast<float>((b >> 8) & 0xffu),
                         static_cast<float>((b >> 16) & 0xffu), static_cast<float>(b >> 24));
+      }
+      else {
+        const uint2 b = *reinterpret_cast<const uint2*>(query + q * D + col);
+        const uint4 c = make_uint4(b.x, b.y, 0u, 0u);
+        v = make_float4(ChunkOf<BaseT>::get(c, 0), ChunkOf<BaseT>::get(c, 1),
+                        ChunkOf<BaseT>::get(c, 2), ChunkOf<BaseT>::get(c, 3));
       }
     }
     out[i] = v;
@@ -1160,7 +1245,7 @@ __global__ void __launch_bounds__(kWave) bf_rerank_kernel(const BfRerankArgs a)
 // ---- host ---------------------------------------------------------------------------------------
 bool bf_mfma_supported(const BfLaunch& a)
 {
-  const uint32_t epc = a.dtype == GGNN_F32 ? 4 : 16;
+  const uint32_t epc = dtype_elems_per_chunk(a.dtype);
   if (!(a.D % epc == 0 && a.k_query + 8 <= kBfMaxKP && a.Nq >= 256 && a.N_base >= 4096))
     return false;
   // tiles + candidate lists (+ the shift vector of the chunked kernel) must fit into 160 KB of LDS
@@ -1315,6 +1400,14 @@ void launch_bf_query_mfma(const BfLaunch& a, hipStream_t stream)
       hipLaunchKernelGGL((pack_query_kernel<float>), grid, dim3(256), 0, stream,
                          static_cast<const float*>(tile_query), a.Nq, a.D, pack_chunks, n4,
                          reinterpret_cast<float4*>(q_packed));
+    else if (a.dtype == GGNN_F16)
+      hipLaunchKernelGGL((pack_query_kernel<f16_t>), grid, dim3(256), 0, stream,
+                         static_cast<const f16_t*>(tile_query), a.Nq, a.D, pack_chunks, n4,
+                         reinterpret_cast<float4*>(q_packed));
+    else if (a.dtype == GGNN_BF16)
+      hipLaunchKernelGGL((pack_query_kernel<bf16_t>), grid, dim3(256), 0, stream,
+                         static_cast<const bf16_t*>(tile_query), a.Nq, a.D, pack_chunks, n4,
+                         reinterpret_cast<float4*>(q_packed));
     else
       hipLaunchKernelGGL((pack_query_kernel<uint8_t>), grid, dim3(256), 0, stream,
                          static_cast<const uint8_t*>(tile_query), a.Nq, a.D, pack_chunks, n4,
@@ -1453,6 +1546,18 @@ void launch_bf_query_mfma(const BfLaunch& a, hipStream_t stream)
       GGNN_BF_MFMA(float, kL2);
     else
       GGNN_BF_MFMA(float, kCos);
+  }
+  else if (a.dtype == GGNN_F16) {
+    if (a.measure == GGNN_EUCLIDEAN)
+      GGNN_BF_MFMA(f16_t, kL2);
+    else
+      GGNN_BF_MFMA(f16_t, kCos);
+  }
+  else if (a.dtype == GGNN_BF16) {
+    if (a.measure == GGNN_EUCLIDEAN)
+      GGNN_BF_MFMA(bf16_t, kL2);
+    else
+      GGNN_BF_MFMA(bf16_t, kCos);
   }
   else {
     if (a.measure == GGNN_EUCLIDEAN)

@@ -36,6 +36,27 @@ struct Error : std::runtime_error {
       throw ::ggnn_amd::Error((status), (msg)); \
   } while (0)
 
+// bytes per element of a base / query row (every dtype the C-ABI accepts)
+inline size_t dtype_size(ggnn_dtype t)
+{
+  switch (t) {
+    case GGNN_F32: return 4;
+    case GGNN_U8: return 1;
+    case GGNN_F16:
+    case GGNN_BF16: return 2;
+  }
+  throw Error(GGNN_INVALID_ARGUMENT, "unknown dtype");
+}
+// elements per 16-byte chunk: the unit of every row load and of the row padding
+inline uint32_t dtype_elems_per_chunk(ggnn_dtype t)
+{
+  return 16u / static_cast<uint32_t>(dtype_size(t));
+}
+inline bool dtype_is_16bit(ggnn_dtype t)
+{
+  return t == GGNN_F16 || t == GGNN_BF16;
+}
+
 // include/ggnn/base/def.h:37-62 of the reference (host helpers, restated)
 inline uint32_t bit_ceil_u32(uint32_t v)
 {

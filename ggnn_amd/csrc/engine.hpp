@@ -143,11 +143,6 @@ struct EventTimer {
   }
 };
 
-inline size_t dtype_size(ggnn_dtype t)
-{
-  return t == GGNN_F32 ? 4 : 1;
-}
-
 // graph pool of one shard, reference layout (src/ggnn/base/graph.cpp:48-91):
 // [N_all x K int32 graph][ST_all int32 translation][ST_all int32 selection][2 float nn1_stats]
 struct Shard {

@@ -35,11 +35,13 @@ struct MergeArgs {
 constexpr uint32_t kMergeCache = 256;      // merge_layer.cuh:44
 constexpr uint32_t kMergeIterations = 200; // merge_layer.cuh:43
 
+#ifndef GGNN_ROWS_16_TU
 uint32_t merge_sorted_size(uint32_t KBuild)
 {
   // merge_layer.cuh:68-69 (CACHE_SIZE = 256 < 512)
   return std::max(64u, next_multiple32(KBuild + 1 + 16));
 }
+#endif
 
 #ifndef GGNN_MERGE_WAVES_EARLY
 #define GGNN_MERGE_WAVES_EARLY 6   // see GGNN_QUERY_WAVES_EARLY (query.hip)
@@ -285,6 +287,11 @@ static void launch_merge_cfg(const MergeArgs& args, bool use_ps, ggnn_measure me
     launch_merge_r<BaseT, LPR, NCH, kCos, NoPrescreen>(args, stream);
 }
 
+#ifndef GGNN_ROWS_16_TU
+// float16 / bfloat16 rows (no pre-screen): merge_16.hip
+void launch_merge_16(const MergeArgs& args, ggnn_measure measure, ggnn_dtype dtype,
+                     hipStream_t stream);
+
 void launch_merge(const MergeLaunch& a, hipStream_t stream)
 {
   const ggnn_graph_config& c = a.cfg;
@@ -330,10 +337,27 @@ void launch_merge(const MergeLaunch& a, hipStream_t stream)
     args.ps_params = a.ps_params;
     args.ps_Dc = a.ps_Dc;
   }
+  if (dtype_is_16bit(a.dtype)) {
+    launch_merge_16(args, a.measure, a.dtype, stream);
+  }
+  else {
 #define GGNN_LAUNCH_MERGE(T, LPR, NCH) launch_merge_cfg<T, LPR, NCH>(args, use_ps, a.measure, stream)
-  GGNN_DISPATCH_DIST(a.dtype, c.D, GGNN_LAUNCH_MERGE);
+    GGNN_DISPATCH_DIST_32_8(a.dtype, c.D, GGNN_LAUNCH_MERGE);
 #undef GGNN_LAUNCH_MERGE
+  }
   GGNN_HIP_CHECK(hipGetLastError());
 }
+
+#else  // GGNN_ROWS_16_TU
+
+void launch_merge_16(const MergeArgs& args, ggnn_measure measure, ggnn_dtype dtype,
+                     hipStream_t stream)
+{
+#define GGNN_LAUNCH_MERGE(T, LPR, NCH) launch_merge_cfg<T, LPR, NCH>(args, false, measure, stream)
+  GGNN_DISPATCH_DIST_16(dtype, args.D, GGNN_LAUNCH_MERGE);
+#undef GGNN_LAUNCH_MERGE
+}
+
+#endif  // GGNN_ROWS_16_TU
 
 }  // namespace ggnn_amd

@@ -265,6 +265,7 @@ __global__ void __launch_bounds__(kWave) query_kernel_lds(const QueryArgs a)
   }
 }
 
+#ifndef GGNN_ROWS_16_TU
 void query_sizing(uint32_t D, uint32_t k_query, uint32_t max_iterations, uint32_t* cache_size,
                   uint32_t* sorted_size)
 {
@@ -279,6 +280,7 @@ void query_sizing(uint32_t D, uint32_t k_query, uint32_t max_iterations, uint32_
   *cache_size = cache;
   *sorted_size = std::max(cache < 512u ? 64u : 32u, required_sorted);
 }
+#endif
 
 template <typename BaseT, int LPR, int NCH, int MODE, class PSC>
 static void launch_query_lds(const QueryArgs& args, uint32_t sorted, hipStream_t stream);
@@ -431,6 +433,11 @@ static void launch_query_cfg(const QueryArgs& args, bool use_ps, ggnn_measure me
     launch_query_r<BaseT, LPR, NCH, kCos, NoPrescreen>(args, args.sorted, stream);
 }
 
+#ifndef GGNN_ROWS_16_TU
+// float16 / bfloat16 rows (no pre-screen): query_16.hip
+void launch_query_16(const QueryArgs& args, ggnn_measure measure, ggnn_dtype dtype,
+                     hipStream_t stream);
+
 void launch_query(const QueryLaunch& a, hipStream_t stream)
 {
   if (a.Nq == 0)
@@ -514,9 +521,14 @@ void launch_query(const QueryLaunch& a, hipStream_t stream)
     args.ps_Dc = a.ps_Dc;
   }
 
+  if (dtype_is_16bit(a.dtype)) {
+    launch_query_16(args, a.measure, a.dtype, stream);
+  }
+  else {
 #define GGNN_LAUNCH_QUERY(T, LPR, NCH) launch_query_cfg<T, LPR, NCH>(args, use_ps, a.measure, stream)
-  GGNN_DISPATCH_DIST(a.dtype, a.D, GGNN_LAUNCH_QUERY);
+    GGNN_DISPATCH_DIST_32_8(a.dtype, a.D, GGNN_LAUNCH_QUERY);
 #undef GGNN_LAUNCH_QUERY
+  }
   GGNN_HIP_CHECK(hipGetLastError());
 }
 
@@ -533,5 +545,17 @@ extern "C" int ggnn_debug_phase_cycles(unsigned long long* out16, int reset)
   return 0;
 }
 #endif
+
+#else  // GGNN_ROWS_16_TU
+
+void launch_query_16(const QueryArgs& args, ggnn_measure measure, ggnn_dtype dtype,
+                     hipStream_t stream)
+{
+#define GGNN_LAUNCH_QUERY(T, LPR, NCH) launch_query_cfg<T, LPR, NCH>(args, false, measure, stream)
+  GGNN_DISPATCH_DIST_16(dtype, args.D, GGNN_LAUNCH_QUERY);
+#undef GGNN_LAUNCH_QUERY
+}
+
+#endif  // GGNN_ROWS_16_TU
 
 }  // namespace ggnn_amd

@@ -31,11 +31,13 @@ struct SymArgs {
 constexpr uint32_t kSymCache = 128;          // sym_query_layer.cuh:43
 constexpr uint32_t kSymPathIterations = 20;  // sym_query_layer.cuh:42
 
+#ifndef GGNN_ROWS_16_TU
 uint32_t sym_sorted_size(uint32_t KBuild)
 {
   // sym_query_layer.cuh:63-64
   return std::max(64u, next_multiple32(KBuild / 2 + 16));
 }
+#endif
 
 // query + "half" point distance engine (simple_knn_sym_cache.cuh:143-283)
 template <typename BaseT, int LPR, int NCH>
@@ -373,6 +375,7 @@ static void launch_sym_cfg(const SymArgs& args, bool use_ps, ggnn_measure measur
     launch_sym_r<BaseT, LPR, NCH, kCos, NoPrescreen>(args, stream);
 }
 
+#ifndef GGNN_ROWS_16_TU
 // deterministic mode, second step: the requests of launch_sym in ascending order (point, then its
 // local neighbour), each at the first of its candidates whose slot counter is below KF -- the
 // schedule of one point per launch, without the in-pass reads.  A request whose point already
@@ -429,6 +432,9 @@ void launch_sym_assign(uint32_t KBuild, uint32_t N_layer, const int32_t* request
   GGNN_HIP_CHECK(hipGetLastError());
 }
 
+// float16 / bfloat16 rows (no pre-screen): sym_16.hip
+void launch_sym_16(const SymArgs& args, ggnn_measure measure, ggnn_dtype dtype, hipStream_t stream);
+
 void launch_sym(const SymLaunch& a, hipStream_t stream)
 {
   check_vector_layout(a.base, a.D, a.dtype);
@@ -461,10 +467,26 @@ void launch_sym(const SymLaunch& a, hipStream_t stream)
     args.ps_params = a.ps_params;
     args.ps_Dc = a.ps_Dc;
   }
+  if (dtype_is_16bit(a.dtype)) {
+    launch_sym_16(args, a.measure, a.dtype, stream);
+  }
+  else {
 #define GGNN_LAUNCH_SYM(T, LPR, NCH) launch_sym_cfg<T, LPR, NCH>(args, use_ps, a.measure, stream)
-  GGNN_DISPATCH_DIST(a.dtype, a.D, GGNN_LAUNCH_SYM);
+    GGNN_DISPATCH_DIST_32_8(a.dtype, a.D, GGNN_LAUNCH_SYM);
 #undef GGNN_LAUNCH_SYM
+  }
   GGNN_HIP_CHECK(hipGetLastError());
 }
+
+#else  // GGNN_ROWS_16_TU
+
+void launch_sym_16(const SymArgs& args, ggnn_measure measure, ggnn_dtype dtype, hipStream_t stream)
+{
+#define GGNN_LAUNCH_SYM(T, LPR, NCH) launch_sym_cfg<T, LPR, NCH>(args, false, measure, stream)
+  GGNN_DISPATCH_DIST_16(dtype, args.D, GGNN_LAUNCH_SYM);
+#undef GGNN_LAUNCH_SYM
+}
+
+#endif  // GGNN_ROWS_16_TU
 
 }  // namespace ggnn_amd

@@ -1092,6 +1092,47 @@ struct ChunkOf<uint8_t> {
   }
 };
 
+// 16-bit rows (GGNN_F16 / GGNN_BF16): element types of their own, 2 bytes of storage each; a
+// chunk is 8 elements in one uint4.  get() widens one element to float32 exactly where it is
+// used (no chunk is widened up front: 8 floats per chunk would double the registers of the rows
+// in flight); everything after it is the float32 arithmetic of the generic path.
+struct f16_t {
+  uint16_t bits;
+};
+struct bf16_t {
+  uint16_t bits;
+};
+template <>
+struct ChunkOf<f16_t> {
+  using type = uint4;
+  static constexpr int EPC = 8;
+  static GGNN_DEV float get(const uint4& v, int e)
+  {
+    const uint32_t w = (e >> 1) == 0 ? v.x : (e >> 1) == 1 ? v.y : (e >> 1) == 2 ? v.z : v.w;
+    // v_cvt_f32_f16 (the high half through SDWA): exact
+    return static_cast<float>(__builtin_bit_cast(_Float16, static_cast<uint16_t>((e & 1) ? w >> 16 : w)));
+  }
+  static GGNN_DEV uint4 zero()
+  {
+    return make_uint4(0u, 0u, 0u, 0u);
+  }
+};
+template <>
+struct ChunkOf<bf16_t> {
+  using type = uint4;
+  static constexpr int EPC = 8;
+  static GGNN_DEV float get(const uint4& v, int e)
+  {
+    const uint32_t w = (e >> 1) == 0 ? v.x : (e >> 1) == 1 ? v.y : (e >> 1) == 2 ? v.z : v.w;
+    // bfloat16 is the high half of a float32: a shift or a mask, exact
+    return __uint_as_float((e & 1) ? (w & 0xffff0000u) : (w << 16));
+  }
+  static GGNN_DEV uint4 zero()
+  {
+    return make_uint4(0u, 0u, 0u, 0u);
+  }
+};
+
 enum DistMode { kL2 = 0, kCos = 1 };
 
 // QL: the query chunks live in LDS (q_lds[c * LPR + g], LPR * NCH chunks = one padded row per
@@ -1213,7 +1254,13 @@ struct DistEngine {
     b = 0.f;
 #pragma unroll
     for (int c = 0; c < NCH; ++c) {
-      const Chunk qc = qchunk(c);
+      Chunk qc = qchunk(c);
+      if constexpr (EPC == 8) {
+        // 16-bit rows: the query chunk is widened again for every row.  Without the opaque copy
+        // the compiler widens it once and keeps the 8 floats per chunk live across all rows in
+        // flight: twice the registers of the packed chunk, and the two-chunk kernels spill.
+        asm volatile("" : "+v"(qc.x), "+v"(qc.y), "+v"(qc.z), "+v"(qc.w));
+      }
 #pragma unroll
       for (int e = 0; e < EPC; ++e) {
         const float o = ChunkOf<BaseT>::get(v[c], e);
@@ -1821,7 +1868,7 @@ struct DistConfig {
 };
 inline DistConfig pick_dist_config(uint32_t D, ggnn_dtype dtype)
 {
-  const uint32_t epc = dtype == GGNN_F32 ? 4 : 16;
+  const uint32_t epc = dtype_elems_per_chunk(dtype);
   const uint32_t chunks = (D + epc - 1) / epc;
   if (chunks <= 8)
     return {8, 1};
@@ -1841,37 +1888,58 @@ inline DistConfig pick_dist_config(uint32_t D, ggnn_dtype dtype)
   return {64, 16};
 }
 
+// dispatch a functor templated on <BaseT, LPR, NCH> over the seven layouts of one element type
+#define GGNN_DISPATCH_LAYOUT(T, _dc, F)                                            \
+  do {                                                                            \
+    if ((_dc).lpr == 8 && (_dc).nch == 1) { F(T, 8, 1); }                         \
+    else if ((_dc).lpr == 8 && (_dc).nch == 2) { F(T, 8, 2); }                    \
+    else if ((_dc).lpr == 8 && (_dc).nch == 3) { F(T, 8, 3); }                    \
+    else if ((_dc).lpr == 16 && (_dc).nch == 2) { F(T, 16, 2); }                  \
+    else if ((_dc).lpr == 16 && (_dc).nch == 4) { F(T, 16, 4); }                  \
+    else if ((_dc).lpr == 64 && (_dc).nch == 4) { F(T, 64, 4); }                  \
+    else { F(T, 64, 16); }                                                        \
+  } while (0)
+
 // dispatch a functor templated on <BaseT, LPR, NCH>
 #define GGNN_DISPATCH_DIST(dtype, D, F)                                           \
   do {                                                                            \
     const ::ggnn_amd::DistConfig _dc = ::ggnn_amd::pick_dist_config((D), (dtype)); \
-    if ((dtype) == GGNN_F32) {                                                    \
-      if (_dc.lpr == 8 && _dc.nch == 1) { F(float, 8, 1); }                       \
-      else if (_dc.lpr == 8 && _dc.nch == 2) { F(float, 8, 2); }                  \
-      else if (_dc.lpr == 8 && _dc.nch == 3) { F(float, 8, 3); }                  \
-      else if (_dc.lpr == 16 && _dc.nch == 2) { F(float, 16, 2); }                \
-      else if (_dc.lpr == 16 && _dc.nch == 4) { F(float, 16, 4); }                \
-      else if (_dc.lpr == 64 && _dc.nch == 4) { F(float, 64, 4); }                \
-      else { F(float, 64, 16); }                                                  \
-    }                                                                             \
-    else {                                                                        \
-      if (_dc.lpr == 8 && _dc.nch == 1) { F(uint8_t, 8, 1); }                     \
-      else if (_dc.lpr == 8 && _dc.nch == 2) { F(uint8_t, 8, 2); }                \
-      else if (_dc.lpr == 8 && _dc.nch == 3) { F(uint8_t, 8, 3); }                \
-      else if (_dc.lpr == 16 && _dc.nch == 2) { F(uint8_t, 16, 2); }              \
-      else if (_dc.lpr == 16 && _dc.nch == 4) { F(uint8_t, 16, 4); }              \
-      else if (_dc.lpr == 64 && _dc.nch == 4) { F(uint8_t, 64, 4); }              \
-      else { F(uint8_t, 64, 16); }                                                \
-    }                                                                             \
+    if ((dtype) == GGNN_F32)                                                      \
+      GGNN_DISPATCH_LAYOUT(float, _dc, F);                                        \
+    else if ((dtype) == GGNN_F16)                                                 \
+      GGNN_DISPATCH_LAYOUT(::ggnn_amd::f16_t, _dc, F);                            \
+    else if ((dtype) == GGNN_BF16)                                                \
+      GGNN_DISPATCH_LAYOUT(::ggnn_amd::bf16_t, _dc, F);                           \
+    else                                                                          \
+      GGNN_DISPATCH_LAYOUT(uint8_t, _dc, F);                                      \
+  } while (0)
+
+// the same for float32 and uint8 rows only: query / merge / sym compile their 16-bit kernels in
+// translation units of their own (query_16.hip, merge_16.hip, sym_16.hip), built in parallel
+#define GGNN_DISPATCH_DIST_32_8(dtype, D, F)                                      \
+  do {                                                                            \
+    const ::ggnn_amd::DistConfig _dc = ::ggnn_amd::pick_dist_config((D), (dtype)); \
+    if ((dtype) == GGNN_F32)                                                      \
+      GGNN_DISPATCH_LAYOUT(float, _dc, F);                                        \
+    else                                                                          \
+      GGNN_DISPATCH_LAYOUT(uint8_t, _dc, F);                                      \
+  } while (0)
+#define GGNN_DISPATCH_DIST_16(dtype, D, F)                                        \
+  do {                                                                            \
+    const ::ggnn_amd::DistConfig _dc = ::ggnn_amd::pick_dist_config((D), (dtype)); \
+    if ((dtype) == GGNN_F16)                                                      \
+      GGNN_DISPATCH_LAYOUT(::ggnn_amd::f16_t, _dc, F);                            \
+    else                                                                          \
+      GGNN_DISPATCH_LAYOUT(::ggnn_amd::bf16_t, _dc, F);                           \
   } while (0)
 
 inline void check_vector_layout(const void* base, uint32_t D, ggnn_dtype dtype)
 {
-  const uint32_t epc = dtype == GGNN_F32 ? 4 : 16;
+  const uint32_t epc = dtype_elems_per_chunk(dtype);
   GGNN_REQUIRE(D >= 1 && D <= 4096, GGNN_INVALID_ARGUMENT, "D must be in [1, 4096]");
   GGNN_REQUIRE(D % epc == 0, GGNN_UNSUPPORTED,
                "this build needs D to be a multiple of 16 bytes per row "
-               "(4 for float32, 16 for uint8)");
+               "(4 for float32, 8 for float16 / bfloat16, 16 for uint8)");
   GGNN_REQUIRE((reinterpret_cast<uintptr_t>(base) & 15u) == 0, GGNN_INVALID_ARGUMENT,
                "base/query pointers must be 16-byte aligned");
 }

@@ -13,12 +13,15 @@ from ._lib import GraphConfig, check, lib
 EUCLIDEAN, COSINE = 0, 1
 
 
+_DTYPE_CODES = {torch.float32: _lib.F32, torch.uint8: _lib.U8, torch.float16: _lib.F16,
+                torch.bfloat16: _lib.BF16}
+
+
 def _dtype_code(t):
-    if t.dtype == torch.float32:
-        return _lib.F32
-    if t.dtype == torch.uint8:
-        return _lib.U8
-    raise TypeError("base/query must be float32 or uint8")
+    code = _DTYPE_CODES.get(t.dtype)
+    if code is None:
+        raise TypeError("base/query must be float32, uint8, float16 or bfloat16")
+    return code
 
 
 def _ptr(t):
@@ -67,9 +70,9 @@ def query_sizing(D, k_query, max_iterations):
 
 def dist_layout(D, dtype):
     """(lanes per row, 16-byte chunks per lane) of the distance kernels for rows of D elements of
-    `dtype` (torch.float32 / torch.uint8)"""
+    `dtype` (torch.float32 / torch.uint8 / torch.float16 / torch.bfloat16)"""
     import ctypes as C
-    code = {torch.float32: _lib.F32, torch.uint8: _lib.U8}[dtype]
+    code = _DTYPE_CODES[dtype]
     lpr, nch = C.c_uint32(), C.c_uint32()
     check(lib().ggnn_op_dist_layout(D, code, C.byref(lpr), C.byref(nch)))
     return lpr.value, nch.value

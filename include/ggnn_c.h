@@ -41,8 +41,14 @@ typedef enum {
 
 /* include/ggnn/base/def.h:27-30 */
 typedef enum { GGNN_EUCLIDEAN = 0, GGNN_COSINE = 1 } ggnn_measure;
-/* include/ggnn/base/dataset.cuh (DataType): base / query element type */
-typedef enum { GGNN_F32 = 0, GGNN_U8 = 1 } ggnn_dtype;
+/* include/ggnn/base/dataset.cuh (DataType): base / query element type.
+ * GGNN_F16 (IEEE binary16) and GGNN_BF16 (bfloat16) have no reference counterpart: the kernels
+ * widen every element exactly to float32 and compute all distances in float32 with the
+ * operations of the float32 path (no intermediate is rounded to 16 bits), so a 16-bit base gives
+ * the results of a float32 base holding the widened values.  Distances returned stay float32.
+ * Rows are padded to 16 bytes as for the other types (8 elements).  No pre-screen: see
+ * ggnn_set_prescreen. */
+typedef enum { GGNN_F32 = 0, GGNN_U8 = 1, GGNN_F16 = 2, GGNN_BF16 = 3 } ggnn_dtype;
 /* include/ggnn/base/data.cuh (MemoryLocation) reduced to what the boundary needs */
 typedef enum { GGNN_CPU = 0, GGNN_GPU = 1 } ggnn_location;
 
@@ -195,7 +201,8 @@ typedef struct {
 ggnn_status ggnn_last_build_work(const ggnn_t* h, ggnn_build_work* out);
 /* Exact pre-screen of the float32 query and merge kernels (no reference counterpart; results
  * are identical with it on or off, see ggnn_op_prescreen_encode).  On by default; hook PRESCREEN = 0
- * (ggnn_set_hook) turns the default of handles created afterwards off. */
+ * (ggnn_set_hook) turns the default of handles created afterwards off.  Accepted on a uint8,
+ * float16 or bfloat16 base, where it has no effect (those rows have no pre-screen codes). */
 ggnn_status ggnn_set_prescreen(ggnn_t* h, int enable);
 /* Deterministic build (no reference counterpart; the reference's build is not reproducible:
  * cuRAND stream graph_construction.cu:96-102,168-169, atomics and cross-block reads in sym
