@@ -1,13 +1,20 @@
 #!/usr/bin/env python3
 """Benchmark of the hot path: queries/sec at recall@10 on a SIFT1M-shaped base (+ build time).
 
-    python bench.py --gpus 1 --steps 20 --warmup 3 [--dump-outputs DIR]
+    python bench.py --gpus 1 --steps 20 --warmup 3 [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
-        --master-port P bench.py --gpus N --steps K --warmup W
+        --master-port P bench.py --gpus N --steps K --warmup W [--full]
 
 A "step" is one pass of the hot path over one batch of synthetic input: `query()` of the whole
 query set (10 000 x 128 f32, k=10) against the resident graph; inputs are in HBM when the timed
 region starts.
+
+A plain run does only what the headline needs: it generates the data, builds the graph, computes
+the exact ground truth, warms up, times the steps, writes --dump-outputs and prints the line
+(`value`, `ms_per_step`, the recall of the last step, build time, kernel time of the steps).
+Everything else below -- held-out recall, roofline and work counters, the pre-screen-off and
+asynchronous checks, other bases, the one-GPU point of the multi-GPU series, the one-handle form,
+the CPU baseline -- runs only with --full, after the timed steps, as before.
 
 N = 1: BASELINE.json configs[1] (1M x 128 f32, k_build 24, tau_b 0.5; k = 10) on one MI355X.
 N > 1: STRONG scaling on the north star's FIXED base: 100M points = 8 shards x 12.5M x 96 f32
@@ -22,7 +29,7 @@ the SAME base in the same three modes (all 8 shards resident on rank 0's GPU, me
 same run) with the like-with-like speed-ups, the one-handle form (set_gpus([...]), in-engine
 RCCL; a child process of rank 0) and the aggregate HBM roofline figure.
 
-Rank 0 prints ONE JSON line (contract in the task statement) with two extra objects:
+Rank 0 prints ONE JSON line; with --full it carries two extra objects:
   roofline     -- SURVEY 8(d): the query kernel's own algorithmic bytes per launch (from its live
                   work counters) / its live HIP-event duration / the 8 TB/s HBM peak; the
                   reference algorithm's bytes (n_dist x 4D, what the kernel avoids moving), the
@@ -714,10 +721,11 @@ def run_single(args, device, ggnn):
 
     # ground truth by exact brute force on the same data (untimed)
     gt, _ = eng.bf_query(query, args.k, measure)
-    # its time is reported from a second call: the first one also grows the scratch pool
-    eng.bf_query(query, args.k, measure)
-    bf_ms = eng.last_timing_ms()["bf_query_ms"]
-    bf_rescanned = eng.last_bf_query_rescanned()
+    if args.full:
+        # its time is reported from a second call: the first one also grows the scratch pool
+        eng.bf_query(query, args.k, measure)
+        bf_ms = eng.last_timing_ms()["bf_query_ms"]
+        bf_rescanned = eng.last_bf_query_rescanned()
 
     for _ in range(args.warmup):
         step()
@@ -734,6 +742,25 @@ def run_single(args, device, ggnn):
 
     recall = recall_at_k(ids, gt)
     c1 = (ids[:, 0] == gt[:, 0]).float().mean().item()
+    nq, d, k = args.n_query, args.dim, args.k
+    ms_per_step = elapsed / args.steps * 1000.0
+    value = nq / (elapsed / args.steps)
+    avg_kernel_ms = float(np.mean(kernel_ms))
+    head = {
+        "metric": "queries/sec @ recall@10 (SIFT1M-shaped, k=10)",
+        "value": value, "unit": "queries/s", "n_gpus": 1, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": ms_per_step, "higher_is_better": True,
+        "scaling": "strong", "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
+        "config": {"workload": workload_string(args), "parallelism": "single GPU",
+                   "operating_point": {"tau_query": args.tau_query, "max_iterations": args.max_iters,
+                                       "source": getattr(args, "operating_point_source", None)}},
+        "full": args.full, "recall_at_10": recall, "c_at_1": c1,
+        "graph_build_s": build_kernel_s, "graph_build_wall_s": build_wall_s,
+        "searched_graph": searched_graph, "query_kernel_ms": avg_kernel_ms,
+    }
+    if not args.full:
+        print(json.dumps(head), flush=True)
+        return
 
     # the operating point was chosen on the query set above (seed 4321); a query set it has never
     # seen tells whether the recall figure generalises
@@ -802,10 +829,7 @@ def run_single(args, device, ggnn):
                      "results": "bit-identical to the blocking calls"}
         del outs
 
-    nq, d, k = args.n_query, args.dim, args.k
     esz = 1 if args.dtype == "u8" else 4
-    ms_per_step = elapsed / args.steps * 1000.0
-    value = nq / (elapsed / args.steps)
     # bytes_q = D*s + n_dist*D*s + n_pop*KBuild*4 + S*4 + 8 + K*8 is what the
     # reference's algorithm moves.  With the exact pre-screen a distance evaluation
     # reads a D-byte code row and only the candidates that pass it read their 4D-byte float row:
@@ -818,7 +842,6 @@ def run_single(args, device, ggnn):
     alg_bytes = fixed + rows["float_rows"] * d * esz + rows["code_rows"] * code_dim
     if prescreened:
         alg_bytes += nq * (code_dim + 8) * 4  # per-dimension offsets + header, per query
-    avg_kernel_ms = float(np.mean(kernel_ms))
     t_kernel = avg_kernel_ms * 1e-3
     alg_gbs = alg_bytes / t_kernel / 1e9
     traffic = pmc_traffic(args, prescreened)
@@ -880,28 +903,18 @@ def run_single(args, device, ggnn):
         "results": "bit-identical to the pre-screened run"})
 
     lid = local_intrinsic_dimension(eng, base, args)
-    out = {
-        "metric": "queries/sec @ recall@10 (SIFT1M-shaped, k=10)",
-        "value": value, "unit": "queries/s", "n_gpus": 1, "steps": args.steps,
-        "warmup": args.warmup, "ms_per_step": ms_per_step, "higher_is_better": True,
-        "scaling": "strong", "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
-        "config": {"workload": workload_string(args), "parallelism": "single GPU",
-                   "operating_point": {"tau_query": args.tau_query, "max_iterations": args.max_iters,
-                                       "source": getattr(args, "operating_point_source", None)}},
-        "recall_at_10": recall, "recall_at_10_heldout_queries": recall_heldout, "c_at_1": c1,
+    out = dict(head, **{
+        "recall_at_10_heldout_queries": recall_heldout,
         "base_local_intrinsic_dimension": lid,
-        "graph_build_s": build_kernel_s, "graph_build_wall_s": build_wall_s,
-        "searched_graph": searched_graph,
         "bf_query_ms": bf_ms,
         "bf_query": bf_block(args, bf_ms, bf_rescanned),
-        "query_kernel_ms": avg_kernel_ms,
         "n_dist_per_query": cnt["n_dist"] / nq, "n_pop_per_query": cnt["n_pop"] / nq,
         "saturated_batch": saturated,
         "pipelined_batches": pipelined,
         "float_rows_per_query": rows["float_rows"] / nq,
         "code_rows_per_query": rows["code_rows"] / nq,
         "roofline": roofline,
-    }
+    })
     plain_f32_l2 = (args.dtype, args.measure) == ("f32", "l2")
     if not args.no_build_roofline and plain_f32_l2:
         out["build"] = dict(build_roofline(args, ggnn, base), graph_build_s=build_kernel_s)
@@ -1065,7 +1078,17 @@ def sharded_case(args, device, world, rank, spg, cpu_group, xgroup=None, dump_di
     elapsed, = max_over_ranks(time.perf_counter() - t0)
     if dump_dir:
         dump_outputs(dump_dir, {"ids": ids, "dists": dists})
-    blocking_parts = sharded.last_query_parts
+    out = {"n_base_per_shard": args.n_base, "shards_per_gpu": spg,
+           "elapsed_s": elapsed, "ms_per_step": elapsed / args.steps * 1e3,
+           "queries_per_s": args.n_query / (elapsed / args.steps),
+           "blocking_half_batches_in_flight": sharded.last_query_parts,
+           "recall_at_10": recall_at_k(ids, gt),
+           "graph_build_s_per_gpu": build_kernel_s, "graph_build_wall_s": build_wall_s}
+    if not args.full:
+        del sharded, eng, base
+        torch.cuda.empty_cache()
+        barrier()
+        return out
     # the same steps as ONE batch each (the blocking mode of rounds 1-3; also the source of the
     # kernel time: the half-batches of the split run on the asynchronous lanes, which are not timed)
     sharded.split_blocking = False
@@ -1108,16 +1131,11 @@ def sharded_case(args, device, world, rank, spg, cpu_group, xgroup=None, dump_di
                               "own row counters, as in the N=1 line) / the slowest rank's summed "
                               "kernel time (HIP events) / (N x 8 TB/s); the exchange and merge "
                               "are in ms_per_step, not in this kernel figure"}
-    out = {"n_base_per_shard": args.n_base, "shards_per_gpu": spg, "roofline": roofline,
-           "elapsed_s": elapsed, "ms_per_step": elapsed / args.steps * 1e3,
-           "queries_per_s": args.n_query / (elapsed / args.steps),
-           "blocking_half_batches_in_flight": blocking_parts,
-           "blocking_as_one_batch": {"ms_per_step": elapsed_unsplit * 1e3,
-                                     "queries_per_s": args.n_query / elapsed_unsplit,
-                                     "results": "bit-identical to the split steps"},
-           "recall_at_10": recall_at_k(ids, gt),
-           "graph_build_s_per_gpu": build_kernel_s, "graph_build_wall_s": build_wall_s,
-           "query_kernel_ms_sum_over_local_shards": float(np.mean(kernel_ms))}
+    out.update(roofline=roofline,
+               blocking_as_one_batch={"ms_per_step": elapsed_unsplit * 1e3,
+                                      "queries_per_s": args.n_query / elapsed_unsplit,
+                                      "results": "bit-identical to the split steps"},
+               query_kernel_ms_sum_over_local_shards=float(np.mean(kernel_ms)))
 
     # informational, never part of `value`; every rank takes part in every reduction whether or
     # not its own attempt worked
@@ -1294,7 +1312,8 @@ def run_sharded(args, device, ggnn, world, rank):
     skipped = []
     # secondary series: 8 shards of the N=1 configuration's shape (SIFT1M-shaped rows of 128)
     series = [(main_base, main_dim)]
-    if args.secondary_n_base and (args.secondary_n_base, 128) != (main_base, main_dim):
+    if (args.full and args.secondary_n_base
+            and (args.secondary_n_base, 128) != (main_base, main_dim)):
         series.append((args.secondary_n_base, 128))
     for n_base, dim in series:
         if (n_base, dim) != (main_base, main_dim) and not still_time(args.optional_budget_s + 90):
@@ -1308,7 +1327,7 @@ def run_sharded(args, device, ggnn, world, rank):
         case["dim"] = dim
         # the one-GPU point of the series on the SAME base, measured by rank 0 while the others wait
         one = None
-        if rank == 0 and not args.no_scaling_reference:
+        if rank == 0 and args.full and not args.no_scaling_reference:
             try:
                 one = one_gpu_reference(args, device, ggnn, ref_steps)
             except Exception as e:  # e.g. not enough free memory next to another job: keep the line
@@ -1316,7 +1335,7 @@ def run_sharded(args, device, ggnn, world, rank):
         barrier()
         # ... and the one-handle form (in-engine RCCL) in a child process of rank 0
         inproc = None
-        if not args.no_in_process and (n_base, dim) == (main_base, main_dim):
+        if args.full and not args.no_in_process and (n_base, dim) == (main_base, main_dim):
             if still_time(args.optional_budget_s):
                 if rank == 0:
                     inproc = in_process_child(args, n_base, args.in_process_timeout)
@@ -1358,25 +1377,31 @@ def run_sharded(args, device, ggnn, world, rank):
             "recall_at_10": main["recall_at_10"],
             "graph_build_s_per_gpu": main["graph_build_s_per_gpu"],
             "graph_build_wall_s": main["graph_build_wall_s"],
-            "query_kernel_ms_sum_over_local_shards": main["query_kernel_ms_sum_over_local_shards"],
-            "one_gpu_same_base": main["one_gpu_same_base"],
-            "speedup_vs_one_gpu_same_base": sp.get("blocking"),
-            "saturated_batch": main.get("saturated_batch"),
-            "saturated_speedup_vs_one_gpu_same_base": sp.get("saturated_batch"),
-            "pipelined_batches": main.get("pipelined_batches"),
-            "pipelined_speedup_vs_one_gpu_same_base": sp.get("pipelined_batches"),
-            "in_process_handle": main.get("in_process_handle"),
-            "secondary_base": (None if len(cases) < 2 else dict(
-                cases[1], note=f"the same series on {TOTAL_SHARDS} x {cases[1]['n_base_per_shard']} "
-                               f"x {cases[1]['dim']} (8 shards of the N=1 configuration's shape)")),
-            "roofline": main.get("roofline"), "cpu_baseline": None,
-            "note": "N=1 of this command is the BASELINE single-shard configuration (1M points); "
-                    "the multi-GPU series keeps the BASE fixed (north star: 100M points) instead, "
-                    "so compare with one_gpu_same_base -- all 8 shards resident on one MI355X, "
-                    "measured by rank 0 in this same run -- not with the N=1 `value`; the three "
-                    "speed-ups compare like with like (blocking / 100k-query batch / two batches "
-                    "in flight)",
+            "full": args.full,
         }
+        if args.full:
+            out.update({
+                "query_kernel_ms_sum_over_local_shards":
+                    main["query_kernel_ms_sum_over_local_shards"],
+                "one_gpu_same_base": main["one_gpu_same_base"],
+                "speedup_vs_one_gpu_same_base": sp.get("blocking"),
+                "saturated_batch": main.get("saturated_batch"),
+                "saturated_speedup_vs_one_gpu_same_base": sp.get("saturated_batch"),
+                "pipelined_batches": main.get("pipelined_batches"),
+                "pipelined_speedup_vs_one_gpu_same_base": sp.get("pipelined_batches"),
+                "in_process_handle": main.get("in_process_handle"),
+                "secondary_base": (None if len(cases) < 2 else dict(
+                    cases[1], note=f"the same series on {TOTAL_SHARDS} x "
+                                   f"{cases[1]['n_base_per_shard']} x {cases[1]['dim']} "
+                                   f"(8 shards of the N=1 configuration's shape)")),
+                "roofline": main.get("roofline"), "cpu_baseline": None,
+                "note": "N=1 of this command is the BASELINE single-shard configuration (1M "
+                        "points); the multi-GPU series keeps the BASE fixed (north star: 100M "
+                        "points) instead, so compare with one_gpu_same_base -- all 8 shards "
+                        "resident on one MI355X, measured by rank 0 in this same run -- not with "
+                        "the N=1 `value`; the three speed-ups compare like with like (blocking / "
+                        "100k-query batch / two batches in flight)",
+            })
         for k_ in ("saturated_batch_error", "pipelined_error"):
             if k_ in main:
                 out[k_] = main[k_]
@@ -1386,18 +1411,23 @@ def run_sharded(args, device, ggnn, world, rank):
     dist.destroy_process_group()
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check everything besides the "
+                         "headline (held-out recall, roofline, other bases and operating points, "
+                         "the one-GPU point and the one-handle form of the multi-GPU series, the "
+                         "CPU baseline); the --no-* flags, --lean and --saturated-batch act on it")
     ap.add_argument("--n-base", type=int, default=None,
                     help="points per shard (default: 1M at N=1 = BASELINE configs[1]; 12.5M at "
                          "N>1 = the north star's 100M-point base in 8 shards)")
     ap.add_argument("--secondary-n-base", type=int, default=1_000_000,
-                    help="N>1: a second, smaller fixed base of 8 such shards (0: skip)")
+                    help="N>1, --full: a second, smaller fixed base of 8 such shards (0: skip)")
     ap.add_argument("--no-in-process", action="store_true",
-                    help="N>1: skip the one-handle set_gpus([...]) form (in-engine RCCL)")
+                    help="N>1, --full: skip the one-handle set_gpus([...]) form (in-engine RCCL)")
     ap.add_argument("--in-process", action="store_true",
                     help="run ONLY the one-handle form over --gpus GPUs in this process")
     ap.add_argument("--in-process-timeout", type=float, default=300.0)
@@ -1430,7 +1460,8 @@ def main():
     ap.add_argument("--no-scaling-reference", action="store_true",
                     help="skip the 8-shards-on-one-GPU point of the strong-scaling series")
     ap.add_argument("--lean", action="store_true",
-                    help="profiling runs: only the headline measurement (implies the --no-* flags)")
+                    help="with --full, for profiling runs: the headline measurement and its own "
+                         "roofline figures only (implies the --no-* flags)")
     ap.add_argument("--saturated-batch", action="store_true",
                     help="also time a 10x larger query batch (informational; off by default so "
                          "that a rocprofv3 --stats of the default command averages only "
@@ -1447,12 +1478,17 @@ def main():
                          "sample of rows beyond that); on one GPU the timed steps then search a "
                          "graph built with the deterministic sym schedule, so that the same "
                          "arguments give the same dump every run")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.steps < 1:
         ap.error("--steps must be at least 1")
     if args.lean:
         args.no_cpu_baseline = args.no_datasets = True
         args.no_build_roofline = args.no_scaling_reference = args.no_pipelined = True
+    return args
+
+
+def main():
+    args = parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))

@@ -1,12 +1,13 @@
-"""Condense rocprofv3 CSV output (gpurun_out/<tag>/) into the tracked summaries under profiles/."""
+"""Condense rocprofv3 CSV output (runs/<tag>/, scripts/profile_round.sh) into the tracked summaries
+under profiles/."""
 import collections, csv, json, os, sys
 
 tag = sys.argv[1] if len(sys.argv) > 1 else "r02"
-src = sys.argv[2] if len(sys.argv) > 2 else f"gpurun_out/{tag}"
+src = sys.argv[2] if len(sys.argv) > 2 else f"runs/{tag}"
 extra = sys.argv[3] if len(sys.argv) > 3 else ""
 out_dir = "profiles"
 os.makedirs(out_dir, exist_ok=True)
-CMD = "python bench.py --lean" + (" " + extra if extra else "")
+CMD = "python bench.py --full --lean" + (" " + extra if extra else "")
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from bench import kernel_source_sha, BUILD_SOURCES  # noqa: E402  (fingerprints of the profiled kernel sources)
 SHA = kernel_source_sha()

@@ -62,6 +62,16 @@ def test_speedups_compare_like_with_like():
     assert bench.speedups(case, {"error": "x"}) is None and bench.speedups(case, None) is None
 
 
+def test_full_is_off_by_default_and_lean_trims_it():
+    import bench
+    a = bench.parse_args(["--gpus", "1", "--steps", "5", "--warmup", "2"])
+    assert a.full is False and (a.steps, a.warmup) == (5, 2) and not a.no_cpu_baseline
+    b = bench.parse_args(["--full", "--lean"])
+    assert b.full is True
+    assert b.no_cpu_baseline and b.no_datasets and b.no_build_roofline
+    assert b.no_scaling_reference and b.no_pipelined
+
+
 def test_kernel_source_sha_is_stable_and_tracks_sources():
     import bench
     a = bench.kernel_source_sha()

@@ -1,9 +1,10 @@
 """Dry runs of every bench.py mode on the one-GPU test box, at toy sizes:
-  * `--gpus 2` under torch.distributed.run (two gloo ranks, both on GPU 0): the fixed-base series
-    with blocking / saturated / pipelined figures, the one-GPU point of the same base, the
+  * `--gpus 2 --full` under torch.distributed.run (two gloo ranks, both on GPU 0): the fixed-base
+    series with blocking / saturated / pipelined figures, the one-GPU point of the same base, the
     one-handle `--in-process` child (in-engine exchange) and the secondary base;
-  * the lean N = 1 line: `roofline` is the HBM own-bytes fraction, `cpu_baseline`
-    and the secondaries have their contracted shape.
+  * the `--full --lean` N = 1 line: `roofline` is the HBM own-bytes fraction,
+    `cpu_baseline` and the secondaries have their contracted shape;
+  * the plain N = 1 line (no --full): the headline fields only.
 These check plumbing and JSON contracts, not performance."""
 import json
 import os
@@ -28,7 +29,7 @@ def run(cmd, timeout=900):
 def test_bench_two_ranks_dry_run():
     out = run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                "--master-addr", "127.0.0.1", "--master-port", "29631", "bench.py", "--gpus", "2",
-               "--steps", "4", "--warmup", "1", "--backend", "gloo", "--single-device",
+               "--full", "--steps", "4", "--warmup", "1", "--backend", "gloo", "--single-device",
                "--n-base", "20000", "--secondary-n-base", "10000", "--n-query", "400",
                "--in-process-timeout", "300"])
     assert out["n_gpus"] == 2 and out["scaling"] == "strong" and out["value"] > 0
@@ -86,7 +87,7 @@ def test_bench_two_ranks_rccl_is_attempted_and_falls_back_loudly():
 
 
 def test_bench_lean_line_contract():
-    out = run([sys.executable, "bench.py", "--lean", "--steps", "3", "--warmup", "1",
+    out = run([sys.executable, "bench.py", "--full", "--lean", "--steps", "3", "--warmup", "1",
                "--n-base", "100000", "--n-query", "2000"])
     rl = out["roofline"]
     assert rl["bound"] == "hbm" and rl["unit"] == "GB/s" and rl["peak"] == 8000.0
@@ -99,8 +100,26 @@ def test_bench_lean_line_contract():
     assert out["dtype"] == "f32" and out["vs_baseline"] is None and out["cpu_baseline"] is None
 
 
+def test_bench_plain_line_is_the_headline_only(tmp_path):
+    """without --full the line carries the headline and nothing measured after the timed steps;
+    --dump-outputs still writes the last step's results"""
+    out = run([sys.executable, "bench.py", "--steps", "3", "--warmup", "1",
+               "--n-base", "100000", "--n-query", "2000", "--dump-outputs", str(tmp_path)])
+    assert out["full"] is False and out["n_gpus"] == 1 and out["steps"] == 3 and out["warmup"] == 1
+    assert out["metric"].startswith("queries/sec @ recall@10") and out["unit"] == "queries/s"
+    assert out["higher_is_better"] is True and out["dtype"] == "f32"
+    assert abs(out["value"] - 2000 / (out["ms_per_step"] * 1e-3)) < 1e-6 * out["value"]
+    assert out["recall_at_10"] > 0.95 and 0 < out["query_kernel_ms"] <= out["ms_per_step"]
+    for key in ("roofline", "cpu_baseline", "recall_at_10_heldout_queries", "bf_query",
+                "pipelined_batches", "recall_targets", "strong_scaling_one_gpu", "build"):
+        assert key not in out, key
+    import numpy as np
+    ids, dists = np.load(tmp_path / "ids.npy"), np.load(tmp_path / "dists.npy")
+    assert ids.shape == dists.shape == (2000, 10)
+
+
 def test_bench_u8_and_cosine_flags():
-    out = run([sys.executable, "bench.py", "--lean", "--steps", "2", "--warmup", "1",
+    out = run([sys.executable, "bench.py", "--full", "--lean", "--steps", "2", "--warmup", "1",
                "--n-base", "50000", "--n-query", "1000", "--dtype", "u8"])
     assert out["dtype"] == "u8" and "u8" in out["config"]["workload"]
     assert out["code_rows_per_query"] == 0 and out["roofline"]["frac"] > 0

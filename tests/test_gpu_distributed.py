@@ -65,15 +65,16 @@ def _json_line(stdout):
 
 
 def test_bench_two_ranks_strong_scaling_line(tmp_path):
-    """bench.py --gpus 2 as the driver launches it (torch.distributed.run, one rank per GPU), here
-    with both ranks on GPU 0 over gloo and a small base: the strong-scaling line must carry
+    """bench.py --gpus 2 --full as the driver launches it (torch.distributed.run, one rank per GPU),
+    here with both ranks on GPU 0 over gloo and a small base: the strong-scaling line must carry
     queries/s on the fixed 8-shard base, the one-GPU point of the same base and the speed-up."""
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     port = 29500 + (os.getpid() % 400) + 57
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"),
            "--gpus", "2", "--steps", "3", "--warmup", "1", "--backend", "gloo", "--single-device",
-           "--n-base", "20000", "--n-query", "600", "--tau-query", "1.0", "--max-iters", "400"]
+           "--n-base", "20000", "--n-query", "600", "--tau-query", "1.0", "--max-iters", "400",
+           "--full"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     d = _json_line(r.stdout)
@@ -92,9 +93,9 @@ def test_bench_two_ranks_strong_scaling_line(tmp_path):
 
 
 def test_bench_single_gpu_line_small():
-    """the N=1 line on a small base: contract fields, roofline and cpu_baseline objects, the
+    """the --full N=1 line on a small base: contract fields, roofline and cpu_baseline objects, the
     dataset block and the one-GPU point of the strong-scaling series"""
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "3", "--warmup", "1",
            "--n-base", "20000", "--n-query", "600", "--tau-query", "1.0", "--max-iters", "400"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
