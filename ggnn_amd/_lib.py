@@ -142,6 +142,9 @@ SIGNATURES = {
                            _u32, _vp]),
     "ggnn_op_sym_prescreened": (_int, [_vp, _vp, _vp, _int, _u32, _u32, _vp, _vp, _u32, _vp, _f32, _vp,
                                        _vp, _u32, _u32, _vp]),
+    "ggnn_op_sym_requests": (_int, [_vp, _int, _vp, _vp, _int, _u32, _u32, _vp, _vp, _u32, _vp, _f32,
+                                    _vp, _vp, _vp, _u32, _u32, _vp]),
+    "ggnn_op_sym_assign": (_int, [_u32, _u32, _vp, _vp, _vp, _vp]),
     "ggnn_op_sym_buffer_merge": (_int, [_u32, _u32, _vp, _vp, _vp, _vp]),
     "ggnn_nn1_stats_scratch_floats": (_sz, []),
     "ggnn_op_nn1_stats": (_int, [_vp, _u32, _vp, _vp, _vp]),

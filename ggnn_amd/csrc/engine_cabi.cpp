@@ -659,6 +659,43 @@ ggnn_status ggnn_op_sym_prescreened(const float* base, const uint8_t* codes, con
   });
 }
 
+ggnn_status ggnn_op_sym_requests(const void* base, ggnn_dtype dtype, const uint8_t* codes,
+                                 const float* params, ggnn_measure measure, uint32_t D,
+                                 uint32_t KBuild, const int32_t* graph_layer,
+                                 const int32_t* translation_layer, uint32_t N_layer,
+                                 const float* nn1_stats, float tau_build, int32_t* sym_buffer,
+                                 uint32_t* sym_atomic, int32_t* requests, uint32_t first_n,
+                                 uint32_t count, void* stream)
+{
+  return guarded(nullptr, [&] {
+    GGNN_REQUIRE(requests != nullptr, GGNN_INVALID_ARGUMENT, "requests is null");
+    GGNN_REQUIRE(!codes == !params, GGNN_INVALID_ARGUMENT,
+                 "pre-screen codes and params go together");
+    GGNN_REQUIRE(!codes || dtype == GGNN_F32, GGNN_INVALID_ARGUMENT,
+                 "the pre-screen needs a float32 base");
+    SymLaunch s{base,    dtype,     measure,   D,          KBuild,     graph_layer, translation_layer,
+                N_layer, nn1_stats, tau_build, sym_buffer, sym_atomic, first_n,     count};
+    if (codes) {
+      s.ps_codes = codes;
+      s.ps_params = params;
+      s.ps_Dc = prescreen_code_dim(D);
+    }
+    s.requests = requests;
+    launch_sym(s, static_cast<hipStream_t>(stream));
+  });
+}
+
+ggnn_status ggnn_op_sym_assign(uint32_t KBuild, uint32_t N_layer, const int32_t* requests,
+                               uint32_t* sym_atomic, int32_t* sym_buffer, void* stream)
+{
+  return guarded(nullptr, [&] {
+    GGNN_REQUIRE(requests && sym_atomic && sym_buffer, GGNN_INVALID_ARGUMENT,
+                 "sym_assign: null buffer");
+    launch_sym_assign(KBuild, N_layer, requests, sym_atomic, sym_buffer,
+                      static_cast<hipStream_t>(stream));
+  });
+}
+
 ggnn_status ggnn_op_sym_buffer_merge(uint32_t KBuild, uint32_t N_layer, int32_t* sym_buffer,
                                      const uint32_t* sym_atomic, int32_t* graph_layer,
                                      void* stream)

@@ -218,11 +218,25 @@ def uniform(n, seed=1234, stream_id=0, device="cuda"):
 
 
 def sym(base, KBuild, graph_layer, translation_layer, nn1_stats, tau_build, sym_buffer,
-        sym_atomic, measure=EUCLIDEAN, first_n=0, count=None, prescreen=None):
-    """prescreen: optional (codes, params) of prescreen_encode(base, measure) (float32)"""
+        sym_atomic, measure=EUCLIDEAN, first_n=0, count=None, prescreen=None, requests=None):
+    """prescreen: optional (codes, params) of prescreen_encode(base, measure) (float32);
+    requests: optional int32 [N_layer, KL, KF] tensor: the request pass of the deterministic sym
+    schedule, which fills it and leaves sym_buffer / sym_atomic alone (ggnn_op_sym_requests)"""
     N_layer = graph_layer.shape[0]
     if count is None:
         count = N_layer
+    if requests is not None:
+        KF = KBuild // 2
+        _need(requests, torch.int32, "requests")
+        if requests.numel() != N_layer * (KBuild - KF) * KF:
+            raise ValueError("requests must have N_layer x KL x KF entries")
+        codes, params = prescreen if prescreen is not None else (None, None)
+        check(lib().ggnn_op_sym_requests(_ptr(base), _dtype_code(base), _ptr(codes), _ptr(params),
+                                         measure, base.shape[1], KBuild, _ptr(graph_layer),
+                                         _ptr(translation_layer), N_layer, _ptr(nn1_stats),
+                                         tau_build, _ptr(sym_buffer), _ptr(sym_atomic),
+                                         _ptr(requests), first_n, count, _stream()))
+        return
     if prescreen is not None:
         codes, params = prescreen
         check(lib().ggnn_op_sym_prescreened(_ptr(base), _ptr(codes), _ptr(params), measure,
@@ -235,6 +249,18 @@ def sym(base, KBuild, graph_layer, translation_layer, nn1_stats, tau_build, sym_
                             _ptr(graph_layer), _ptr(translation_layer), N_layer, _ptr(nn1_stats),
                             tau_build, _ptr(sym_buffer), _ptr(sym_atomic), first_n, count,
                             _stream()))
+
+
+def sym_assign(KBuild, requests, sym_atomic, sym_buffer):
+    """assign step of the deterministic sym schedule (ggnn_op_sym_assign), in place on sym_atomic
+    [N_layer] / sym_buffer [N_layer, KF]"""
+    _need(requests, torch.int32, "requests"), _need(sym_buffer, torch.int32, "sym_buffer")
+    _need(sym_atomic, torch.int32, "sym_atomic")
+    N_layer, KF = sym_atomic.numel(), KBuild // 2
+    if sym_buffer.numel() != N_layer * KF or requests.numel() != N_layer * (KBuild - KF) * KF:
+        raise ValueError("sym_assign: sym_buffer is [N, KF], requests [N, KL, KF]")
+    check(lib().ggnn_op_sym_assign(KBuild, N_layer, _ptr(requests), _ptr(sym_atomic),
+                                   _ptr(sym_buffer), _stream()))
 
 
 def sym_buffer_merge(KBuild, sym_buffer, sym_atomic, graph_layer):

@@ -426,6 +426,28 @@ ggnn_status ggnn_op_sym_prescreened(const float* base, const uint8_t* codes, con
                                     int32_t* sym_buffer, uint32_t* sym_atomic, uint32_t first_n,
                                     uint32_t count, void* stream);
 
+/* The two steps of the deterministic sym schedule (ggnn_set_build_hooks, serial_sym = 2; no
+ * reference counterpart), for tests.
+ * Request pass: ggnn_op_sym / ggnn_op_sym_prescreened (codes and params non-null: float32 with
+ * the pre-screen, dtype must be GGNN_F32) with `requests` [N_layer x (KBuild - KBuild / 2) x
+ * KBuild / 2]: the searches treat the pending inverse links as empty and neither read nor write
+ * sym_buffer / sym_atomic (which may be null); per point and local neighbour the row is -1
+ * everywhere if the search met the point, else its best list, nearest first, -1 from the first
+ * unused entry on. */
+ggnn_status ggnn_op_sym_requests(const void* base, ggnn_dtype dtype, const uint8_t* codes,
+                                 const float* params, ggnn_measure measure, uint32_t D,
+                                 uint32_t KBuild, const int32_t* graph_layer,
+                                 const int32_t* translation_layer, uint32_t N_layer,
+                                 const float* nn1_stats, float tau_build, int32_t* sym_buffer,
+                                 uint32_t* sym_atomic, int32_t* requests, uint32_t first_n,
+                                 uint32_t count, void* stream);
+/* Assign step (one wave; a whole pass starts from sym_atomic = 0, sym_buffer = -1): the request
+ * rows in ascending (point n, local neighbour) order; the candidates c of a row up to the first
+ * -1 or id >= N_layer: if n is among sym_buffer[c][0 .. min(sym_atomic[c], KF)) the row is done;
+ * else pos = sym_atomic[c]++, and pos < KF stores n at sym_buffer[c][pos] and ends the row. */
+ggnn_status ggnn_op_sym_assign(uint32_t KBuild, uint32_t N_layer, const int32_t* requests,
+                               uint32_t* sym_atomic, int32_t* sym_buffer, void* stream);
+
 /* sym_buffer_merge  sym_buffer_merge_layer.cu:36-99 (sym_buffer is used as scratch) */
 ggnn_status ggnn_op_sym_buffer_merge(uint32_t KBuild, uint32_t N_layer, int32_t* sym_buffer,
                                      const uint32_t* sym_atomic, int32_t* graph_layer,

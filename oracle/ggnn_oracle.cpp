@@ -19,6 +19,7 @@
 #include <cmath>
 #include <cstring>
 #include <limits>
+#include <mutex>
 #include <thread>
 #include <vector>
 
@@ -752,6 +753,96 @@ inline uint32_t radix_key(float f)
   return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
 }
 
+// The KL searches of one point n (sym_query_layer.cu:59-119), one from every local neighbour
+// back to n.  `pending` [Nlayer x KF]: the inverse links requested so far, which end an anchor's
+// neighbour list (:102-104); null in the request pass of the deterministic schedule, where
+// they count as empty.  end_of_search(j, found, cache) runs after search j with the cache as the
+// search left it.  `margin`: smallest relative margin of a half-point decision (orc_margin_min).
+template <typename F>
+void sym_point_searches(const BaseView& b, int measure, uint32_t KBuild,
+                        const int32_t* graph_layer, const int32_t* translation, float xi,
+                        int32_t n, const int32_t* pending, double& margin, F&& end_of_search)
+{
+  constexpr uint32_t K_BLOCK = 32, MAX_PER_PATH_ITERATIONS = 20, CACHE_SIZE = 128;
+  const uint32_t KF = KBuild / 2, KL = KBuild - KF;
+  const uint32_t sorted_size = std::max(64u, next_multiple32(KBuild / 2 + 16));
+  uint32_t items;
+  const uint32_t block = orc_construction_block(b.D, 64, &items);
+  {
+    SymDist sd(b, measure, block, items);
+    sd.load_query((uint64_t)(translation ? translation[n] : n));
+    Cache cache(KF, sorted_size, CACHE_SIZE, block, xi);
+    float criteria_half = 0.f;
+    for (uint32_t i = 0; i < KL; i += K_BLOCK) {
+      int32_t s_sym_ids[K_BLOCK];
+      for (uint32_t t = 0; t < K_BLOCK && i + t < KL; ++t)
+        s_sym_ids[t] = graph_layer[(size_t)n * KBuild + i + t];
+      for (uint32_t k = 0; i + k < KL && k < K_BLOCK; ++k) {
+        bool connected = false;
+        {
+          // init_start_point, simple_knn_sym_cache.cuh:159-201
+          const int32_t other_n = s_sym_ids[k];
+          const int32_t other_m = translation ? translation[other_n] : other_n;
+          sd.set_half((uint64_t)other_m);
+          float dq, dh;
+          sd.distance((uint64_t)other_m, dq, dh);
+          criteria_half = dh + xi;
+          cache.init();
+          cache.key[0] = cache.key[cache.BEST] = other_n;
+          cache.dist[0] = cache.dist[cache.BEST] = dq;
+        }
+        bool found = false;
+        for (uint32_t ite = 0; ite < MAX_PER_PATH_ITERATIONS && !found; ++ite) {
+          // pop with criteria_sym() = s_dists[0] + xi (:285-288, :387)
+          const int32_t anchor = cache.pop_with(cache.dist[0] + cache.xi);
+          if (anchor == EMPTY_KEY)
+            break;
+          int32_t s_knn[K_BLOCK];
+          for (uint32_t i2 = 0; i2 < KBuild; i2 += K_BLOCK) {
+            for (uint32_t t = 0; t < K_BLOCK; ++t) {
+              const uint32_t k2 = i2 + t;
+              if (k2 < KBuild) {
+                const int32_t other_id =
+                    (k2 < KL)   ? graph_layer[(size_t)anchor * KBuild + k2]
+                    : pending ? pending[(size_t)anchor * KF + k2 - KL]
+                                : EMPTY_KEY;
+                if (other_id == n)
+                  connected = true;
+                s_knn[t] = other_id;
+              }
+              else
+                s_knn[t] = EMPTY_KEY;
+            }
+            if (connected) {
+              found = true;
+              break;
+            }
+            // fetch, simple_knn_sym_cache.cuh:405-436
+            cache.filter_sym(s_knn, K_BLOCK);
+            for (uint32_t kk = 0; kk < K_BLOCK; ++kk) {
+              const int32_t other_n = s_knn[kk];
+              if (other_n == EMPTY_KEY)
+                continue;
+              const int32_t other_m = translation ? translation[other_n] : other_n;
+              float dq, dh;
+              sd.distance((uint64_t)other_m, dq, dh);
+              const float crit = cache.dist[0] + cache.xi;
+              if (dq < crit) {
+                const double mg = std::fabs((double)dh - (double)criteria_half) /
+                                  std::max(1e-30, (double)std::fabs(criteria_half));
+                margin = std::min(margin, mg);
+              }
+              if (dq < crit && dh < criteria_half)
+                cache.push(other_n, dq);
+            }
+          }
+        }
+        end_of_search(i + k, found, cache);
+      }
+    }
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -1235,95 +1326,90 @@ void orc_sym(const void* base, int dtype, int measure, uint32_t D, uint32_t KBui
              const float* nn1_stats, float tau_build, int32_t* sym_buffer, uint32_t* sym_atomic,
              uint32_t first_n, uint32_t count)
 {
-  constexpr uint32_t K_BLOCK = 32, MAX_PER_PATH_ITERATIONS = 20, CACHE_SIZE = 128;
-  const uint32_t KF = KBuild / 2, KL = KBuild - KF;
-  const uint32_t sorted_size = std::max(64u, next_multiple32(KBuild / 2 + 16));
-  uint32_t items;
-  const uint32_t block = orc_construction_block(D, 64, &items);
+  const uint32_t KF = KBuild / 2;
   BaseView b{base, dtype, D};
   const float xi = xi_from(measure, nn1_stats[0], tau_build);
   const uint32_t end = std::min(Nlayer, first_n + count);
   for (uint32_t un = first_n; un < end; ++un) {
     const int32_t n = (int32_t)un;
-    SymDist sd(b, measure, block, items);
-    sd.load_query((uint64_t)(translation ? translation[n] : n));
-    Cache cache(KF, sorted_size, CACHE_SIZE, block, xi);
-    float criteria_half = 0.f;
-    for (uint32_t i = 0; i < KL; i += K_BLOCK) {
-      int32_t s_sym_ids[K_BLOCK];
-      for (uint32_t t = 0; t < K_BLOCK && i + t < KL; ++t)
-        s_sym_ids[t] = graph_layer[(size_t)n * KBuild + i + t];
-      for (uint32_t k = 0; i + k < KL && k < K_BLOCK; ++k) {
-        bool connected = false;
-        {
-          // init_start_point, simple_knn_sym_cache.cuh:159-201
-          const int32_t other_n = s_sym_ids[k];
-          const int32_t other_m = translation ? translation[other_n] : other_n;
-          sd.set_half((uint64_t)other_m);
-          float dq, dh;
-          sd.distance((uint64_t)other_m, dq, dh);
-          criteria_half = dh + xi;
-          cache.init();
-          cache.key[0] = cache.key[cache.BEST] = other_n;
-          cache.dist[0] = cache.dist[cache.BEST] = dq;
-        }
-        bool found = false;
-        for (uint32_t ite = 0; ite < MAX_PER_PATH_ITERATIONS && !found; ++ite) {
-          // pop with criteria_sym() = s_dists[0] + xi (:285-288, :387)
-          const int32_t anchor = cache.pop_with(cache.dist[0] + cache.xi);
-          if (anchor == EMPTY_KEY)
-            break;
-          int32_t s_knn[K_BLOCK];
-          for (uint32_t i2 = 0; i2 < KBuild; i2 += K_BLOCK) {
-            for (uint32_t t = 0; t < K_BLOCK; ++t) {
-              const uint32_t k2 = i2 + t;
-              if (k2 < KBuild) {
-                const int32_t other_id =
-                    (k2 < KL) ? graph_layer[(size_t)anchor * KBuild + k2]
-                              : sym_buffer[(size_t)anchor * KF + k2 - KL];
-                if (other_id == n)
-                  connected = true;
-                s_knn[t] = other_id;
-              }
-              else
-                s_knn[t] = EMPTY_KEY;
-            }
-            if (connected) {
-              found = true;
-              break;
-            }
-            // fetch, simple_knn_sym_cache.cuh:405-436
-            cache.filter_sym(s_knn, K_BLOCK);
-            for (uint32_t kk = 0; kk < K_BLOCK; ++kk) {
-              const int32_t other_n = s_knn[kk];
-              if (other_n == EMPTY_KEY)
-                continue;
-              const int32_t other_m = translation ? translation[other_n] : other_n;
-              float dq, dh;
-              sd.distance((uint64_t)other_m, dq, dh);
-              const float crit = cache.dist[0] + cache.xi;
-              if (dq < crit) {
-                const double mg = std::fabs((double)dh - (double)criteria_half) /
-                                  std::max(1e-30, (double)std::fabs(criteria_half));
-                g_margin_min = std::min(g_margin_min, mg);
-              }
-              if (dq < crit && dh < criteria_half)
-                cache.push(other_n, dq);
-            }
-          }
-        }
-        if (!found) {
-          // :121-141
-          for (uint32_t i3 = 0; i3 < KF; ++i3) {
-            const int32_t other_n = cache.key[i3];
-            if (other_n == EMPTY_KEY)
-              break;
-            const uint32_t pos = sym_atomic[other_n]++;
-            if (pos < KF) {
-              sym_buffer[(size_t)other_n * KF + pos] = n;
-              break;
-            }
-          }
+    sym_point_searches(b, measure, KBuild, graph_layer, translation, xi, n, sym_buffer,
+                       g_margin_min, [&](uint32_t, bool found, const Cache& cache) {
+                         if (found)
+                           return;
+                         // :121-141
+                         for (uint32_t i3 = 0; i3 < KF; ++i3) {
+                           const int32_t other_n = cache.key[i3];
+                           if (other_n == EMPTY_KEY)
+                             break;
+                           const uint32_t pos = sym_atomic[other_n]++;
+                           if (pos < KF) {
+                             sym_buffer[(size_t)other_n * KF + pos] = n;
+                             break;
+                           }
+                         }
+                       });
+  }
+}
+
+// ------------------------------------------------------------------------------------------
+// The engine's deterministic sym schedule (ggnn_set_build_hooks with serial_sym = 2,
+// include/ggnn_c.h; no reference counterpart: the reference's sym is one racy launch,
+// sym_query_layer.cu:102-104 against :124-141).
+// Step 1, the request pass: the searches of orc_sym with every anchor's pending inverse links
+// counted as empty.  A search that meets n leaves its row at -1; any other leaves the best list
+// that :121-124 would walk, nearest first, -1 where the list is unused.  No point reads what
+// another writes, so the points may run on threads.
+// ------------------------------------------------------------------------------------------
+void orc_sym_requests(const void* base, int dtype, int measure, uint32_t D, uint32_t KBuild,
+                      const int32_t* graph_layer, const int32_t* translation, uint32_t Nlayer,
+                      const float* nn1_stats, float tau_build, int32_t* requests,
+                      uint32_t first_n, uint32_t count, int threads)
+{
+  const uint32_t KF = KBuild / 2, KL = KBuild - KF;
+  BaseView b{base, dtype, D};
+  const float xi = xi_from(measure, nn1_stats[0], tau_build);
+  if (first_n >= Nlayer)
+    return;
+  count = std::min(count, Nlayer - first_n);
+  std::mutex margin_lock;
+  parallel_for(count, threads, [&](uint32_t i) {
+    const int32_t n = (int32_t)(first_n + i);
+    double margin = std::numeric_limits<double>::infinity();
+    sym_point_searches(b, measure, KBuild, graph_layer, translation, xi, n, nullptr, margin,
+                       [&](uint32_t j, bool found, const Cache& cache) {
+                         int32_t* row = requests + ((size_t)n * KL + j) * KF;
+                         for (uint32_t i3 = 0; i3 < KF; ++i3)
+                           row[i3] = found ? EMPTY_KEY : cache.key[i3];
+                       });
+    std::lock_guard<std::mutex> hold(margin_lock);
+    g_margin_min = std::min(g_margin_min, margin);
+  });
+}
+
+// Step 2, the assign step: the request rows in ascending (point, local neighbour) order, each at
+// the first of its candidates that still has a slot -- what :124-141 does for one search, with
+// one addition: a point that already holds a slot at a candidate is not given a second one there
+// and asks no further (in a serial schedule its later search would have met that pending
+// link).  Counters may end above KF, as there.
+void orc_sym_assign(uint32_t KBuild, uint32_t Nlayer, const int32_t* requests,
+                    uint32_t* sym_atomic, int32_t* sym_buffer)
+{
+  const uint32_t KF = KBuild / 2, KL = KBuild - KF;
+  for (uint32_t n = 0; n < Nlayer; ++n) {
+    for (uint32_t j = 0; j < KL; ++j) {
+      const int32_t* row = requests + ((size_t)n * KL + j) * KF;
+      for (uint32_t i = 0; i < KF; ++i) {
+        const int32_t c = row[i];
+        if (c < 0 || (uint32_t)c >= Nlayer)
+          break;
+        const int32_t* slots = sym_buffer + (size_t)c * KF;
+        const int32_t* slots_end = slots + std::min(sym_atomic[c], KF);
+        if (std::find(slots, slots_end, (int32_t)n) != slots_end)
+          break;  // n holds a slot at c already
+        const uint32_t pos = sym_atomic[c]++;
+        if (pos < KF) {
+          sym_buffer[(size_t)c * KF + pos] = (int32_t)n;
+          break;
         }
       }
     }
@@ -1386,9 +1472,12 @@ void orc_nn1_stats(const float* v, uint32_t N, float* out)
 void orc_build(const void* base, int dtype, int measure, const OrcGraphConfig* cfg,
                float tau_build, uint32_t refinement_iterations, const float* rng,
                int32_t* graph_all, int32_t* translation_all, int32_t* selection_all,
-               float* nn1_stats, int threads)
+               float* nn1_stats, int threads, int sym_mode)
 {
   const uint32_t N = cfg->N, K = cfg->KBuild, KF = cfg->KF, D = cfg->D;
+  std::vector<int32_t> requests;
+  if (sym_mode == ORC_SYM_DETERMINISTIC)
+    requests.resize((size_t)N * (K - KF) * KF);
   std::vector<float> nn1_dist(N);
   std::vector<int32_t> graph_buffer((size_t)N * K);
   std::vector<int32_t> sym_buffer((size_t)N * KF);
@@ -1415,8 +1504,14 @@ void orc_build(const void* base, int dtype, int measure, const OrcGraphConfig* c
   auto do_sym = [&](uint32_t l) {
     std::fill(sym_buffer.begin(), sym_buffer.begin() + (size_t)cfg->Ns[l] * KF, -1);
     std::fill(sym_atomic.begin(), sym_atomic.begin() + cfg->Ns[l], 0u);
-    orc_sym(base, dtype, measure, D, K, layer_graph(l), layer_tr(l), cfg->Ns[l], nn1_stats,
-            tau_build, sym_buffer.data(), sym_atomic.data(), 0, cfg->Ns[l]);
+    if (sym_mode == ORC_SYM_DETERMINISTIC) {
+      orc_sym_requests(base, dtype, measure, D, K, layer_graph(l), layer_tr(l), cfg->Ns[l],
+                       nn1_stats, tau_build, requests.data(), 0, cfg->Ns[l], threads);
+      orc_sym_assign(K, cfg->Ns[l], requests.data(), sym_atomic.data(), sym_buffer.data());
+    }
+    else
+      orc_sym(base, dtype, measure, D, K, layer_graph(l), layer_tr(l), cfg->Ns[l], nn1_stats,
+              tau_build, sym_buffer.data(), sym_atomic.data(), 0, cfg->Ns[l]);
     orc_sym_buffer_merge(K, cfg->Ns[l], sym_buffer.data(), sym_atomic.data(), layer_graph(l));
   };
 

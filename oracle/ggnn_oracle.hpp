@@ -96,6 +96,24 @@ void orc_sym(const void* base, int dtype, int measure, uint32_t D, uint32_t KBui
              uint32_t Nlayer, const float* nn1_stats, float tau_build, int32_t* sym_buffer,
              uint32_t* sym_atomic, uint32_t first_n, uint32_t count);
 
+// The engine's deterministic sym schedule (ggnn_set_build_hooks with serial_sym = 2; an extension,
+// the reference has the one racy launch only), in two steps.
+// Request pass: the searches of orc_sym, except that an anchor's pending inverse links count as
+// empty.  requests [Nlayer x KL x KF] receives, per point and local neighbour, -1 everywhere if
+// the search met the point, else its best list (nearest first, -1 from the first unused entry
+// on).  A pure function of its inputs: any split into first_n/count pieces and any number of
+// threads give the same bytes.
+void orc_sym_requests(const void* base, int dtype, int measure, uint32_t D, uint32_t KBuild,
+                      const int32_t* graph_layer, const int32_t* translation_layer,
+                      uint32_t Nlayer, const float* nn1_stats, float tau_build,
+                      int32_t* requests, uint32_t first_n, uint32_t count, int threads);
+// Assign step (a whole pass starts from sym_atomic = 0, sym_buffer = -1): rows in ascending
+// (point n, local neighbour) order; the candidates c of a row up to the first -1 or id >= Nlayer:
+// if n is among sym_buffer[c][0 .. min(sym_atomic[c], KF)) the row is done; else pos =
+// sym_atomic[c]++, and pos < KF stores n at sym_buffer[c][pos] and ends the row.
+void orc_sym_assign(uint32_t KBuild, uint32_t Nlayer, const int32_t* requests,
+                    uint32_t* sym_atomic, int32_t* sym_buffer);
+
 // src/ggnn/construction/sym_buffer_merge_layer.cu:36-99
 void orc_sym_buffer_merge(uint32_t KBuild, uint32_t Nlayer, const int32_t* sym_buffer,
                           const uint32_t* sym_atomic, int32_t* graph_layer);
@@ -105,10 +123,13 @@ void orc_nn1_stats(const float* nn1_dist_buffer, uint32_t N, float* out);
 
 // full schedule, src/ggnn/construction/graph_construction.cu:128-147 ; rng: [4 x N] uniform
 // (0,1] numbers, row l used by select(l).  graph_all [N_all x K], translation/selection [ST_all].
+// sym_mode: ORC_SYM_SERIAL = orc_sym over all points of a layer (one serialisation of the
+// reference's racy launch); ORC_SYM_DETERMINISTIC = orc_sym_requests + orc_sym_assign instead.
+enum { ORC_SYM_SERIAL = 1, ORC_SYM_DETERMINISTIC = 2 };
 void orc_build(const void* base, int dtype, int measure, const OrcGraphConfig* cfg,
                float tau_build, uint32_t refinement_iterations, const float* rng,
                int32_t* graph_all, int32_t* translation_all, int32_t* selection_all,
-               float* nn1_stats, int threads);
+               float* nn1_stats, int threads, int sym_mode);
 
 // src/ggnn/base/gpu_instance.cu:745-790 (stable ascending sort of each [shards*K] row by dist)
 void orc_sort_shard_results(uint32_t Nq, uint32_t row_len, int32_t* ids, float* dists);

@@ -202,6 +202,38 @@ def sym(base, KBuild, graph_layer, translation_layer, nn1_stats, tau_build, sym_
                   C.c_uint32(count))
 
 
+def sym_requests(base, KBuild, graph_layer, translation_layer, nn1_stats, tau_build,
+                 measure=EUCLIDEAN, first_n=0, count=None, threads=0, out=None):
+    """request pass of the deterministic sym schedule: requests [N x KL x KF] int32 (rows of
+    points outside first_n .. first_n + count - 1 stay as `out` has them, -1 in a new array)"""
+    base = _c(base)
+    graph_layer = _c(graph_layer, np.int32)
+    tr = None if translation_layer is None else _c(translation_layer, np.int32)
+    nn1_stats = _c(nn1_stats, np.float32)
+    Nl = graph_layer.shape[0]
+    KF = KBuild // 2
+    if count is None:
+        count = Nl
+    if out is None:
+        out = np.full((Nl, KBuild - KF, KF), -1, np.int32)
+    assert out.dtype == np.int32 and out.flags.c_contiguous and out.size == Nl * (KBuild - KF) * KF
+    lib().orc_sym_requests(_p(base), _dtype_code(base), measure, C.c_uint32(base.shape[1]),
+                           C.c_uint32(KBuild), _p(graph_layer), _p(tr), C.c_uint32(Nl),
+                           _p(nn1_stats), C.c_float(tau_build), _p(out), C.c_uint32(first_n),
+                           C.c_uint32(count), threads)
+    return out
+
+
+def sym_assign(KBuild, requests, sym_atomic, sym_buffer):
+    """assign step of the deterministic sym schedule, in place on sym_atomic [N] uint32 /
+    sym_buffer [N x KF] int32"""
+    requests = _c(requests, np.int32)
+    assert sym_buffer.dtype == np.int32 and sym_atomic.dtype == np.uint32
+    assert sym_buffer.flags.c_contiguous and sym_atomic.flags.c_contiguous
+    lib().orc_sym_assign(C.c_uint32(KBuild), C.c_uint32(sym_atomic.shape[0]), _p(requests),
+                         _p(sym_atomic), _p(sym_buffer))
+
+
 def sym_buffer_merge(KBuild, sym_buffer, sym_atomic, graph_layer):
     """in-place on graph_layer [N x K] int32"""
     assert graph_layer.dtype == np.int32 and graph_layer.flags.c_contiguous
@@ -224,7 +256,9 @@ def make_rng(N, seed=1234):
 
 
 def build(base, KBuild, tau_build, refinement_iterations=2, measure=EUCLIDEAN, rng=None,
-          threads=0):
+          threads=0, deterministic_sym=False):
+    """deterministic_sym: sym_requests + sym_assign in place of the serial sym (the engine's
+    set_build_hooks(deterministic_sym=True))"""
     base = _c(base)
     N, D = base.shape
     cfg = graph_config(N, D, KBuild)
@@ -237,7 +271,7 @@ def build(base, KBuild, tau_build, refinement_iterations=2, measure=EUCLIDEAN, r
     stats = np.zeros(2, np.float32)
     lib().orc_build(_p(base), _dtype_code(base), measure, C.byref(cfg), C.c_float(tau_build),
                     C.c_uint32(refinement_iterations), _p(rng), _p(graph_all), _p(tr), _p(sel),
-                    _p(stats), threads)
+                    _p(stats), threads, 2 if deterministic_sym else 1)
     return cfg, graph_all, tr, sel, stats
 
 

@@ -14,6 +14,8 @@ import ctypes.util
 import numpy as np
 import pytest
 
+import sym_assign_cases
+
 _libm = ctypes.CDLL(ctypes.util.find_library("m"))
 _libm.logf.restype = ctypes.c_float
 _libm.logf.argtypes = [ctypes.c_float]
@@ -195,6 +197,72 @@ def test_sym_buffer_merge_equals_numpy_restatement(orc, K):
     assert np.array_equal(g1[:, :K - KF], graph[:, :K - KF])  # own links untouched
 
 
+# ---- assign step of the deterministic sym schedule (include/ggnn_c.h, ggnn_set_build_hooks) ------
+def np_sym_assign(KBuild, requests, sym_atomic, sym_buffer):
+    """Rows in ascending (point, local neighbour) order.  A row asks its candidates in turn, up to
+    the first -1 or id outside the layer: a candidate that lists the point among its granted
+    slots (the first min(counter, KF) of them) settles the row, and so does one that still has a
+    free slot, which the point takes; a full candidate only counts the request."""
+    KF = KBuild // 2
+    N = sym_atomic.shape[0]
+    for n, rows in enumerate(np.asarray(requests).reshape(N, KBuild - KF, KF)):
+        for row in rows:
+            for c in row.tolist():
+                if not 0 <= c < N:
+                    break
+                granted = sym_buffer[c, :min(int(sym_atomic[c]), KF)]
+                if n in granted.tolist():
+                    break
+                sym_atomic[c] += 1
+                if len(granted) < KF:
+                    sym_buffer[c, len(granted)] = n
+                    break
+
+
+def _assign_both(orc, K, req, atomic0, buffer0):
+    a1, b1 = atomic0.copy(), buffer0.copy()
+    orc.sym_assign(K, req, a1, b1)
+    a2, b2 = atomic0.astype(np.int64), buffer0.astype(np.int64)
+    np_sym_assign(K, req, a2, b2)
+    assert np.array_equal(a1.astype(np.int64), a2) and np.array_equal(b1.astype(np.int64), b2)
+    return a1, b1
+
+
+@pytest.mark.parametrize("case", sym_assign_cases.all_cases(), ids=lambda c: c[0])
+def test_sym_assign_known_answers(orc, case):
+    """hand-written expectations (tests/sym_assign_cases.py): the oracle and the numpy
+    restatement both give them"""
+    name, K, req, atomic0, buffer0, atomic1, buffer1 = case
+    a, b = _assign_both(orc, K, req, atomic0, buffer0)
+    assert a.tolist() == atomic1.tolist(), name
+    assert b.tolist() == buffer1.tolist(), name
+
+
+@pytest.mark.parametrize("K,layer", [(24, 0), (24, 2), (21, 0), (21, 2)])
+def test_sym_assign_on_real_requests_equals_numpy_restatement(orc, K, layer):
+    """the requests of a layer of a built graph (KBuild 21: KF = 10, KL = 11)"""
+    N, D = 1500, 32
+    base = (np.random.default_rng(K + layer).integers(0, 52, (N, D)) * 5).astype(np.float32)
+    cfg, graph, tr, sel, stats = orc.build(base, K, 0.5, 0, rng=orc.make_rng(N, 3))
+    Nl = cfg.Ns[layer]
+    rows = graph[cfg.Ns_offsets[layer]:cfg.Ns_offsets[layer] + Nl].copy()
+    tr_l = None if layer == 0 else tr[cfg.STs_offsets[layer]:cfg.STs_offsets[layer] + Nl].copy()
+    req = orc.sym_requests(base, K, rows, tr_l, stats, 0.5)
+    a, b = _assign_both(orc, K, req, np.zeros(Nl, np.uint32), np.full((Nl, K // 2), -1, np.int32))
+    assert int(a.sum()) > 0, "no inverse link was requested: the case tests nothing"
+    granted = np.minimum(a, K // 2)
+    assert ((b >= 0) == (np.arange(K // 2)[None, :] < granted[:, None])).all()
+
+
+@pytest.mark.parametrize("K", [24, 9])
+def test_sym_assign_under_contention_equals_numpy_restatement(orc, K):
+    """every row asks among 12 targets: most rows pass several full ones, many find none"""
+    N = 300
+    req = sym_assign_cases.contention_table(N, K, 12, K)
+    a, b = _assign_both(orc, K, req, np.zeros(N, np.uint32), np.full((N, K // 2), -1, np.int32))
+    assert int((a > K // 2).sum()) >= 10 and int((a == 0).sum()) == N - 12
+
+
 # ---- computeNN1Stats, graph_construction.cu:381-402 -----------------------------------------------
 def test_nn1_stats_mean_and_max(orc):
     v = (np.random.default_rng(3).random(100_000, dtype=np.float32) * 50).astype(np.float32)
@@ -206,10 +274,11 @@ def test_nn1_stats_mean_and_max(orc):
 
 
 # ---- the build / refine schedule, graph_construction.cu:128-147, 186-201, 298-379, 381-402 --------
-def py_schedule(orc, base, K, tau, refine, rng):
+def py_schedule(orc, base, K, tau, refine, rng, deterministic_sym=False):
     """the launch order written from the cited lines, driving the oracle's per-kernel entry points
     from Python; `orc.build` (one C++ function, the thing the engine's whole build is compared
-    with) must produce the same arrays"""
+    with) must produce the same arrays.  deterministic_sym: the engine's deterministic sym
+    schedule (request pass + assign step) where the reference launches sym"""
     N, D = base.shape
     cfg = orc.graph_config(N, D, K)
     KF = K // 2
@@ -245,7 +314,11 @@ def py_schedule(orc, base, K, tau, refine, rng):
         buf = np.full((cfg.Ns[layer], KF), -1, np.int32)
         atom = np.zeros(cfg.Ns[layer], np.uint32)
         rows = np.ascontiguousarray(layer_rows(layer))
-        orc.sym(base, K, rows, layer_tr(layer), stats, tau, buf, atom)
+        if deterministic_sym:
+            req = orc.sym_requests(base, K, rows, layer_tr(layer), stats, tau)
+            orc.sym_assign(K, req, atom, buf)
+        else:
+            orc.sym(base, K, rows, layer_tr(layer), stats, tau, buf, atom)
         orc.sym_buffer_merge(K, buf, atom, rows)
         layer_rows(layer)[:] = rows
 
@@ -262,15 +335,31 @@ def py_schedule(orc, base, K, tau, refine, rng):
     return cfg, graph_all, tr, sel, stats
 
 
-@pytest.mark.parametrize("N,D,K,refine", [(3000, 32, 24, 2), (6000, 16, 20, 1), (2048, 64, 24, 0)])
-def test_build_schedule_equals_python_schedule_over_oracle_kernels(orc, N, D, K, refine):
+def _schedule_case(orc, N, D, K, refine, deterministic_sym):
     base = (np.random.default_rng(N).integers(0, 52, (N, D)) * 5).astype(np.float32)
     rng = orc.make_rng(N, 17)
-    cfg, graph, tr, sel, stats = orc.build(base, K, 0.5, refine, rng=rng)
-    cfg2, graph2, tr2, sel2, stats2 = py_schedule(orc, base, K, 0.5, refine, rng)
+    cfg, graph, tr, sel, stats = orc.build(base, K, 0.5, refine, rng=rng,
+                                           deterministic_sym=deterministic_sym)
+    cfg2, graph2, tr2, sel2, stats2 = py_schedule(orc, base, K, 0.5, refine, rng,
+                                                  deterministic_sym)
     assert np.array_equal(tr, tr2), "translation"
     assert np.array_equal(sel, sel2), "selection"
     assert stats.tobytes() == np.asarray(stats2, np.float32).tobytes(), (stats, stats2)
     for l in range(4):
         a, b = cfg.Ns_offsets[l], cfg.Ns_offsets[l] + cfg.Ns[l]
         assert np.array_equal(graph[a:b], graph2[a:b]), f"layer {l}"
+    return graph
+
+
+@pytest.mark.parametrize("N,D,K,refine", [(3000, 32, 24, 2), (6000, 16, 20, 1), (2048, 64, 24, 0)])
+def test_build_schedule_equals_python_schedule_over_oracle_kernels(orc, N, D, K, refine):
+    _schedule_case(orc, N, D, K, refine, False)
+
+
+@pytest.mark.parametrize("N,D,K,refine", [(3000, 32, 24, 2), (6000, 16, 20, 1), (2048, 64, 21, 0)])
+def test_deterministic_build_schedule_equals_python_schedule(orc, N, D, K, refine):
+    """orc.build(deterministic_sym=True); its graph is not the serial schedule's"""
+    graph = _schedule_case(orc, N, D, K, refine, True)
+    base = (np.random.default_rng(N).integers(0, 52, (N, D)) * 5).astype(np.float32)
+    serial = orc.build(base, K, 0.5, refine, rng=orc.make_rng(N, 17))[1]
+    assert not np.array_equal(graph, serial)

@@ -497,6 +497,100 @@ def test_sym_prefix_equals_python_restatement(orc, KB, layer):
     assert atom_b.sum() > 0, "no inverse link was requested: the case tests nothing"
 
 
+# ---- request pass of the deterministic sym schedule (include/ggnn_c.h, ggnn_set_build_hooks) ------
+def py_sym_requests(base, KBuild, graph, translation, nn1_stats, tau_build, points):
+    """Per point n and local neighbour j < KL: the search of py_sym from neighbour j back to n,
+    where an anchor's neighbour list is its KL local links followed by KF EMPTY entries (the
+    pending inverse links count as empty).  Row (n, j) is all -1 if n was met, else the best list
+    s_cache[0 .. KF), which is -1 from its first unused entry on.  Returns {n: [KL, KF] rows}."""
+    KF = KBuild // 2
+    KL = KBuild - KF
+    CACHE, MAX_PER_PATH = 128, 20
+    sorted_size = max(64 if CACHE < 512 else 32, ((KF + 16 + 31) // 32) * 32)
+    tau = np.float32(tau_build)
+    mean = np.float32(nn1_stats[0])
+    xi = np.float32(np.float32(np.float32(mean * mean) * tau) * tau)
+    out = {}
+    for n in points:
+        m = n if translation is None else int(translation[n])
+        c = PySymCache(KF, sorted_size, CACHE, xi, base, m)
+        rows = np.full((KL, KF), EMPTY_KEY, np.int64)
+        for j in range(KL):
+            c.init_start_point(int(graph[n, j]), translation)
+            found = False
+            for _ in range(MAX_PER_PATH):
+                anchor = c.pop()
+                if anchor == EMPTY_KEY:
+                    break
+                links = np.full(((KBuild + 31) // 32) * 32, EMPTY_KEY, np.int64)
+                links[:KL] = graph[anchor, :KL]
+                for i in range(0, KBuild, 32):
+                    s_knn = links[i:i + 32].copy()
+                    if (s_knn == n).any():
+                        found = True
+                        break
+                    c.fetch_sym(s_knn, translation)
+                if found:
+                    break
+            if not found:
+                rows[j] = c.s_cache[:KF]
+        out[n] = rows
+    return out
+
+
+def _mult5_layer(orc, KB, layer, seed):
+    """a layer of an oracle-built graph on multiples of 5 (exact half point, see
+    test_sym_prefix_equals_python_restatement): base, graph rows, translation, stats"""
+    N, D = 1500, 32
+    base = (np.random.default_rng(seed).integers(0, 52, (N, D)) * 5).astype(np.float32)
+    cfg, graph, tr, sel, stats = orc.build(base, KB, 0.5, 0, rng=orc.make_rng(N, 3))
+    Nl = cfg.Ns[layer]
+    g_layer = graph[cfg.Ns_offsets[layer]:cfg.Ns_offsets[layer] + Nl].copy()
+    tr_l = None if layer == 0 else tr[cfg.STs_offsets[layer]:cfg.STs_offsets[layer] + Nl].copy()
+    return base, g_layer, tr_l, stats
+
+
+@pytest.mark.parametrize("KB,layer", [(24, 0), (24, 2), (21, 0), (21, 2)])
+def test_sym_requests_equal_python_restatement(orc, KB, layer):
+    """KBuild 21: KF = 10 slots, KL = 11 searches per point.  Sampled points of the layer, its
+    first and last included; every row of theirs bit for bit."""
+    base, g_layer, tr_l, stats = _mult5_layer(orc, KB, layer, 40 + KB + layer)
+    Nl = g_layer.shape[0]
+    req = orc.sym_requests(base, KB, g_layer, tr_l, stats, 0.5)
+    assert req.shape == (Nl, KB - KB // 2, KB // 2)
+    pts = sorted(set(np.random.default_rng(KB).integers(0, Nl, 70).tolist() + [0, Nl - 1]))
+    mine = py_sym_requests(base, KB, g_layer, tr_l, stats, 0.5, pts)
+    asked = 0
+    for n in pts:
+        assert np.array_equal(req[n].astype(np.int64), mine[n]), n
+        asked += int((mine[n][:, 0] != EMPTY_KEY).sum())
+    assert asked > 0, "no search of the sample failed to meet its point: the case tests nothing"
+    # the rows are lists: nothing follows a -1
+    gap = (req[:, :, :-1] == EMPTY_KEY) & (req[:, :, 1:] != EMPTY_KEY)
+    assert not gap.any()
+
+
+@pytest.mark.parametrize("KB,layer", [(24, 0), (21, 2)])
+def test_sym_requests_do_not_depend_on_pieces_or_threads(orc, KB, layer):
+    """one call, calls of count = 7, and 1 or 4 threads: identical bytes"""
+    base, g_layer, tr_l, stats = _mult5_layer(orc, KB, layer, 40 + KB + layer)
+    Nl = g_layer.shape[0]
+    whole = orc.sym_requests(base, KB, g_layer, tr_l, stats, 0.5, threads=1)
+    for threads in (4, 0):
+        again = orc.sym_requests(base, KB, g_layer, tr_l, stats, 0.5, threads=threads)
+        assert again.tobytes() == whole.tobytes(), threads
+    pieces = np.full_like(whole, -1)
+    for first in range(0, Nl, 7):
+        orc.sym_requests(base, KB, g_layer, tr_l, stats, 0.5, first_n=first, count=7, threads=4,
+                         out=pieces)
+    assert pieces.tobytes() == whole.tobytes()
+    # a piece writes the rows of its own points only
+    part = np.full_like(whole, -7)
+    orc.sym_requests(base, KB, g_layer, tr_l, stats, 0.5, first_n=5, count=3, out=part)
+    assert (part[:5] == -7).all() and (part[8:] == -7).all()
+    assert np.array_equal(part[5:8], whole[5:8])
+
+
 def test_cosine_query_equals_python_restatement(orc):
     """Cosine measure (distance.cuh:139-158: |1 - q.b / sqrt(|q|^2 |b|^2)|, xi = nn1_max * tau,
     query_layer.cu:48-61).  Small integer coordinates: dot products and norms are exact, the few
