@@ -78,6 +78,44 @@ def _host_rows(t):
     return t.numpy()
 
 
+def pack_filter(mask):
+    """Pack a boolean mask over the base ids (numpy / torch, length N) into the bitset of the
+    filtered calls: int32 words, id i is allowed iff bit (i & 31) of word (i >> 5) is set,
+    ceil(N / 32) words, padding bits zero.  Returns a CPU torch.int32 tensor."""
+    if isinstance(mask, torch.Tensor):
+        mask = mask.detach().cpu().numpy()
+    mask = np.asarray(mask)
+    if mask.dtype != np.bool_ or mask.ndim != 1:
+        raise TypeError("mask must be a 1-dimensional boolean array")
+    packed = np.packbits(mask, bitorder="little")
+    words = np.zeros((mask.size + 31) // 32 * 4, np.uint8)
+    words[:packed.size] = packed
+    return torch.from_numpy(words.view(np.int32).copy())
+
+
+def _filter_words(filter, N):
+    """the `filter` argument of query_filtered / bf_query_filtered as a contiguous int32 tensor of
+    ceil(N / 32) words (CPU or CUDA): a boolean mask of length N is packed on the host, an
+    int32 / uint32 array is taken as already packed"""
+    if isinstance(filter, np.ndarray) and filter.dtype == np.uint32:
+        filter = filter.view(np.int32)
+    if isinstance(filter, np.ndarray):
+        filter = torch.from_numpy(np.ascontiguousarray(filter))
+    if not isinstance(filter, torch.Tensor) or filter.dim() != 1:
+        raise TypeError("filter must be a 1-dimensional numpy array or torch tensor")
+    if filter.dtype == torch.bool:
+        if filter.numel() != N:
+            raise ValueError(f"a boolean filter needs one entry per base vector ({N})")
+        return pack_filter(filter)
+    if hasattr(torch, "uint32") and filter.dtype == torch.uint32:
+        filter = filter.view(torch.int32)
+    if filter.dtype != torch.int32:
+        raise TypeError("filter must be boolean, or int32 / uint32 words of a packed bitset")
+    if filter.numel() != (N + 31) // 32:
+        raise ValueError(f"a packed filter needs ceil(N / 32) = {(N + 31) // 32} words")
+    return filter.contiguous()
+
+
 # ---------------------------------------------------------------------------------------------
 # Datasets (nanobind.cu:153-181; Dataset<T>::load/store, src/ggnn/base/dataset.cu:118-233)
 # ---------------------------------------------------------------------------------------------
@@ -311,6 +349,48 @@ class GGNN:
                                      _dtype_code(t), loc, dev, int(k_query), float(tau_query),
                                      int(max_iterations), int(measure), ids.data_ptr(),
                                      dists.data_ptr(), _lib.GPU if on_gpu else _lib.CPU))
+        return ids, dists
+
+    def query_filtered(self, query, k_query, tau_query, max_iterations=400,
+                       measure=DistanceMeasure.Euclidean, filter=None):
+        """Extension: `query` among the base vectors `filter` allows -- a boolean mask of length N
+        (numpy / torch) or an already packed bitset (`pack_filter`: int32 / uint32, ceil(N / 32)
+        words, CPU or GPU), shared by all queries of the batch.  Denied vectors still route the
+        search but are never reported; slots that could not be filled hold id -1 and distance
+        +inf.  `filter=None` is `query`."""
+        if filter is None:
+            return self.query(query, k_query, tau_query, max_iterations, measure)
+        t = _as_tensor(query, what="query")
+        N = self._base_shape[0] if hasattr(self, "_base_shape") else 0
+        f = _filter_words(filter, N)
+        loc, dev = _loc(t)
+        floc, fdev = _loc(f)
+        on_gpu = self._return_results_on_gpu
+        width = int(k_query) * (self._shards if on_gpu else 1)
+        ids, dists = self._out(t.shape[0], width, on_gpu, self._result_device(t) if on_gpu else None)
+        self._check(lib().ggnn_query_filtered(
+            self._h, t.data_ptr(), t.shape[0], t.shape[1], _dtype_code(t), loc, dev, int(k_query),
+            float(tau_query), int(max_iterations), int(measure), ids.data_ptr(), dists.data_ptr(),
+            _lib.GPU if on_gpu else _lib.CPU, f.data_ptr(), N, floc, fdev))
+        return ids, dists
+
+    def bf_query_filtered(self, query, k_gt=100, measure=DistanceMeasure.Euclidean, filter=None):
+        """Extension: the exact `k_gt` nearest among the base vectors `filter` allows (see
+        `query_filtered`); slots beyond the number of allowed vectors are (-1, +inf)."""
+        if filter is None:
+            return self.bf_query(query, k_gt, measure)
+        t = _as_tensor(query, what="query")
+        N = self._base_shape[0] if hasattr(self, "_base_shape") else 0
+        f = _filter_words(filter, N)
+        loc, dev = _loc(t)
+        floc, fdev = _loc(f)
+        on_gpu = self._return_results_on_gpu
+        ids, dists = self._out(t.shape[0], int(k_gt), on_gpu,
+                               self._result_device(t) if on_gpu else None)
+        self._check(lib().ggnn_bf_query_filtered(
+            self._h, t.data_ptr(), t.shape[0], t.shape[1], _dtype_code(t), loc, dev, int(k_gt),
+            int(measure), ids.data_ptr(), dists.data_ptr(), _lib.GPU if on_gpu else _lib.CPU,
+            f.data_ptr(), N, floc, fdev))
         return ids, dists
 
     def query_async(self, query, k_query, tau_query, max_iterations=400,

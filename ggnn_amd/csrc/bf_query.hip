@@ -7,6 +7,10 @@
 // per (query, base slice), 64/LPR base rows per coalesced 16 B/lane load instruction, K-best
 // list in registers.  Slices are merged by a second tiny kernel.  (An MFMA Q x B^T tile path
 // for large query batches is planned on top of this parity anchor, see DESIGN.md.)
+//
+// FILT = true (ggnn_bf_query_filtered): the exact K nearest among the rows an allowed-id bitset
+// admits -- a denied row's distance becomes +inf before the ballot.  The filtered call always runs
+// on these scan kernels: a filtered matrix-core path (bf_mfma.hip, bf_i8.hip) is out of scope.
 #include <cstdlib>
 
 #include "hooks.hpp"
@@ -24,9 +28,31 @@ struct BfArgs {
   // sized for all Nq queries and the surplus blocks leave at once)
   const uint32_t* qlist;
   const uint32_t* qcount;
+  // filtered scan (FILT kernels): allowed-id bitset, row i is allowed iff bit i + filter_bit_offset
+  const uint32_t* filter_bits;
+  uint32_t filter_bit_offset;
 };
 
-template <typename BaseT, int LPR, int NCH, int R, int MODE>
+// FILT: this lane's word of the bitset for the 64 (or fewer) rows of a batch starting at i0 -- one
+// coalesced load per batch, issued in front of the rows -- and the verdict for row i0 + lane
+template <bool FILT>
+GGNN_DEV uint32_t bf_filter_word(const BfArgs& a, uint32_t i0, uint32_t end)
+{
+  if constexpr (FILT) {
+    const uint32_t row = i0 + threadIdx.x;
+    return row < end ? a.filter_bits[(row + a.filter_bit_offset) >> 5] : 0u;
+  }
+  return 0u;
+}
+template <bool FILT>
+GGNN_DEV bool bf_row_allowed(const BfArgs& a, uint32_t word, uint32_t i0)
+{
+  if constexpr (FILT)
+    return (word >> ((i0 + threadIdx.x + a.filter_bit_offset) & 31u)) & 1u;
+  return true;
+}
+
+template <typename BaseT, int LPR, int NCH, int R, int MODE, bool FILT = false>
 __global__ void __launch_bounds__(kWave) bf_query_kernel(const BfArgs a)
 {
   constexpr int ROWS = kWave / LPR;
@@ -65,6 +91,7 @@ __global__ void __launch_bounds__(kWave) bf_query_kernel(const BfArgs a)
   const uint32_t begin = slice * a.rows_per_slice;
   const uint32_t end = min(a.N_base, begin + a.rows_per_slice);
   for (uint32_t i0 = begin; i0 < end; i0 += ROWS * STEPS) {
+    const uint32_t fword = bf_filter_word<FILT>(a, i0, end);
     Chunk v[STEPS][NCH];
 #pragma unroll
     for (int s = 0; s < STEPS; ++s) {
@@ -92,7 +119,8 @@ __global__ void __launch_bounds__(kWave) bf_query_kernel(const BfArgs a)
     __syncthreads();
     // visit the batch in base order (bf_query_layer.cu:52-57)
     const uint32_t cnt = min((uint32_t)(ROWS * STEPS), end - i0);
-    const float cd = lane < (int)cnt ? s_d[lane] : inf_f();
+    // a denied row never enters the list
+    const float cd = (lane < (int)cnt && bf_row_allowed<FILT>(a, fword, i0)) ? s_d[lane] : inf_f();
     unsigned long long m = __ballot(cd < best.dist_at(a.K - 1));
     while (m) {
       const int j = __ffsll(static_cast<long long>(m)) - 1;
@@ -116,7 +144,7 @@ __global__ void __launch_bounds__(kWave) bf_query_kernel(const BfArgs a)
 
 // k > 256: the K-best list lives in LDS (dists [K] | ids [K]); stable insertion by a wave-wide
 // shift, rare after the first few thousand rows.
-template <typename BaseT, int LPR, int NCH, int MODE>
+template <typename BaseT, int LPR, int NCH, int MODE, bool FILT = false>
 __global__ void __launch_bounds__(kWave) bf_query_lds_kernel(const BfArgs a)
 {
   constexpr int ROWS = kWave / LPR;
@@ -152,6 +180,7 @@ __global__ void __launch_bounds__(kWave) bf_query_lds_kernel(const BfArgs a)
   const uint32_t begin = slice * a.rows_per_slice;
   const uint32_t end = min(a.N_base, begin + a.rows_per_slice);
   for (uint32_t i0 = begin; i0 < end; i0 += ROWS * STEPS) {
+    const uint32_t fword = bf_filter_word<FILT>(a, i0, end);
     Chunk v[STEPS][NCH];
 #pragma unroll
     for (int s = 0; s < STEPS; ++s) {
@@ -178,7 +207,8 @@ __global__ void __launch_bounds__(kWave) bf_query_lds_kernel(const BfArgs a)
     }
     __syncthreads();
     const uint32_t cnt = min((uint32_t)(ROWS * STEPS), end - i0);
-    const float cd = lane < (int)cnt ? s_d[lane] : inf_f();
+    // a denied row never enters the list
+    const float cd = (lane < (int)cnt && bf_row_allowed<FILT>(a, fword, i0)) ? s_d[lane] : inf_f();
     unsigned long long m = __ballot(cd < best_d[a.K - 1]);
     while (m) {
       const int j = __ffsll(static_cast<long long>(m)) - 1;
@@ -217,6 +247,21 @@ template <typename BaseT, int LPR, int NCH, int MODE>
 static void launch_bf_r(const BfArgs& args, hipStream_t stream)
 {
   const dim3 grid = grid_for(static_cast<uint64_t>(args.Nq) * args.slices);
+  if (args.filter_bits) {
+    if (args.K <= 64)
+      hipLaunchKernelGGL((bf_query_kernel<BaseT, LPR, NCH, 1, MODE, true>), grid, dim3(kWave), 0,
+                         stream, args);
+    else if (args.K <= 128)
+      hipLaunchKernelGGL((bf_query_kernel<BaseT, LPR, NCH, 2, MODE, true>), grid, dim3(kWave), 0,
+                         stream, args);
+    else if (args.K <= 256)
+      hipLaunchKernelGGL((bf_query_kernel<BaseT, LPR, NCH, 4, MODE, true>), grid, dim3(kWave), 0,
+                         stream, args);
+    else
+      hipLaunchKernelGGL((bf_query_lds_kernel<BaseT, LPR, NCH, MODE, true>), grid, dim3(kWave),
+                         (2 * args.K + 64) * sizeof(int), stream, args);
+    return;
+  }
   if (args.K <= 64)
     hipLaunchKernelGGL((bf_query_kernel<BaseT, LPR, NCH, 1, MODE>), grid, dim3(kWave), 0, stream,
                        args);
@@ -251,6 +296,8 @@ static void launch_bf_scan(const BfLaunch& a, uint32_t slices, uint32_t rows_per
   args.rows_per_slice = rows_per_slice;
   args.qlist = qlist;
   args.qcount = qcount;
+  args.filter_bits = a.filter_bits;
+  args.filter_bit_offset = a.filter_bit_offset;
   args.ids = slices > 1 ? tmp_ids : a.ids;
   args.dists = slices > 1 ? tmp_dists : a.dists;
 
@@ -308,7 +355,8 @@ void launch_bf_query(const BfLaunch& a, hipStream_t stream)
   if (a.Nq == 0)
     return;
   // large batches: Q x B^T on the matrix cores (bf_mfma.hip); hook BF_SCAN = 1 forces the scan
-  const bool force_scan = hook(kHookBfScan) == 1;
+  // (a filtered call always scans: there is no filtered matrix-core path)
+  const bool force_scan = hook(kHookBfScan) == 1 || a.filter_bits != nullptr;
   if (!force_scan && bf_mfma_supported(a)) {
     launch_bf_query_mfma(a, stream);
     return;

@@ -150,6 +150,10 @@ struct QueryLaunch {
   const float* ps_params{nullptr};
   uint32_t ps_Dc{0};
   uint32_t* n_rows{nullptr};  // optional [Nq x 2]: float rows and code rows read per query
+  // optional allowed-id bitset (device; bit (id + filter_bit_offset) of the uint32 words): the
+  // search reports allowed ids only (query_filtered.hip)
+  const uint32_t* filter_bits{nullptr};
+  uint32_t filter_bit_offset{0};
 };
 void launch_query(const QueryLaunch& a, hipStream_t stream);
 
@@ -192,6 +196,10 @@ struct BfLaunch {
   // optional (device): number of queries the matrix-core path could not certify and answered
   // with the scan kernel instead (0 on the scan path)
   uint32_t* n_rescanned{nullptr};
+  // optional allowed-id bitset (device; bit (row + filter_bit_offset)): the exact K nearest among
+  // the allowed rows, on the scan kernels (bf_query.hip)
+  const uint32_t* filter_bits{nullptr};
+  uint32_t filter_bit_offset{0};
 };
 void launch_bf_query(const BfLaunch& a, hipStream_t stream);
 

@@ -310,6 +310,10 @@ struct DeviceCtx {
   hipEvent_t shard_done[kShardStreams] = {nullptr, nullptr, nullptr, nullptr};
   hipEvent_t ev_ready{nullptr};
   DeviceBuffer bf_rescanned;    // one uint32: queries of the last bf_query answered by the scan
+  // filtered call in progress (query_filtered / bf_query_filtered): the whole allowed-id bitset on
+  // this GPU (the caller's own memory or filter_stage); null otherwise
+  DeviceBuffer filter_stage;
+  const uint32_t* filter_bits{nullptr};
   std::unique_ptr<SwapState> swap;  // out-of-core shards (null: every shard resident)
   // Result staging of query() / query_async(): grown on demand, kept between calls.  One set per
   // lane: lanes [0, kShardStreams) belong to the asynchronous slots (their streams), lane
@@ -467,6 +471,13 @@ struct ggnn_handle {
   ggnn_build_work build_work{};  // collect_counters during build(): see ggnn_last_build_work
   std::mutex build_work_mutex;   // one host thread per GPU accounts into it
   uint32_t last_bf_rescanned{0};
+  // allowed-id bitset of the filtered call in progress as the caller gave it (null: no filter)
+  struct FilterSpec {
+    const uint32_t* bits{nullptr};
+    uint64_t n_bits{0};
+    ggnn_location loc{GGNN_CPU};
+    int gpu{0};
+  } active_filter;
 
   std::string last_error;
 
@@ -570,6 +581,23 @@ struct ggnn_handle {
   void query(const void* q, uint64_t Nq, uint32_t D, ggnn_dtype dtype, ggnn_location loc,
              int q_gpu, uint32_t k_query, float tau_query, uint32_t max_iterations,
              ggnn_measure measure, int32_t* ids_out, float* dists_out, ggnn_location out_loc);
+
+  // filtered calls: the blocking query() / bf_query() with an allowed-id bitset over the global
+  // base ids (n_bits == base_N), shared by all queries of the batch
+  void query_filtered(const void* q, uint64_t Nq, uint32_t D, ggnn_dtype dtype, ggnn_location loc,
+                      int q_gpu, uint32_t k_query, float tau_query, uint32_t max_iterations,
+                      ggnn_measure measure, int32_t* ids_out, float* dists_out,
+                      ggnn_location out_loc, const uint32_t* bits, uint64_t n_bits,
+                      ggnn_location filter_loc, int filter_gpu);
+  void bf_query_filtered(const void* q, uint64_t Nq, uint32_t D, ggnn_dtype dtype,
+                         ggnn_location loc, int q_gpu, uint32_t k_gt, ggnn_measure measure,
+                         int32_t* ids_out, float* dists_out, ggnn_location out_loc,
+                         const uint32_t* bits, uint64_t n_bits, ggnn_location filter_loc,
+                         int filter_gpu);
+  void begin_filter(const uint32_t* bits, uint64_t n_bits, ggnn_location loc, int gpu);
+  void end_filter();
+  // the active filter on ctx's GPU, copied on ctx.stream unless it already lives there (null: none)
+  const uint32_t* stage_filter(DeviceCtx& ctx);
 
   void query_split(const void* q, uint32_t nq, uint32_t D, ggnn_dtype dtype, ggnn_location loc,
                    int q_gpu, uint32_t k_query, float tau_query, uint32_t max_iterations,

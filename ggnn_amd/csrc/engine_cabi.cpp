@@ -359,6 +359,35 @@ ggnn_status ggnn_bf_query(ggnn_t* h, const void* query, uint64_t Nq, uint32_t D,
   });
 }
 
+ggnn_status ggnn_query_filtered(ggnn_t* h, const void* query, uint64_t Nq, uint32_t D,
+                                ggnn_dtype dtype, ggnn_location location, int gpu_id,
+                                uint32_t k_query, float tau_query, uint32_t max_iterations,
+                                ggnn_measure measure, int32_t* ids_out, float* dists_out,
+                                ggnn_location out_location, const uint32_t* allowed_bits,
+                                uint64_t n_bits, ggnn_location filter_location, int filter_gpu_id)
+{
+  GGNN_NEED_HANDLE(h);
+  return guarded(h, [&] {
+    h->query_filtered(query, Nq, D, dtype, location, gpu_id, k_query, tau_query, max_iterations,
+                      measure, ids_out, dists_out, out_location, allowed_bits, n_bits,
+                      filter_location, filter_gpu_id);
+  });
+}
+
+ggnn_status ggnn_bf_query_filtered(ggnn_t* h, const void* query, uint64_t Nq, uint32_t D,
+                                   ggnn_dtype dtype, ggnn_location location, int gpu_id,
+                                   uint32_t k_gt, ggnn_measure measure, int32_t* ids_out,
+                                   float* dists_out, ggnn_location out_location,
+                                   const uint32_t* allowed_bits, uint64_t n_bits,
+                                   ggnn_location filter_location, int filter_gpu_id)
+{
+  GGNN_NEED_HANDLE(h);
+  return guarded(h, [&] {
+    h->bf_query_filtered(query, Nq, D, dtype, location, gpu_id, k_gt, measure, ids_out, dists_out,
+                         out_location, allowed_bits, n_bits, filter_location, filter_gpu_id);
+  });
+}
+
 ggnn_status ggnn_get_graph(ggnn_t* h, uint32_t global_shard_id, ggnn_graph_view* out)
 {
   GGNN_NEED_HANDLE(h);
@@ -536,6 +565,54 @@ ggnn_status ggnn_op_query_prescreened(const float* base, uint32_t N_base, uint32
     q.ps_Dc = prescreen_code_dim(D);
     q.n_rows = n_rows;
     launch_query(q, static_cast<hipStream_t>(stream));
+  });
+}
+
+ggnn_status ggnn_op_query_filtered(const void* base, ggnn_dtype dtype, uint32_t N_base, uint32_t D,
+                                   const uint8_t* codes, const float* params, const void* query,
+                                   uint32_t Nq, const int32_t* graph0, uint32_t KBuild,
+                                   const int32_t* start, uint32_t num_start,
+                                   const float* nn1_stats, uint32_t k_query, float tau_query,
+                                   uint32_t max_iterations, ggnn_measure measure,
+                                   uint32_t shards_per_gpu, uint32_t on_gpu_shard, int32_t* ids,
+                                   float* dists, uint32_t* n_dist, uint32_t* n_pop,
+                                   uint32_t* n_rows, const uint32_t* filter_bits,
+                                   uint32_t filter_bit_offset, void* stream)
+{
+  return guarded(nullptr, [&] {
+    GGNN_REQUIRE(filter_bits != nullptr, GGNN_INVALID_ARGUMENT, "the filter bitset is null");
+    GGNN_REQUIRE(!codes == !params, GGNN_INVALID_ARGUMENT,
+                 "pre-screen codes and params go together");
+    GGNN_REQUIRE(!codes || dtype == GGNN_F32, GGNN_INVALID_ARGUMENT,
+                 "the pre-screen needs a float32 base");
+    QueryLaunch q{base,      query,          dtype,    N_base,         D,         Nq,
+                  graph0,    KBuild,         start,    num_start,      nn1_stats, k_query,
+                  tau_query, max_iterations, measure,  shards_per_gpu, on_gpu_shard, ids,
+                  dists,     n_dist,         n_pop};
+    if (codes) {
+      q.ps_codes = codes;
+      q.ps_params = params;
+      q.ps_Dc = prescreen_code_dim(D);
+    }
+    q.n_rows = n_rows;
+    q.filter_bits = filter_bits;
+    q.filter_bit_offset = filter_bit_offset;
+    launch_query(q, static_cast<hipStream_t>(stream));
+  });
+}
+
+ggnn_status ggnn_op_bf_query_filtered(const void* base, ggnn_dtype dtype, uint32_t N_base,
+                                      uint32_t D, const void* query, uint32_t Nq,
+                                      uint32_t k_query, ggnn_measure measure, int32_t* ids,
+                                      float* dists, const uint32_t* filter_bits,
+                                      uint32_t filter_bit_offset, void* stream)
+{
+  return guarded(nullptr, [&] {
+    GGNN_REQUIRE(filter_bits != nullptr, GGNN_INVALID_ARGUMENT, "the filter bitset is null");
+    BfLaunch b{base, query, dtype, N_base, D, Nq, k_query, measure, ids, dists};
+    b.filter_bits = filter_bits;
+    b.filter_bit_offset = filter_bit_offset;
+    launch_bf_query(b, static_cast<hipStream_t>(stream));
   });
 }
 

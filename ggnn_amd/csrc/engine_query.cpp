@@ -47,6 +47,7 @@ void ggnn_handle::query_device(DeviceCtx& ctx, const void* d_query, uint32_t nq,
 {
   hipStream_t stream = ctx.stream;
   const uint32_t spg = shards_per_gpu;
+  ctx.filter_bits = stage_filter(ctx);
   DeviceBuffer c_dist, c_pop, c_rows;
   if (collect_counters) {
     c_dist.alloc(static_cast<size_t>(nq) * 4);
@@ -109,6 +110,8 @@ void ggnn_handle::query_device(DeviceCtx& ctx, const void* d_query, uint32_t nq,
       ql.ps_Dc = prescreen_code_dim(pad_D);
     }
     ql.n_rows = c_rows.as<uint32_t>();
+    ql.filter_bits = ctx.filter_bits;
+    ql.filter_bit_offset = sh.global_id * cfg.N;
     if (overlap) {
       launch_query(ql, ctx.shard_stream[si % DeviceCtx::kShardStreams]);
       continue;
@@ -247,6 +250,7 @@ void ggnn_handle::query_split(const void* q, uint32_t nq, uint32_t D, ggnn_dtype
       (void)ensure_prescreen(ctx, si, measure);
     ctx.ensure_shard_streams();
     staged[g] = stage_query(ctx, q, nq, D, dtype, loc, q_gpu);
+    ctx.filter_bits = stage_filter(ctx);
     GGNN_HIP_CHECK(hipEventRecord(ctx.ev_ready, ctx.stream));
     GGNN_HIP_CHECK(hipEventRecord(ctx.ev_a, ctx.stream));
     for (int half = 0; half < 2; ++half) {
@@ -412,6 +416,8 @@ void ggnn_handle::enqueue_local_search(DeviceCtx& ctx, int lane, const void* d_q
       ql.ps_params = sh.ps_params.as<float>();
       ql.ps_Dc = prescreen_code_dim(pad_D);
     }
+    ql.filter_bits = ctx.filter_bits;  // (null outside a filtered blocking call)
+    ql.filter_bit_offset = sh.global_id * cfg.N;
     launch_query(ql, stream);
   }
   if (shards_per_gpu > 1)
@@ -495,6 +501,7 @@ void ggnn_handle::bf_query(const void* q, uint64_t Nq, uint32_t D, ggnn_dtype dt
     ctx.bf_rescanned.alloc(sizeof(uint32_t));
   BfLaunch bl{bf_base, sq.ptr, base_dtype, static_cast<uint32_t>(base_N), pad_D, nq, k_gt,
               measure,    d_ids,  d_dists,    ctx.bf_rescanned.as<uint32_t>()};
+  bl.filter_bits = stage_filter(ctx);
   EventTimer timer(ctx.stream, ctx.ev_a, ctx.ev_b);
   launch_bf_query(bl, ctx.stream);
   bf_ms = timer.stop();
@@ -509,4 +516,69 @@ void ggnn_handle::bf_query(const void* q, uint64_t Nq, uint32_t D, ggnn_dtype dt
                                   hipMemcpyDeviceToHost, ctx.stream));
   }
   GGNN_HIP_CHECK(hipStreamSynchronize(ctx.stream));
+}
+
+// ---- filtered calls ---------------------------------------------------------------------------
+void ggnn_handle::begin_filter(const uint32_t* bits, uint64_t n_bits, ggnn_location loc, int gpu)
+{
+  GGNN_REQUIRE(bits != nullptr, GGNN_INVALID_ARGUMENT, "the filter bitset is null");
+  GGNN_REQUIRE(!base_set || n_bits == base_N, GGNN_INVALID_ARGUMENT,
+               "the filter needs one bit per base vector (n_bits must equal N)");
+  GGNN_REQUIRE(base_set, GGNN_INVALID_STATE, "There is no base dataset the filter could refer to.");
+  active_filter.bits = bits;
+  active_filter.n_bits = n_bits;
+  active_filter.loc = loc;
+  active_filter.gpu = gpu;
+}
+
+void ggnn_handle::end_filter()
+{
+  active_filter = FilterSpec{};
+  for (DeviceCtx& ctx : devs)
+    ctx.filter_bits = nullptr;
+}
+
+const uint32_t* ggnn_handle::stage_filter(DeviceCtx& ctx)
+{
+  const FilterSpec& f = active_filter;
+  if (!f.bits)
+    return nullptr;
+  if (f.loc == GGNN_GPU && f.gpu == ctx.device && (reinterpret_cast<uintptr_t>(f.bits) & 3u) == 0)
+    return f.bits;
+  const size_t bytes = static_cast<size_t>((f.n_bits + 31) / 32) * sizeof(uint32_t);
+  DeviceCtx::grow(ctx.filter_stage, bytes);
+  GGNN_HIP_CHECK(hipMemcpyAsync(ctx.filter_stage.p, f.bits, bytes,
+                                f.loc == GGNN_GPU ? hipMemcpyDefault : hipMemcpyHostToDevice,
+                                ctx.stream));
+  return ctx.filter_stage.as<uint32_t>();
+}
+
+namespace {
+struct FilterScope {
+  ggnn_handle& h;
+  ~FilterScope() { h.end_filter(); }
+};
+}  // namespace
+
+void ggnn_handle::query_filtered(const void* q, uint64_t Nq, uint32_t D, ggnn_dtype dtype,
+                                 ggnn_location loc, int q_gpu, uint32_t k_query, float tau_query,
+                                 uint32_t max_iterations, ggnn_measure measure, int32_t* ids_out,
+                                 float* dists_out, ggnn_location out_loc, const uint32_t* bits,
+                                 uint64_t n_bits, ggnn_location filter_loc, int filter_gpu)
+{
+  begin_filter(bits, n_bits, filter_loc, filter_gpu);
+  FilterScope scope{*this};
+  query(q, Nq, D, dtype, loc, q_gpu, k_query, tau_query, max_iterations, measure, ids_out,
+        dists_out, out_loc);
+}
+
+void ggnn_handle::bf_query_filtered(const void* q, uint64_t Nq, uint32_t D, ggnn_dtype dtype,
+                                    ggnn_location loc, int q_gpu, uint32_t k_gt,
+                                    ggnn_measure measure, int32_t* ids_out, float* dists_out,
+                                    ggnn_location out_loc, const uint32_t* bits, uint64_t n_bits,
+                                    ggnn_location filter_loc, int filter_gpu)
+{
+  begin_filter(bits, n_bits, filter_loc, filter_gpu);
+  FilterScope scope{*this};
+  bf_query(q, Nq, D, dtype, loc, q_gpu, k_gt, measure, ids_out, dists_out, out_loc);
 }

@@ -437,6 +437,9 @@ static void launch_query_cfg(const QueryArgs& args, bool use_ps, ggnn_measure me
 // float16 / bfloat16 rows (no pre-screen): query_16.hip
 void launch_query_16(const QueryArgs& args, ggnn_measure measure, ggnn_dtype dtype,
                      hipStream_t stream);
+// restricted to an allowed-id bitset: query_filtered.hip
+void launch_query_filtered(const QueryArgs& args, bool use_ps, ggnn_measure measure,
+                           ggnn_dtype dtype, hipStream_t stream);
 
 void launch_query(const QueryLaunch& a, hipStream_t stream)
 {
@@ -486,8 +489,10 @@ void launch_query(const QueryLaunch& a, hipStream_t stream)
   const bool global_ring = args.sorted <= 64 && vis_hash_regs(vis) != 0 && a.max_iterations <= vis &&
                            a.KBuild <= 8 * kEarlySteps && hook(kHookQueryEarly) != 0 &&
                            hook(kHookQueryGlobalRing) != 0 && early_shape && set_shape;
-  if (global_ring || (args.sorted <= 64 && set_shape && tag_set_usable(vis, a.N_base) &&
-                      hook(kHookVisTagSet) != 0)) {
+  // (the filtered kernels keep their ring in LDS: no scratch)
+  if (!a.filter_bits &&
+      (global_ring || (args.sorted <= 64 && set_shape && tag_set_usable(vis, a.N_base) &&
+                       hook(kHookVisTagSet) != 0))) {
     args.tag_bits = global_ring ? 0 : tag_set_bucket_bits(vis);
     try {
       args.ring = static_cast<int32_t*>(
@@ -521,7 +526,12 @@ void launch_query(const QueryLaunch& a, hipStream_t stream)
     args.ps_Dc = a.ps_Dc;
   }
 
-  if (dtype_is_16bit(a.dtype)) {
+  if (a.filter_bits) {
+    args.filter_bits = a.filter_bits;
+    args.filter_bit_offset = a.filter_bit_offset;
+    launch_query_filtered(args, use_ps, a.measure, a.dtype, stream);
+  }
+  else if (dtype_is_16bit(a.dtype)) {
     launch_query_16(args, a.measure, a.dtype, stream);
   }
   else {

@@ -27,6 +27,10 @@ struct QueryArgs {
   // global memory (scratch of the launch) and the bucket bits of the set
   int32_t* ring;
   uint32_t tag_bits;
+  // filtered search (query_filtered.hip): allowed-id bitset over the global ids and the first
+  // global id of this shard; null for the unfiltered kernels
+  const uint32_t* filter_bits;
+  uint32_t filter_bit_offset;
 };
 
 }  // namespace ggnn_amd

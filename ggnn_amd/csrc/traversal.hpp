@@ -530,7 +530,8 @@ struct SortedList {
   }
 
   // simple_knn_cache.cuh:126-213 in lane form (oracle/wave_model.hpp::push)
-  GGNN_DEV void push(int k, float d)
+  // denied (wave-uniform, filtered search): the key may be queued but never enters the best list
+  GGNN_DEV void push(int k, float d, const bool denied = false)
   {
     bool dup = false;
 #pragma unroll
@@ -555,7 +556,7 @@ struct SortedList {
         bool low_active = false;
 #pragma unroll
         for (int r = g * 4 + 3; r >= g * 4; --r)
-          low_active = push_step(r, k, d, qlane);
+          low_active = push_step(r, k, d, qlane, denied);
         if ((g * 4 + 1) * kWave <= BEST && !__any(low_active))
           settled = true;
       }
@@ -563,12 +564,13 @@ struct SortedList {
     else {
 #pragma unroll
       for (int r = R - 1; r >= 0; --r)
-        push_step(r, k, d, qlane);
+        push_step(r, k, d, qlane, denied);
     }
   }
 
   // one register of push(): entry i takes (k, d) at the insertion point, its lower neighbour above
-  GGNN_DEV bool push_step(const int r, const int k, const float d, const int qlane)
+  GGNN_DEV bool push_step(const int r, const int k, const float d, const int qlane,
+                          const bool denied = false)
   {
     const int lane = threadIdx.x;
     const int i = r * kWave + lane;
@@ -583,7 +585,7 @@ struct SortedList {
       }
     }
     const bool first = (i == 0) || (i == BEST);
-    const bool active = (dist[r] >= d) && (i < SORTED);
+    const bool active = (dist[r] >= d) && (i < SORTED) && !(denied && i < BEST);
     const bool prev_active = !first && (pd >= d);
     if (active) {
       if (first || !prev_active) {
@@ -966,7 +968,8 @@ struct LdsList {
   //  * an inserting lane and the lane left of it never write the same slot for the same reason;
   //  * writes of a chunk touch the chunk itself and the first slot of the chunk above, which was
   //    read an iteration earlier.
-  GGNN_DEV void push(int k, float d)
+  // denied (wave-uniform, filtered search): logical entries below BEST are never active
+  GGNN_DEV void push(int k, float d, const bool denied = false)
   {
     const int lane = threadIdx.x;
     __syncthreads();
@@ -980,7 +983,7 @@ struct LdsList {
     for (int block_start = (SORTED + kWave - 1) / kWave * kWave - kWave; block_start >= 0;
          block_start -= kWave) {
       const int li = block_start + lane;
-      bool active = li < SORTED;
+      bool active = li < SORTED && !(denied && li < BEST);
       int idx = 0, r_key = kEmptyKey;
       float r_dist = 0.f, p_dist = -inf_f();
       if (active) {
@@ -1607,13 +1610,68 @@ GGNN_DEV int prescreen_pass(const PS& ps, const WaveLds& lds, int nsurv, float s
 struct NoHook {
   GGNN_DEV void operator()() const {}
 };
-template <int MODE, bool FILTER, class SL, class DE, class PS, class HOOK = NoHook>
+
+// Allowed-id bitset of a filtered search (query_filtered.hip): id i is allowed iff bit
+// (i + offset) & 31 of word (i + offset) >> 5 is set (offset: first global id of the shard).
+// request(): every lane asks for the word of the candidate it holds -- one dword gather, issued
+// in front of the candidates' first-read rows, so that it travels with them and the wait for the
+// rows covers it (loads return in order).  The verdict is taken at the replay: denied(dl, k) says
+// whether candidate k of the last request is denied, a compare and a ballot per pushed candidate.
+struct NoIdFilter {
+  static constexpr bool enabled = false;
+};
+struct IdFilter {
+  static constexpr bool enabled = true;
+  const uint32_t* bits;
+  uint32_t offset;
+  int key;        // the candidate this lane asked for (or EMPTY)
+  uint32_t word;  // its word of the bitset
+  GGNN_DEV void request(const int cand)
+  {
+    key = cand;
+    // EMPTY slots read the word of the shard's first id (verdict ignored)
+    word = bits[(static_cast<uint32_t>(max(cand, 0)) + offset) >> 5];
+  }
+  // lanes whose candidate is denied
+  GGNN_DEV unsigned long long denied_lanes() const
+  {
+    const uint32_t b = static_cast<uint32_t>(key) + offset;
+    return __ballot(key != kEmptyKey && !((word >> (b & 31u)) & 1u));
+  }
+  GGNN_DEV bool denied(const unsigned long long dl, const int k) const
+  {
+    return (__ballot(key == k) & dl) != 0ull;
+  }
+};
+
+// the replay of a fetch (simple_knn_cache.cuh:268-286) under a filter: as replay_lanes() below,
+// a denied candidate is pushed with the flag
+template <class SL>
+GGNN_DEV void replay_lanes_filtered(SL& sl, unsigned long long m, const int k_of, const float d_of,
+                                    const IdFilter& filt)
+{
+  const unsigned long long dl = filt.denied_lanes();
+  while (m) {
+    const int j = __ffsll(static_cast<long long>(m)) - 1;
+    m &= m - 1;
+    const float d = rdlanef(d_of, j);
+    const int k = rdlane(k_of, j);
+    if (d < sl.criteria())
+      sl.push(k, d, dl != 0ull && filt.denied(dl, k));
+  }
+}
+
+template <int MODE, bool FILTER, class SL, class DE, class PS, class HOOK = NoHook,
+          class FILT = NoIdFilter>
 GGNN_DEV int fetch(SL& sl, const DE& de, const WaveLds& lds, int cand,
                    const int32_t* translation, const PS& ps, uint2& rows,
-                   HOOK&& after_filter = NoHook{})
+                   HOOK&& after_filter = NoHook{}, FILT&& filt = FILT{})
 {
+  constexpr bool kFiltered = std::remove_reference_t<FILT>::enabled;
   const int lane = threadIdx.x;
   cand = lower_half_to_both(cand);
+  if constexpr (kFiltered)
+    filt.request(cand);
   GGNN_TICK(1);  // graph row arrived
   if (FILTER)
     cand = sl.filter(cand, lds.known);
@@ -1654,6 +1712,10 @@ GGNN_DEV int fetch(SL& sl, const DE& de, const WaveLds& lds, int cand,
   const int ck = lane < neval ? lds.ckeys[lane] : kEmptyKey;
   // criteria() never increases during a fetch, so candidates failing it now fail it later
   unsigned long long m = __ballot(cd < sl.criteria());
+  if constexpr (kFiltered) {
+    replay_lanes_filtered(sl, m, ck, cd, filt);
+    return nsurv;
+  }
   while (m) {
     const int j = __ffsll(static_cast<long long>(m)) - 1;
     m &= m - 1;
@@ -1772,11 +1834,15 @@ GGNN_DEV void replay_lanes(SL& sl, unsigned long long m, const int k_of, const f
 // the sorted part moves behind the verdicts (SortedList::drop_sorted) -- same candidates on the
 // float rows, same pushes, same results; the return value and `rows` then count the survivors of
 // the VISITED test only and are not used.
-template <int MODE, bool COUNT = true, class SL, class DE, class PS, class ER, class HOOK>
+// filt (filtered search): the caller has requested the bit words of `cand` (IdFilter::request)
+// in front of er.issue()
+template <int MODE, bool COUNT = true, class SL, class DE, class PS, class ER, class HOOK,
+          class FILT = NoIdFilter>
 GGNN_DEV int fetch_early(SL& sl, const DE& de, const WaveLds& lds, int cand, const ER& er,
                          const PS& ps, uint2& rows, HOOK&& after_filter,
-                         const int32_t* translation = nullptr)
+                         const int32_t* translation = nullptr, FILT&& filt = FILT{})
 {
+  constexpr bool kFiltered = std::remove_reference_t<FILT>::enabled;
   const int lane = threadIdx.x;
   const int grp = lane >> 3, w = lane & 7;
   cand = sl.template filter<false, COUNT>(lower_half_to_both(cand), lds.known);
@@ -1825,7 +1891,10 @@ GGNN_DEV int fetch_early(SL& sl, const DE& de, const WaveLds& lds, int cand, con
     __syncthreads();
     const float cd = lane < neval ? lds.cd0[lane] : inf_f();
     const int ck = lane < neval ? lds.ckeys[lane] : kEmptyKey;
-    replay_lanes(sl, __ballot(cd < sl.criteria()), ck, cd);
+    if constexpr (kFiltered)
+      replay_lanes_filtered(sl, __ballot(cd < sl.criteria()), ck, cd, filt);
+    else
+      replay_lanes(sl, __ballot(cd < sl.criteria()), ck, cd);
     return nsurv;
   }
   else {
@@ -1849,7 +1918,10 @@ GGNN_DEV int fetch_early(SL& sl, const DE& de, const WaveLds& lds, int cand, con
     unsigned long long m = __ballot(alive && dmine < sl.criteria());
     if constexpr (!COUNT)
       m = sl.drop_sorted(m, mykey);
-    replay_lanes(sl, m, mykey, dmine);
+    if constexpr (kFiltered)
+      replay_lanes_filtered(sl, m, mykey, dmine, filt);
+    else
+      replay_lanes(sl, m, mykey, dmine);
     return nsurv;
   }
 }

@@ -152,6 +152,56 @@ def query(base, query, graph0, start, nn1_stats, k_query, tau_query, max_iterati
     return ids, dists
 
 
+def query_filtered(base, query, graph0, start, nn1_stats, k_query, tau_query, filter_bits,
+                   max_iterations=400, measure=EUCLIDEAN, filter_bit_offset=0, shards_per_gpu=1,
+                   on_gpu_shard=0, counters=False, prescreen=None, rows_read=None):
+    """`query` restricted to an allowed-id bitset: filter_bits is a packed int32 CUDA tensor
+    (ggnn_amd.pack_filter), key k of this shard is allowed iff bit k + filter_bit_offset is set.
+    prescreen: optional (codes, params) of prescreen_encode(base, measure) (float32)."""
+    _need(base, name="base"), _need(query, base.dtype, "query")
+    _need(graph0, torch.int32, "graph0"), _need(start, torch.int32, "start")
+    _need(nn1_stats, torch.float32, "nn1_stats"), _need(filter_bits, torch.int32, "filter_bits")
+    if filter_bits.numel() * 32 < filter_bit_offset + base.shape[0]:
+        raise ValueError("filter_bits is shorter than filter_bit_offset + N bits")
+    Nq = query.shape[0]
+    ids = torch.empty((Nq, k_query * shards_per_gpu), dtype=torch.int32, device=base.device)
+    dists = torch.empty((Nq, k_query * shards_per_gpu), dtype=torch.float32, device=base.device)
+    nd = npop = None
+    if counters:
+        nd = torch.zeros(Nq, dtype=torch.int32, device=base.device)
+        npop = torch.zeros(Nq, dtype=torch.int32, device=base.device)
+    codes, params = prescreen if prescreen is not None else (None, None)
+    if prescreen is not None:
+        _need(base, torch.float32, "base"), _need(codes, torch.uint8, "codes")
+        _need(params, torch.float32, "params")
+    check(lib().ggnn_op_query_filtered(
+        _ptr(base), _dtype_code(base), base.shape[0], base.shape[1], _ptr(codes), _ptr(params),
+        _ptr(query), Nq, _ptr(graph0), graph0.shape[1], _ptr(start), start.numel(),
+        _ptr(nn1_stats), k_query, tau_query, max_iterations, measure, shards_per_gpu,
+        on_gpu_shard, _ptr(ids), _ptr(dists), _ptr(nd), _ptr(npop), _ptr(rows_read),
+        _ptr(filter_bits), filter_bit_offset, _stream()))
+    if counters:
+        return ids, dists, nd, npop
+    return ids, dists
+
+
+def bf_query_filtered(base, query, k_query, filter_bits, measure=EUCLIDEAN, filter_bit_offset=0):
+    """the exact k nearest among the rows the bitset allows (row i: bit i + filter_bit_offset);
+    slots beyond the number of allowed rows are (-1, +inf)"""
+    _need(base, name="base"), _need(query, base.dtype, "query")
+    _need(filter_bits, torch.int32, "filter_bits")
+    if filter_bits.numel() * 32 < filter_bit_offset + base.shape[0]:
+        raise ValueError("filter_bits is shorter than filter_bit_offset + N bits")
+    Nq = query.shape[0]
+    ids = torch.empty((Nq, k_query), dtype=torch.int32, device=base.device)
+    dists = torch.empty((Nq, k_query), dtype=torch.float32, device=base.device)
+    check(lib().ggnn_op_bf_query_filtered(_ptr(base), _dtype_code(base), base.shape[0],
+                                          base.shape[1], _ptr(query), Nq, k_query, measure,
+                                          _ptr(ids), _ptr(dists), _ptr(filter_bits),
+                                          filter_bit_offset, _stream()))
+    return ids, dists
+
+
 def bf_query(base, query, k_query, measure=EUCLIDEAN, rescanned=False):
     """rescanned=True: also return how many queries the matrix-core path handed to the scan"""
     _need(base, name="base"), _need(query, base.dtype, "query")

@@ -133,6 +133,42 @@ class GGNN {
     return r;
   }
 
+  // Extensions (the reference has no filter): query / bfQuery among the base vectors a bitset
+  // allows -- uint32 words over the global base ids, id i allowed iff bit (i & 31) of word
+  // (i >> 5) is set, n_bits == N; on the host, or on GPU bits_gpu_id (see ggnn_query_filtered)
+  [[nodiscard]] virtual Results queryFiltered(
+      const GenericDataset& query, const uint32_t KQuery, const float tau_query,
+      const uint32_t* allowed_bits, const uint64_t n_bits, const uint32_t max_iterations = 400,
+      const DistanceMeasure measure = DistanceMeasure::Euclidean, const bool bits_on_gpu = false,
+      const int bits_gpu_id = 0)
+  {
+    const uint32_t width = on_gpu_ ? KQuery * num_shards() : KQuery;
+    Results r = make_results(query, width);
+    detail::check(
+        ggnn_query_filtered(h_, query.raw(), query.N, query.D, dtype_of(query), loc_of(query),
+                            query.gpu_id, KQuery, tau_query, max_iterations,
+                            static_cast<ggnn_measure>(measure), r.ids.data(), r.dists.data(),
+                            on_gpu_ ? GGNN_GPU : GGNN_CPU, allowed_bits, n_bits,
+                            bits_on_gpu ? GGNN_GPU : GGNN_CPU, bits_gpu_id),
+        h_);
+    return r;
+  }
+  [[nodiscard]] virtual Results bfQueryFiltered(
+      const GenericDataset& query, const uint32_t* allowed_bits, const uint64_t n_bits,
+      const uint32_t KGT = 100, const DistanceMeasure measure = DistanceMeasure::Euclidean,
+      const bool bits_on_gpu = false, const int bits_gpu_id = 0)
+  {
+    Results r = make_results(query, KGT);
+    detail::check(
+        ggnn_bf_query_filtered(h_, query.raw(), query.N, query.D, dtype_of(query), loc_of(query),
+                               query.gpu_id, KGT, static_cast<ggnn_measure>(measure),
+                               r.ids.data(), r.dists.data(), on_gpu_ ? GGNN_GPU : GGNN_CPU,
+                               allowed_bits, n_bits, bits_on_gpu ? GGNN_GPU : GGNN_CPU,
+                               bits_gpu_id),
+        h_);
+    return r;
+  }
+
   [[nodiscard]] virtual const Graph& getGraph(const uint32_t global_shard_id = 0)
   {
     ggnn_graph_view v{};

@@ -132,6 +132,36 @@ ggnn_status ggnn_bf_query(ggnn_t* h, const void* query, uint64_t Nq, uint32_t D,
                           ggnn_measure measure, int32_t* ids_out, float* dists_out,
                           ggnn_location out_location);
 
+/* Filtered search (an extension: the reference has no filter).  ggnn_query / ggnn_bf_query
+ * restricted to the base vectors a bitset allows: one filter per call, shared by all queries of
+ * the batch, over the GLOBAL base ids -- uint32 words, id i is allowed iff bit (i & 31) of word
+ * (i >> 5) is set, ceil(n_bits / 32) words, bits at and above n_bits are ignored.  n_bits must
+ * equal the base's N (GGNN_INVALID_ARGUMENT otherwise, also for a null bitset).  The bitset
+ * may live on the host (filter_location GGNN_CPU; copied per call) or on GPU filter_gpu_id;
+ * every GPU of the handle gets the whole bitset.
+ * ggnn_query_filtered: the traversal of ggnn_query in which a denied vector still routes the
+ * search (it is evaluated, queued, popped and expanded) but never enters the best list; the
+ * termination rule then widens by itself until k_query ALLOWED vectors are found.  An all-ones
+ * filter gives the result of ggnn_query bit for bit; slots that could not be filled hold
+ * distance +inf and id -1 (plus the shard's id offset, as ggnn_query writes an unfilled slot).
+ * Raise max_iterations / tau_query as the filter narrows; for very selective filters
+ * ggnn_bf_query_filtered is the better call.  Works with several shards per GPU, several GPUs and
+ * out-of-core shards; counters and timings are reported as for ggnn_query.
+ * ggnn_bf_query_filtered: the exact k_gt nearest among the allowed vectors (ties: lower id first),
+ * on the exhaustive scan kernels (there is no filtered matrix-core path). */
+ggnn_status ggnn_query_filtered(ggnn_t* h, const void* query, uint64_t Nq, uint32_t D,
+                                ggnn_dtype dtype, ggnn_location location, int gpu_id,
+                                uint32_t k_query, float tau_query, uint32_t max_iterations,
+                                ggnn_measure measure, int32_t* ids_out, float* dists_out,
+                                ggnn_location out_location, const uint32_t* allowed_bits,
+                                uint64_t n_bits, ggnn_location filter_location, int filter_gpu_id);
+ggnn_status ggnn_bf_query_filtered(ggnn_t* h, const void* query, uint64_t Nq, uint32_t D,
+                                   ggnn_dtype dtype, ggnn_location location, int gpu_id,
+                                   uint32_t k_gt, ggnn_measure measure, int32_t* ids_out,
+                                   float* dists_out, ggnn_location out_location,
+                                   const uint32_t* allowed_bits, uint64_t n_bits,
+                                   ggnn_location filter_location, int filter_gpu_id);
+
 /* layout of one graph shard, include/ggnn/base/graph_config.h:31-112 */
 typedef struct {
   uint32_t N, D, KBuild;
@@ -360,6 +390,27 @@ ggnn_status ggnn_op_query_prescreened(const float* base, uint32_t N_base, uint32
                                       uint32_t shards_per_gpu, uint32_t on_gpu_shard, int32_t* ids,
                                       float* dists, uint32_t* n_dist, uint32_t* n_pop,
                                       uint32_t* n_rows, void* stream);
+
+/* ggnn_op_query restricted to an allowed-id bitset (device memory): candidate key k of this
+ * shard is allowed iff bit (k + filter_bit_offset) of filter_bits is set (filter_bit_offset: the
+ * shard's first global id).  codes / params: the pre-screen copy of a float32 base, or both NULL
+ * (no pre-screen).  n_rows: optional [Nq x 2]. */
+ggnn_status ggnn_op_query_filtered(const void* base, ggnn_dtype dtype, uint32_t N_base, uint32_t D,
+                                   const uint8_t* codes, const float* params, const void* query,
+                                   uint32_t Nq, const int32_t* graph0, uint32_t KBuild,
+                                   const int32_t* start, uint32_t num_start,
+                                   const float* nn1_stats, uint32_t k_query, float tau_query,
+                                   uint32_t max_iterations, ggnn_measure measure,
+                                   uint32_t shards_per_gpu, uint32_t on_gpu_shard, int32_t* ids,
+                                   float* dists, uint32_t* n_dist, uint32_t* n_pop,
+                                   uint32_t* n_rows, const uint32_t* filter_bits,
+                                   uint32_t filter_bit_offset, void* stream);
+/* ggnn_op_bf_query among the allowed rows only (scan kernels); unfilled slots are (-1, +inf) */
+ggnn_status ggnn_op_bf_query_filtered(const void* base, ggnn_dtype dtype, uint32_t N_base,
+                                      uint32_t D, const void* query, uint32_t Nq,
+                                      uint32_t k_query, ggnn_measure measure, int32_t* ids,
+                                      float* dists, const uint32_t* filter_bits,
+                                      uint32_t filter_bit_offset, void* stream);
 
 /* QueryKernels::bruteForceQuery  query_kernels.cu:188-264 -> bf_query_layer.cu:39-65 */
 ggnn_status ggnn_op_bf_query(const void* base, ggnn_dtype dtype, uint32_t N_base, uint32_t D,
