@@ -93,6 +93,66 @@ def pack_filter(mask):
     return torch.from_numpy(words.view(np.int32).copy())
 
 
+def pack_filters(masks):
+    """Pack F boolean masks over the base ids ([F, N], numpy / torch) into a filter table for
+    `GGNN.set_filters`: int32 words [F, ceil(N / 32)], row f is `pack_filter(masks[f])`.  The
+    result lives where the masks live: CUDA masks are packed on their GPU (one ballot per 64
+    rows, no host round trip), anything else on the host."""
+    if isinstance(masks, np.ndarray):
+        masks = torch.from_numpy(np.ascontiguousarray(masks))
+    if not isinstance(masks, torch.Tensor) or masks.dtype != torch.bool or masks.dim() != 2:
+        raise TypeError("masks must be a 2-dimensional boolean array [F, N]")
+    F, N = masks.shape
+    words = (N + 31) // 32
+    if masks.is_cuda:
+        from . import ops
+        return ops.pack_filters(masks)
+    m = masks.detach().numpy()
+    out = np.zeros((F, words * 4), np.uint8)
+    if N:
+        packed = np.packbits(m, axis=1, bitorder="little")
+        out[:, :packed.shape[1]] = packed
+    return torch.from_numpy(out.view(np.int32).reshape(F, words).copy())
+
+
+def _filter_table(filters, N):
+    """the `filters` argument of set_filters as a contiguous int32 tensor [F, ceil(N / 32)] (CPU or
+    CUDA): boolean masks [F, N] are packed where they live, int32 / uint32 words are taken as
+    already packed"""
+    if isinstance(filters, np.ndarray) and filters.dtype == np.uint32:
+        filters = filters.view(np.int32)
+    if isinstance(filters, np.ndarray):
+        filters = torch.from_numpy(np.ascontiguousarray(filters))
+    if not isinstance(filters, torch.Tensor) or filters.dim() != 2:
+        raise TypeError("filters must be a 2-dimensional numpy array or torch tensor")
+    if filters.dtype == torch.bool:
+        if filters.shape[1] != N:
+            raise ValueError(f"boolean filters need one column per base vector ({N})")
+        return pack_filters(filters)
+    if hasattr(torch, "uint32") and filters.dtype == torch.uint32:
+        filters = filters.view(torch.int32)
+    if filters.dtype != torch.int32:
+        raise TypeError("filters must be boolean, or int32 / uint32 words of packed bitsets")
+    if filters.shape[1] != (N + 31) // 32:
+        raise ValueError(f"packed filters need ceil(N / 32) = {(N + 31) // 32} words per row")
+    return filters.contiguous()
+
+
+def _filter_ids(filter_ids, Nq):
+    """the `filter_ids` argument as a contiguous 1-D int32 tensor of length Nq (int64 is converted)"""
+    if isinstance(filter_ids, np.ndarray):
+        filter_ids = torch.from_numpy(np.ascontiguousarray(filter_ids))
+    if not isinstance(filter_ids, torch.Tensor) or filter_ids.dim() != 1:
+        raise TypeError("filter_ids must be a 1-dimensional numpy array or torch tensor")
+    if filter_ids.dtype == torch.int64:
+        filter_ids = filter_ids.to(torch.int32)
+    if filter_ids.dtype != torch.int32:
+        raise TypeError("filter_ids must be int32 (or int64)")
+    if filter_ids.numel() != Nq:
+        raise ValueError(f"filter_ids needs one entry per query ({Nq})")
+    return filter_ids.contiguous()
+
+
 def _filter_words(filter, N):
     """the `filter` argument of query_filtered / bf_query_filtered as a contiguous int32 tensor of
     ceil(N / 32) words (CPU or CUDA): a boolean mask of length N is packed on the host, an
@@ -216,11 +276,13 @@ _MAX_TICKETS_PER_SLOT = 64   # query_async batches whose tensors are held per sl
 
 class QueryTicket:
     """Result of `GGNN.query_async`: `ids, dists = ticket` works as before; `query` keeps the
-    input alive; `done` is set by `synchronize()`."""
-    __slots__ = ("query", "ids", "dists", "slot", "done")
+    input alive (and `filter_ids` the filter ids of a batch that has some); `done` is set by
+    `synchronize()`."""
+    __slots__ = ("query", "ids", "dists", "slot", "done", "filter_ids")
 
-    def __init__(self, query, ids, dists, slot):
+    def __init__(self, query, ids, dists, slot, filter_ids=None):
         self.query, self.ids, self.dists, self.slot, self.done = query, ids, dists, slot, False
+        self.filter_ids = filter_ids
 
     def __iter__(self):
         return iter((self.ids, self.dists))
@@ -351,22 +413,80 @@ class GGNN:
                                      dists.data_ptr(), _lib.GPU if on_gpu else _lib.CPU))
         return ids, dists
 
+    @property
+    def _N(self):
+        return self._base_shape[0] if hasattr(self, "_base_shape") else 0
+
+    def set_filters(self, filters):
+        """Extension: make `filters` the resident filter table of this engine -- boolean masks
+        [F, N] (packed where they live) or packed bitsets [F, ceil(N / 32)] int32 / uint32
+        (`pack_filters`), CPU or GPU.  The engine copies the table and keeps it on every GPU it
+        drives, also across `build` / `load`; queries then name a row per query (`filter_ids=` of
+        `query_filtered_by`, `bf_query_filtered_by` and `query_async`).
+        `None` drops the table.  Waits for batches in flight."""
+        if filters is None:
+            self._check(lib().ggnn_set_filters(self._h, None, 0, 0, _lib.CPU, 0))
+            return
+        N = self._N
+        f = _filter_table(filters, N)
+        if f.shape[0] == 0:
+            raise ValueError("the filter table is empty (set_filters(None) drops it)")
+        floc, fdev = _loc(f)
+        self._check(lib().ggnn_set_filters(self._h, f.data_ptr(), f.shape[0], N, floc, fdev))
+
+    def update_filter(self, i, filter):
+        """Extension: replace row `i` of the filter table (`filter` as in `query_filtered`) on
+        every GPU.  Waits for batches in flight."""
+        N = self._N
+        f = _filter_words(filter, N)
+        floc, fdev = _loc(f)
+        self._check(lib().ggnn_update_filter(self._h, int(i), f.data_ptr(), N, floc, fdev))
+
+    @property
+    def num_filters(self):
+        """rows of the resident filter table (0: none)"""
+        n = C.c_uint32(0)
+        self._check(lib().ggnn_get_num_filters(self._h, C.byref(n)))
+        return int(n.value)
+
     def query_filtered(self, query, k_query, tau_query, max_iterations=400,
                        measure=DistanceMeasure.Euclidean, filter=None):
         """Extension: `query` among the base vectors `filter` allows -- a boolean mask of length N
         (numpy / torch) or an already packed bitset (`pack_filter`: int32 / uint32, ceil(N / 32)
         words, CPU or GPU), shared by all queries of the batch.  Denied vectors still route the
         search but are never reported; slots that could not be filled hold id -1 and distance
-        +inf.  `filter=None` is `query`."""
-        if filter is None:
+        +inf.  `filter=None` is `query`.  A filter per query: `query_filtered_by`."""
+        return self.query_filtered_by(query, k_query, tau_query, max_iterations, measure,
+                                      filter=filter)
+
+    def query_filtered_by(self, query, k_query, tau_query, max_iterations=400,
+                          measure=DistanceMeasure.Euclidean, filter_ids=None, filter=None):
+        """Extension: `query_filtered` with a filter per query.  `filter_ids`: one row of the
+        filter table (`set_filters`) per query -- 1-D int32 / int64 of length Nq, CPU or GPU; -1
+        searches unfiltered, and an id in device memory that names no row gives an empty result
+        (on the host it is an error).  `filter` (instead of `filter_ids`) is the one bitset of
+        `query_filtered`; giving both is a ValueError, giving neither is `query`."""
+        if filter is not None and filter_ids is not None:
+            raise ValueError("give either filter or filter_ids, not both")
+        if filter is None and filter_ids is None:
             return self.query(query, k_query, tau_query, max_iterations, measure)
         t = _as_tensor(query, what="query")
-        N = self._base_shape[0] if hasattr(self, "_base_shape") else 0
-        f = _filter_words(filter, N)
+        N = self._N
         loc, dev = _loc(t)
-        floc, fdev = _loc(f)
         on_gpu = self._return_results_on_gpu
         width = int(k_query) * (self._shards if on_gpu else 1)
+        if filter_ids is not None:
+            fi = _filter_ids(filter_ids, t.shape[0])
+            iloc, idev = _loc(fi)
+            ids, dists = self._out(t.shape[0], width, on_gpu,
+                                   self._result_device(t) if on_gpu else None)
+            self._check(lib().ggnn_query_filtered_by(
+                self._h, t.data_ptr(), t.shape[0], t.shape[1], _dtype_code(t), loc, dev,
+                int(k_query), float(tau_query), int(max_iterations), int(measure), ids.data_ptr(),
+                dists.data_ptr(), _lib.GPU if on_gpu else _lib.CPU, fi.data_ptr(), iloc, idev))
+            return ids, dists
+        f = _filter_words(filter, N)
+        floc, fdev = _loc(f)
         ids, dists = self._out(t.shape[0], width, on_gpu, self._result_device(t) if on_gpu else None)
         self._check(lib().ggnn_query_filtered(
             self._h, t.data_ptr(), t.shape[0], t.shape[1], _dtype_code(t), loc, dev, int(k_query),
@@ -377,16 +497,32 @@ class GGNN:
     def bf_query_filtered(self, query, k_gt=100, measure=DistanceMeasure.Euclidean, filter=None):
         """Extension: the exact `k_gt` nearest among the base vectors `filter` allows (see
         `query_filtered`); slots beyond the number of allowed vectors are (-1, +inf)."""
-        if filter is None:
+        return self.bf_query_filtered_by(query, k_gt, measure, filter=filter)
+
+    def bf_query_filtered_by(self, query, k_gt=100, measure=DistanceMeasure.Euclidean,
+                             filter_ids=None, filter=None):
+        """Extension: `bf_query_filtered` with a filter per query (`filter_ids`, `filter`: see
+        `query_filtered_by`)."""
+        if filter is not None and filter_ids is not None:
+            raise ValueError("give either filter or filter_ids, not both")
+        if filter is None and filter_ids is None:
             return self.bf_query(query, k_gt, measure)
         t = _as_tensor(query, what="query")
-        N = self._base_shape[0] if hasattr(self, "_base_shape") else 0
-        f = _filter_words(filter, N)
+        N = self._N
         loc, dev = _loc(t)
-        floc, fdev = _loc(f)
         on_gpu = self._return_results_on_gpu
         ids, dists = self._out(t.shape[0], int(k_gt), on_gpu,
                                self._result_device(t) if on_gpu else None)
+        if filter_ids is not None:
+            fi = _filter_ids(filter_ids, t.shape[0])
+            iloc, idev = _loc(fi)
+            self._check(lib().ggnn_bf_query_filtered_by(
+                self._h, t.data_ptr(), t.shape[0], t.shape[1], _dtype_code(t), loc, dev, int(k_gt),
+                int(measure), ids.data_ptr(), dists.data_ptr(), _lib.GPU if on_gpu else _lib.CPU,
+                fi.data_ptr(), iloc, idev))
+            return ids, dists
+        f = _filter_words(filter, N)
+        floc, fdev = _loc(f)
         self._check(lib().ggnn_bf_query_filtered(
             self._h, t.data_ptr(), t.shape[0], t.shape[1], _dtype_code(t), loc, dev, int(k_gt),
             int(measure), ids.data_ptr(), dists.data_ptr(), _lib.GPU if on_gpu else _lib.CPU,
@@ -394,7 +530,7 @@ class GGNN:
         return ids, dists
 
     def query_async(self, query, k_query, tau_query, max_iterations=400,
-                    measure=DistanceMeasure.Euclidean, slot=0):
+                    measure=DistanceMeasure.Euclidean, slot=0, filter_ids=None):
         """Extension for serving: enqueue a batch and return a `QueryTicket` (unpacks like the
         `(ids, dists)` pair) whose GPU tensors are valid after `synchronize()`.  Batches with
         different `slot`s overlap on the device (one GPU, query on that GPU); the result has the
@@ -406,13 +542,23 @@ class GGNN:
         the caller does with its own references -- a temporary passed as `query`, or a
         rebound loop variable, cannot be recycled under a running kernel.  At most
         `_MAX_TICKETS_PER_SLOT` batches are held per slot: enqueueing one more first synchronises
-        that slot and releases them."""
+        that slot and releases them.
+
+        `filter_ids`: one row of the filter table (`set_filters`) per query, as in
+        `query_filtered_by`; the ids live where the query lives (they are moved there otherwise) and
+        are kept alive with it."""
         t = _as_tensor(query, what="query")
+        fi = None if filter_ids is None else _filter_ids(filter_ids, t.shape[0])
         if self._num_gpus > 1 or _lib.get_hook("EXCHANGE") == 1:
             # several GPUs (or the forced RCCL path of the tests): merged [Nq, k] results; host-side tensors are page-locked so that the
             # engine's copies stay asynchronous
             if not t.is_cuda and not t.is_pinned():
                 t = t.pin_memory()
+            if fi is not None:
+                # the ids follow the query's memory rule: its GPU, or page-locked host memory
+                fi = fi.to(t.device) if t.is_cuda else (fi.cpu() if fi.is_cuda else fi)
+                if not fi.is_cuda and not fi.is_pinned():
+                    fi = fi.pin_memory()
             dev = t.device.index if t.is_cuda else -1
             if t.is_cuda:
                 ids, dists = self._out(t.shape[0], int(k_query), True, t.device)
@@ -424,12 +570,22 @@ class GGNN:
             if not t.is_cuda:
                 raise RuntimeError("query_async needs the query on the GPU")
             loc, dev = _loc(t)
+            if fi is not None:
+                fi = fi.to(t.device)
             ids, dists = self._out(t.shape[0], int(k_query) * self._shards, True, t.device)
-        self._check(lib().ggnn_query_async(self._h, t.data_ptr(), t.shape[0], t.shape[1],
-                                           _dtype_code(t), dev, int(k_query), float(tau_query),
-                                           int(max_iterations), int(measure), ids.data_ptr(),
-                                           dists.data_ptr(), int(slot)))
-        ticket = QueryTicket(t, ids, dists, int(slot))
+        if fi is not None:
+            if fi.is_cuda:
+                torch.cuda.current_stream(fi.device).synchronize()
+            self._check(lib().ggnn_query_async_filtered_by(
+                self._h, t.data_ptr(), t.shape[0], t.shape[1], _dtype_code(t), dev, int(k_query),
+                float(tau_query), int(max_iterations), int(measure), ids.data_ptr(),
+                dists.data_ptr(), int(slot), fi.data_ptr()))
+        else:
+            self._check(lib().ggnn_query_async(self._h, t.data_ptr(), t.shape[0], t.shape[1],
+                                               _dtype_code(t), dev, int(k_query), float(tau_query),
+                                               int(max_iterations), int(measure), ids.data_ptr(),
+                                               dists.data_ptr(), int(slot)))
+        ticket = QueryTicket(t, ids, dists, int(slot), fi)
         held = self._inflight.setdefault(int(slot) % _ASYNC_SLOTS, [])
         if len(held) >= _MAX_TICKETS_PER_SLOT:
             # a serving loop that waits some other way (its own events, torch.cuda.synchronize)

@@ -33,14 +33,33 @@ struct BfArgs {
   uint32_t filter_bit_offset;
 };
 
+// Arguments of the FILT kernels: per-query filters make filter_bits a table and add the id array
+// (FilterTable, common.hpp).  A struct of its own: the unfiltered kernels keep their argument block.
+struct BfFilteredArgs : BfArgs {
+  FilterTable filter_table;
+};
+template <bool FILT>
+using BfArgsOf = std::conditional_t<FILT, BfFilteredArgs, BfArgs>;
+
+// FILT: the bitset of this (query, slice) wave -- the call's, or the table row that the filter id
+// of query n names (scalar, once per wave)
+template <bool FILT>
+GGNN_DEV const uint32_t* bf_wave_filter(const BfArgsOf<FILT>& a, uint32_t n)
+{
+  if constexpr (FILT)
+    return wave_filter_bits(a.filter_bits, a.filter_table, n);
+  else
+    return nullptr;
+}
+
 // FILT: this lane's word of the bitset for the 64 (or fewer) rows of a batch starting at i0 -- one
 // coalesced load per batch, issued in front of the rows -- and the verdict for row i0 + lane
 template <bool FILT>
-GGNN_DEV uint32_t bf_filter_word(const BfArgs& a, uint32_t i0, uint32_t end)
+GGNN_DEV uint32_t bf_filter_word(const BfArgs& a, const uint32_t* bits, uint32_t i0, uint32_t end)
 {
   if constexpr (FILT) {
     const uint32_t row = i0 + threadIdx.x;
-    return row < end ? a.filter_bits[(row + a.filter_bit_offset) >> 5] : 0u;
+    return row < end ? bits[(row + a.filter_bit_offset) >> 5] : 0u;
   }
   return 0u;
 }
@@ -53,7 +72,7 @@ GGNN_DEV bool bf_row_allowed(const BfArgs& a, uint32_t word, uint32_t i0)
 }
 
 template <typename BaseT, int LPR, int NCH, int R, int MODE, bool FILT = false>
-__global__ void __launch_bounds__(kWave) bf_query_kernel(const BfArgs a)
+__global__ void __launch_bounds__(kWave) bf_query_kernel(const BfArgsOf<FILT> a)
 {
   constexpr int ROWS = kWave / LPR;
   constexpr int STEPS = StepsOf<LPR, NCH>::value;
@@ -90,8 +109,9 @@ __global__ void __launch_bounds__(kWave) bf_query_kernel(const BfArgs a)
 
   const uint32_t begin = slice * a.rows_per_slice;
   const uint32_t end = min(a.N_base, begin + a.rows_per_slice);
+  const uint32_t* fbits = bf_wave_filter<FILT>(a, n);
   for (uint32_t i0 = begin; i0 < end; i0 += ROWS * STEPS) {
-    const uint32_t fword = bf_filter_word<FILT>(a, i0, end);
+    const uint32_t fword = bf_filter_word<FILT>(a, fbits, i0, end);
     Chunk v[STEPS][NCH];
 #pragma unroll
     for (int s = 0; s < STEPS; ++s) {
@@ -145,7 +165,7 @@ __global__ void __launch_bounds__(kWave) bf_query_kernel(const BfArgs a)
 // k > 256: the K-best list lives in LDS (dists [K] | ids [K]); stable insertion by a wave-wide
 // shift, rare after the first few thousand rows.
 template <typename BaseT, int LPR, int NCH, int MODE, bool FILT = false>
-__global__ void __launch_bounds__(kWave) bf_query_lds_kernel(const BfArgs a)
+__global__ void __launch_bounds__(kWave) bf_query_lds_kernel(const BfArgsOf<FILT> a)
 {
   constexpr int ROWS = kWave / LPR;
   constexpr int STEPS = StepsOf<LPR, NCH>::value;
@@ -179,8 +199,9 @@ __global__ void __launch_bounds__(kWave) bf_query_lds_kernel(const BfArgs a)
 
   const uint32_t begin = slice * a.rows_per_slice;
   const uint32_t end = min(a.N_base, begin + a.rows_per_slice);
+  const uint32_t* fbits = bf_wave_filter<FILT>(a, n);
   for (uint32_t i0 = begin; i0 < end; i0 += ROWS * STEPS) {
-    const uint32_t fword = bf_filter_word<FILT>(a, i0, end);
+    const uint32_t fword = bf_filter_word<FILT>(a, fbits, i0, end);
     Chunk v[STEPS][NCH];
 #pragma unroll
     for (int s = 0; s < STEPS; ++s) {
@@ -244,10 +265,11 @@ __global__ void __launch_bounds__(kWave) bf_query_lds_kernel(const BfArgs a)
 }
 
 template <typename BaseT, int LPR, int NCH, int MODE>
-static void launch_bf_r(const BfArgs& args, hipStream_t stream)
+static void launch_bf_r(const BfFilteredArgs& fargs, hipStream_t stream)
 {
-  const dim3 grid = grid_for(static_cast<uint64_t>(args.Nq) * args.slices);
-  if (args.filter_bits) {
+  const dim3 grid = grid_for(static_cast<uint64_t>(fargs.Nq) * fargs.slices);
+  if (fargs.filter_bits) {
+    const BfFilteredArgs& args = fargs;
     if (args.K <= 64)
       hipLaunchKernelGGL((bf_query_kernel<BaseT, LPR, NCH, 1, MODE, true>), grid, dim3(kWave), 0,
                          stream, args);
@@ -262,6 +284,7 @@ static void launch_bf_r(const BfArgs& args, hipStream_t stream)
                          (2 * args.K + 64) * sizeof(int), stream, args);
     return;
   }
+  const BfArgs& args = fargs;
   if (args.K <= 64)
     hipLaunchKernelGGL((bf_query_kernel<BaseT, LPR, NCH, 1, MODE>), grid, dim3(kWave), 0, stream,
                        args);
@@ -276,6 +299,41 @@ static void launch_bf_r(const BfArgs& args, hipStream_t stream)
                        (2 * args.K + 64) * sizeof(int), stream, args);
 }
 
+// [F x N] byte masks -> [F x ceil(N / 32)] bitset words: one wave per 64 rows of one filter, one
+// ballot, lanes 0 and 1 store its halves.  Rows at and above N vote 0: the padding bits are zero.
+__global__ void __launch_bounds__(kWave) pack_filters_kernel(const uint8_t* masks, uint32_t F,
+                                                             uint64_t N, uint32_t chunks,
+                                                             uint32_t words, uint32_t* out)
+{
+  const uint64_t b = static_cast<uint64_t>(blockIdx.y) * gridDim.x + blockIdx.x;
+  if (b >= static_cast<uint64_t>(F) * chunks)
+    return;
+  const uint32_t f = static_cast<uint32_t>(b / chunks);
+  const uint32_t c = static_cast<uint32_t>(b % chunks);
+  const uint64_t row = static_cast<uint64_t>(c) * kWave + threadIdx.x;
+  const bool allowed = row < N && masks[static_cast<uint64_t>(f) * N + row] != 0;
+  const unsigned long long m = __ballot(allowed);
+  const uint32_t w = 2u * c + threadIdx.x;
+  if (threadIdx.x < 2 && w < words)
+    out[static_cast<size_t>(f) * words + w] =
+        static_cast<uint32_t>(threadIdx.x == 0 ? m : m >> 32);
+}
+
+void launch_pack_filters(const uint8_t* masks, uint32_t F, uint64_t N, uint32_t* words_out,
+                         hipStream_t stream)
+{
+  if (!F || !N)
+    return;
+  GGNN_REQUIRE(masks != nullptr && words_out != nullptr, GGNN_INVALID_ARGUMENT,
+               "pack_filters: null pointer");
+  GGNN_REQUIRE(N <= 0xffffffffull, GGNN_INVALID_ARGUMENT, "pack_filters: too many rows");
+  const uint32_t chunks = static_cast<uint32_t>((N + kWave - 1) / kWave);
+  const uint32_t words = static_cast<uint32_t>((N + 31) / 32);
+  hipLaunchKernelGGL(pack_filters_kernel, grid_for(static_cast<uint64_t>(F) * chunks), dim3(kWave),
+                     0, stream, masks, F, N, chunks, words, words_out);
+  GGNN_HIP_CHECK(hipGetLastError());
+}
+
 bool bf_mfma_supported(const BfLaunch& a);
 void launch_bf_query_mfma(const BfLaunch& a, hipStream_t stream);
 
@@ -285,7 +343,7 @@ static void launch_bf_scan(const BfLaunch& a, uint32_t slices, uint32_t rows_per
                            const uint32_t* qlist, const uint32_t* qcount, int32_t* tmp_ids,
                            float* tmp_dists, hipStream_t stream)
 {
-  BfArgs args{};
+  BfFilteredArgs args{};
   args.base = a.base;
   args.query = a.query;
   args.D = a.D;
@@ -298,6 +356,7 @@ static void launch_bf_scan(const BfLaunch& a, uint32_t slices, uint32_t rows_per
   args.qcount = qcount;
   args.filter_bits = a.filter_bits;
   args.filter_bit_offset = a.filter_bit_offset;
+  args.filter_table = a.filter_table;
   args.ids = slices > 1 ? tmp_ids : a.ids;
   args.dists = slices > 1 ? tmp_dists : a.dists;
 
@@ -381,7 +440,19 @@ void launch_bf_query(const BfLaunch& a, hipStream_t stream)
     GGNN_HIP_CHECK(hipMallocAsync(reinterpret_cast<void**>(&tmp_ids), n * sizeof(int32_t), stream));
     GGNN_HIP_CHECK(hipMallocAsync(reinterpret_cast<void**>(&tmp_dists), n * sizeof(float), stream));
   }
-  launch_bf_scan(a, slices, rows_per_slice, nullptr, nullptr, tmp_ids, tmp_dists, stream);
+  if (a.filter_bits && a.filter_table.ids) {
+    GGNN_REQUIRE(a.filter_table.words != 0 && a.filter_table.num_filters != 0,
+                 GGNN_INVALID_ARGUMENT, "filter ids need a filter table");
+    // the all-ones / all-zero rows of a launch that brings none (operator seam)
+    BfLaunch b = a;
+    uint32_t* consts = filter_consts_scratch(a.filter_table, stream);
+    if (consts)
+      b.filter_table.consts = consts;
+    launch_bf_scan(b, slices, rows_per_slice, nullptr, nullptr, tmp_ids, tmp_dists, stream);
+    scratch_free(consts, stream);
+  }
+  else
+    launch_bf_scan(a, slices, rows_per_slice, nullptr, nullptr, tmp_ids, tmp_dists, stream);
   if (slices > 1) {
     GGNN_HIP_CHECK(hipFreeAsync(tmp_ids, stream));
     GGNN_HIP_CHECK(hipFreeAsync(tmp_dists, stream));

@@ -126,6 +126,21 @@ extern int g_log_level;
   } while (0)
 
 // ---- host-side launchers implemented in the .hip files ---------------------------------------
+// Per-query filters: filter_bits of a launch is a table of [num_filters x words] bitsets and
+// query n searches under row ids[n] (-1: unfiltered, any other value outside [0, num_filters): empty
+// result).  ids == nullptr is the per-call form: filter_bits is ONE bitset shared by every query.
+// consts: [2 x words] device words, all ones then all zeros -- what the ids -1 / out of range read;
+// when it is null the launcher makes the two rows in stream-ordered scratch of the launch.
+struct FilterTable {
+  const int32_t* ids{nullptr};      // [Nq] (device) or null
+  const uint32_t* consts{nullptr};  // [2 x words]
+  uint32_t words{0};                // words per filter: ceil(bits / 32) over the global ids
+  uint32_t num_filters{0};
+};
+// the two constant rows for a launch that was given none (null if ids is null); free with
+// scratch_free(p, stream) after the launch
+uint32_t* filter_consts_scratch(const FilterTable& t, hipStream_t stream);
+
 struct QueryLaunch {
   const void* base;
   const void* query;
@@ -154,6 +169,8 @@ struct QueryLaunch {
   // search reports allowed ids only (query_filtered.hip)
   const uint32_t* filter_bits{nullptr};
   uint32_t filter_bit_offset{0};
+  // per-query filters: filter_bits is then a table (see FilterTable)
+  FilterTable filter_table{};
 };
 void launch_query(const QueryLaunch& a, hipStream_t stream);
 
@@ -200,6 +217,8 @@ struct BfLaunch {
   // the allowed rows, on the scan kernels (bf_query.hip)
   const uint32_t* filter_bits{nullptr};
   uint32_t filter_bit_offset{0};
+  // per-query filters: filter_bits is then a table (see FilterTable)
+  FilterTable filter_table{};
 };
 void launch_bf_query(const BfLaunch& a, hipStream_t stream);
 
@@ -277,6 +296,9 @@ void launch_sym_buffer_merge(uint32_t KBuild, uint32_t N_layer, int32_t* sym_buf
 constexpr uint32_t kStatsBlocks = 1024;
 void launch_nn1_stats(const float* nn1, uint32_t N, float* scratch, float* out,
                       hipStream_t stream);
+// [F x N] byte masks (non-zero = allowed) -> [F x ceil(N / 32)] bitset words, padding bits zero
+void launch_pack_filters(const uint8_t* masks, uint32_t F, uint64_t N, uint32_t* words,
+                         hipStream_t stream);
 void launch_sort_shard_results(uint32_t Nq, uint32_t row_len, int32_t* ids, float* dists,
                                hipStream_t stream);
 void launch_merge_results(uint32_t Nq, uint32_t k, uint32_t num_parts, uint32_t stride,

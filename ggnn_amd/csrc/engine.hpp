@@ -314,6 +314,14 @@ struct DeviceCtx {
   // this GPU (the caller's own memory or filter_stage); null otherwise
   DeviceBuffer filter_stage;
   const uint32_t* filter_bits{nullptr};
+  // per-query filters: this GPU's copy of the handle's filter table, [(F + 2) x words] -- the F
+  // rows, then the all-ones and the all-zero row that the ids -1 / out of range read -- current when
+  // filter_table_epoch equals the handle's; and the id array of the blocking call in progress
+  // (the caller's own device memory or filter_ids_stage; with it, filter_bits is the table)
+  DeviceBuffer filter_table;
+  uint64_t filter_table_epoch{0};
+  DeviceBuffer filter_ids_stage;
+  const int32_t* filter_ids{nullptr};
   std::unique_ptr<SwapState> swap;  // out-of-core shards (null: every shard resident)
   // Result staging of query() / query_async(): grown on demand, kept between calls.  One set per
   // lane: lanes [0, kShardStreams) belong to the asynchronous slots (their streams), lane
@@ -325,6 +333,7 @@ struct DeviceCtx {
   static constexpr int kBlockingLane = kShardStreams;
   struct ExchangeBufs {
     DeviceBuffer q_stage;  // the query set on this GPU when it has to be copied (async lanes)
+    DeviceBuffer f_stage;  // ... and its filter ids (query_async with filter ids)
     DeviceBuffer r_pack;   // this GPU's sorted rows, ids then distances
     DeviceBuffer g_pack;   // r_pack of all GPUs after the exchange, [G][2 * Nq * row]
     DeviceBuffer m_pack;   // merged results, [ids: Nq x K][dists: Nq x K] (this GPU's slice filled)
@@ -366,8 +375,12 @@ struct DeviceCtx {
     o.ev_a = o.ev_b = o.ev_ready = nullptr;
     base_copy = std::move(o.base_copy);
     bf_rescanned = std::move(o.bf_rescanned);
+    filter_table = std::move(o.filter_table);
+    filter_table_epoch = o.filter_table_epoch;
+    o.filter_table_epoch = 0;
     for (int i = 0; i <= kShardStreams; ++i) {
       xb[i].q_stage = std::move(o.xb[i].q_stage);
+      xb[i].f_stage = std::move(o.xb[i].f_stage);
       xb[i].r_pack = std::move(o.xb[i].r_pack);
       xb[i].g_pack = std::move(o.xb[i].g_pack);
       xb[i].m_pack = std::move(o.xb[i].m_pack);
@@ -478,6 +491,19 @@ struct ggnn_handle {
     ggnn_location loc{GGNN_CPU};
     int gpu{0};
   } active_filter;
+  // per-query filters.  The table as ggnn_set_filters copied it, [num_filters x filter_words]
+  // words on the host (placed on a GPU when a context exists: place_filter_table), and the id array
+  // of the blocking *_filtered_by call in progress as the caller gave it (null: none)
+  std::vector<uint32_t> filter_table_host;
+  uint32_t num_filters{0};
+  uint32_t filter_words{0};
+  uint64_t filter_epoch{0};  // counts ggnn_set_filters calls: a context with another value is stale
+  struct FilterIdSpec {
+    const int32_t* ids{nullptr};
+    uint64_t count{0};
+    ggnn_location loc{GGNN_CPU};
+    int gpu{0};
+  } active_filter_ids;
 
   std::string last_error;
 
@@ -596,8 +622,30 @@ struct ggnn_handle {
                          int filter_gpu);
   void begin_filter(const uint32_t* bits, uint64_t n_bits, ggnn_location loc, int gpu);
   void end_filter();
-  // the active filter on ctx's GPU, copied on ctx.stream unless it already lives there (null: none)
+  // the active filter on ctx's GPU, copied on ctx.stream unless it already lives there (null: none);
+  // with filter ids active: the resident table, and ctx.filter_ids is staged beside it
   const uint32_t* stage_filter(DeviceCtx& ctx);
+
+  // per-query filters (engine_query.cpp)
+  void set_filters(const uint32_t* bits, uint32_t F, uint64_t n_bits, ggnn_location loc, int gpu);
+  void update_filter(uint32_t index, const uint32_t* bits, uint64_t n_bits, ggnn_location loc,
+                     int gpu);
+  void drop_filters();
+  // ctx's copy of the table, placed now if it is missing or stale (synchronous; ctx is active)
+  const uint32_t* place_filter_table(DeviceCtx& ctx);
+  void place_filter_tables();  // ... on every context there is
+  // filter_table / consts / words / num_filters of a launch on ctx with the id array `ids`
+  FilterTable launch_filter_table(const DeviceCtx& ctx, const int32_t* ids) const;
+  void begin_filter_ids(const int32_t* ids, uint64_t Nq, ggnn_location loc, int gpu);
+  void query_filtered_by(const void* q, uint64_t Nq, uint32_t D, ggnn_dtype dtype,
+                         ggnn_location loc, int q_gpu, uint32_t k_query, float tau_query,
+                         uint32_t max_iterations, ggnn_measure measure, int32_t* ids_out,
+                         float* dists_out, ggnn_location out_loc, const int32_t* filter_ids,
+                         ggnn_location ids_loc, int ids_gpu);
+  void bf_query_filtered_by(const void* q, uint64_t Nq, uint32_t D, ggnn_dtype dtype,
+                            ggnn_location loc, int q_gpu, uint32_t k_gt, ggnn_measure measure,
+                            int32_t* ids_out, float* dists_out, ggnn_location out_loc,
+                            const int32_t* filter_ids, ggnn_location ids_loc, int ids_gpu);
 
   void query_split(const void* q, uint32_t nq, uint32_t D, ggnn_dtype dtype, ggnn_location loc,
                    int q_gpu, uint32_t k_query, float tau_query, uint32_t max_iterations,
@@ -628,11 +676,14 @@ struct ggnn_handle {
   void query_async(const void* d_query, uint64_t Nq, uint32_t D, ggnn_dtype dtype,
                    ggnn_location loc, int q_gpu, uint32_t k_query, float tau_query,
                    uint32_t max_iterations, ggnn_measure measure, int32_t* d_ids, float* d_dists,
-                   uint32_t slot);
+                   uint32_t slot, const int32_t* filter_ids = nullptr);
 
+  // filter_bits / filter_ids: the bitset (ids null) or the filter table and the ids of these nq
+  // queries, on ctx's GPU; both null: unfiltered
   void enqueue_local_search(DeviceCtx& ctx, int lane, const void* d_query, uint32_t nq,
                             uint32_t k_query, float tau_query, uint32_t max_iterations,
-                            ggnn_measure measure, int32_t* d_ids, float* d_dists);
+                            ggnn_measure measure, int32_t* d_ids, float* d_dists,
+                            const uint32_t* filter_bits, const int32_t* filter_ids);
   void synchronize_slot(uint32_t slot);
   void synchronize();
 

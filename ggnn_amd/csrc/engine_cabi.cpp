@@ -44,6 +44,24 @@ ggnn_status guarded(ggnn_t* h, F&& f)
 #define GGNN_NEED_HANDLE(h) \
   if (!(h))                 \
   return GGNN_INVALID_ARGUMENT
+
+// the table arguments of the *_filtered_by seam calls as a launch sees them
+FilterTable seam_filter_table(const uint32_t* filter_table, uint32_t num_filters, uint64_t n_bits,
+                              const int32_t* filter_ids, uint32_t filter_bit_offset,
+                              uint32_t N_base)
+{
+  GGNN_REQUIRE(filter_table != nullptr && num_filters > 0, GGNN_INVALID_ARGUMENT,
+               "the filter table is null or empty");
+  GGNN_REQUIRE(filter_ids != nullptr, GGNN_INVALID_ARGUMENT, "the filter id array is null");
+  GGNN_REQUIRE(n_bits >= static_cast<uint64_t>(filter_bit_offset) + N_base &&
+                   n_bits <= 0xffffffffull,
+               GGNN_INVALID_ARGUMENT, "a filter needs filter_bit_offset + N_base bits");
+  FilterTable t{};
+  t.ids = filter_ids;
+  t.words = static_cast<uint32_t>((n_bits + 31) / 32);
+  t.num_filters = num_filters;
+  return t;
+}
 }  // namespace
 
 extern "C" {
@@ -244,6 +262,8 @@ ggnn_status ggnn_set_base(ggnn_t* h, const void* data, uint64_t N, uint32_t D, g
     const size_t bytes = N * D * dtype_size(dtype);
     h->drop_host_copy();
     h->base_dev_copy.release();
+    if (h->num_filters)
+      h->drop_filters();  // a filter table is over the ids of the base it was set for
     h->devs.clear();  // a base staged for an earlier bf_query() is stale now
     h->base_src = data;
     h->base_loc = location;
@@ -385,6 +405,75 @@ ggnn_status ggnn_bf_query_filtered(ggnn_t* h, const void* query, uint64_t Nq, ui
   return guarded(h, [&] {
     h->bf_query_filtered(query, Nq, D, dtype, location, gpu_id, k_gt, measure, ids_out, dists_out,
                          out_location, allowed_bits, n_bits, filter_location, filter_gpu_id);
+  });
+}
+
+ggnn_status ggnn_set_filters(ggnn_t* h, const uint32_t* bits, uint32_t num_filters,
+                             uint64_t n_bits, ggnn_location location, int gpu_id)
+{
+  GGNN_NEED_HANDLE(h);
+  return guarded(h, [&] { h->set_filters(bits, num_filters, n_bits, location, gpu_id); });
+}
+
+ggnn_status ggnn_update_filter(ggnn_t* h, uint32_t index, const uint32_t* bits, uint64_t n_bits,
+                               ggnn_location location, int gpu_id)
+{
+  GGNN_NEED_HANDLE(h);
+  return guarded(h, [&] { h->update_filter(index, bits, n_bits, location, gpu_id); });
+}
+
+ggnn_status ggnn_get_num_filters(const ggnn_t* h, uint32_t* num_filters)
+{
+  GGNN_NEED_HANDLE(h);
+  if (!num_filters)
+    return GGNN_INVALID_ARGUMENT;
+  *num_filters = h->num_filters;
+  return GGNN_OK;
+}
+
+ggnn_status ggnn_query_filtered_by(ggnn_t* h, const void* query, uint64_t Nq, uint32_t D,
+                                   ggnn_dtype dtype, ggnn_location location, int gpu_id,
+                                   uint32_t k_query, float tau_query, uint32_t max_iterations,
+                                   ggnn_measure measure, int32_t* ids_out, float* dists_out,
+                                   ggnn_location out_location, const int32_t* filter_ids,
+                                   ggnn_location ids_location, int ids_gpu_id)
+{
+  GGNN_NEED_HANDLE(h);
+  return guarded(h, [&] {
+    h->query_filtered_by(query, Nq, D, dtype, location, gpu_id, k_query, tau_query,
+                         max_iterations, measure, ids_out, dists_out, out_location, filter_ids,
+                         ids_location, ids_gpu_id);
+  });
+}
+
+ggnn_status ggnn_bf_query_filtered_by(ggnn_t* h, const void* query, uint64_t Nq, uint32_t D,
+                                      ggnn_dtype dtype, ggnn_location location, int gpu_id,
+                                      uint32_t k_gt, ggnn_measure measure, int32_t* ids_out,
+                                      float* dists_out, ggnn_location out_location,
+                                      const int32_t* filter_ids, ggnn_location ids_location,
+                                      int ids_gpu_id)
+{
+  GGNN_NEED_HANDLE(h);
+  return guarded(h, [&] {
+    h->bf_query_filtered_by(query, Nq, D, dtype, location, gpu_id, k_gt, measure, ids_out,
+                            dists_out, out_location, filter_ids, ids_location, ids_gpu_id);
+  });
+}
+
+ggnn_status ggnn_query_async_filtered_by(ggnn_t* h, const void* query, uint64_t Nq, uint32_t D,
+                                         ggnn_dtype dtype, int gpu_id, uint32_t k_query,
+                                         float tau_query, uint32_t max_iterations,
+                                         ggnn_measure measure, int32_t* ids_out, float* dists_out,
+                                         uint32_t slot, const int32_t* filter_ids)
+{
+  GGNN_NEED_HANDLE(h);
+  return guarded(h, [&] {
+    GGNN_REQUIRE(h->num_filters != 0, GGNN_INVALID_STATE,
+                 "There is no filter table the filter ids could refer to (ggnn_set_filters).");
+    GGNN_REQUIRE(!Nq || filter_ids != nullptr, GGNN_INVALID_ARGUMENT,
+                 "the filter id array is null");
+    h->query_async(query, Nq, D, dtype, gpu_id < 0 ? GGNN_CPU : GGNN_GPU, gpu_id, k_query,
+                   tau_query, max_iterations, measure, ids_out, dists_out, slot, filter_ids);
   });
 }
 
@@ -613,6 +702,68 @@ ggnn_status ggnn_op_bf_query_filtered(const void* base, ggnn_dtype dtype, uint32
     b.filter_bits = filter_bits;
     b.filter_bit_offset = filter_bit_offset;
     launch_bf_query(b, static_cast<hipStream_t>(stream));
+  });
+}
+
+ggnn_status ggnn_op_query_filtered_by(const void* base, ggnn_dtype dtype, uint32_t N_base,
+                                      uint32_t D, const uint8_t* codes, const float* params,
+                                      const void* query, uint32_t Nq, const int32_t* graph0,
+                                      uint32_t KBuild, const int32_t* start, uint32_t num_start,
+                                      const float* nn1_stats, uint32_t k_query, float tau_query,
+                                      uint32_t max_iterations, ggnn_measure measure,
+                                      uint32_t shards_per_gpu, uint32_t on_gpu_shard, int32_t* ids,
+                                      float* dists, uint32_t* n_dist, uint32_t* n_pop,
+                                      uint32_t* n_rows, const uint32_t* filter_table,
+                                      uint32_t num_filters, uint64_t n_bits,
+                                      const int32_t* filter_ids, uint32_t filter_bit_offset,
+                                      void* stream)
+{
+  return guarded(nullptr, [&] {
+    GGNN_REQUIRE(!codes == !params, GGNN_INVALID_ARGUMENT,
+                 "pre-screen codes and params go together");
+    GGNN_REQUIRE(!codes || dtype == GGNN_F32, GGNN_INVALID_ARGUMENT,
+                 "the pre-screen needs a float32 base");
+    QueryLaunch q{base,      query,          dtype,    N_base,         D,         Nq,
+                  graph0,    KBuild,         start,    num_start,      nn1_stats, k_query,
+                  tau_query, max_iterations, measure,  shards_per_gpu, on_gpu_shard, ids,
+                  dists,     n_dist,         n_pop};
+    if (codes) {
+      q.ps_codes = codes;
+      q.ps_params = params;
+      q.ps_Dc = prescreen_code_dim(D);
+    }
+    q.n_rows = n_rows;
+    q.filter_table =
+        seam_filter_table(filter_table, num_filters, n_bits, filter_ids, filter_bit_offset, N_base);
+    q.filter_bits = filter_table;
+    q.filter_bit_offset = filter_bit_offset;
+    launch_query(q, static_cast<hipStream_t>(stream));
+  });
+}
+
+ggnn_status ggnn_op_bf_query_filtered_by(const void* base, ggnn_dtype dtype, uint32_t N_base,
+                                         uint32_t D, const void* query, uint32_t Nq,
+                                         uint32_t k_query, ggnn_measure measure, int32_t* ids,
+                                         float* dists, const uint32_t* filter_table,
+                                         uint32_t num_filters, uint64_t n_bits,
+                                         const int32_t* filter_ids, uint32_t filter_bit_offset,
+                                         void* stream)
+{
+  return guarded(nullptr, [&] {
+    BfLaunch b{base, query, dtype, N_base, D, Nq, k_query, measure, ids, dists};
+    b.filter_table =
+        seam_filter_table(filter_table, num_filters, n_bits, filter_ids, filter_bit_offset, N_base);
+    b.filter_bits = filter_table;
+    b.filter_bit_offset = filter_bit_offset;
+    launch_bf_query(b, static_cast<hipStream_t>(stream));
+  });
+}
+
+ggnn_status ggnn_op_pack_filters(const uint8_t* masks, uint32_t num_filters, uint64_t N,
+                                 uint32_t* words, void* stream)
+{
+  return guarded(nullptr, [&] {
+    launch_pack_filters(masks, num_filters, N, words, static_cast<hipStream_t>(stream));
   });
 }
 

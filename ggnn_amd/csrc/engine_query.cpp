@@ -112,6 +112,7 @@ void ggnn_handle::query_device(DeviceCtx& ctx, const void* d_query, uint32_t nq,
     ql.n_rows = c_rows.as<uint32_t>();
     ql.filter_bits = ctx.filter_bits;
     ql.filter_bit_offset = sh.global_id * cfg.N;
+    ql.filter_table = launch_filter_table(ctx, ctx.filter_ids);
     if (overlap) {
       launch_query(ql, ctx.shard_stream[si % DeviceCtx::kShardStreams]);
       continue;
@@ -267,8 +268,10 @@ void ggnn_handle::query_split(const void* q, uint32_t nq, uint32_t D, ggnn_dtype
       int32_t* r = x.r_pack.as<int32_t>();
       const uint8_t* qh = static_cast<const uint8_t*>(staged[g].ptr) +
                           static_cast<size_t>(first[half]) * pad_D * es;
+      // (each half sees its own half of the filter ids)
       enqueue_local_search(ctx, lane, qh, count[half], k_query, tau_query, max_iterations,
-                           measure, r, reinterpret_cast<float*>(r + part));
+                           measure, r, reinterpret_cast<float*>(r + part), ctx.filter_bits,
+                           ctx.filter_ids ? ctx.filter_ids + first[half] : nullptr);
       GGNN_HIP_CHECK(hipEventRecord(ctx.shard_done[lane], st));
       GGNN_HIP_CHECK(hipStreamWaitEvent(ctx.stream, ctx.shard_done[lane], 0));
     }
@@ -331,10 +334,12 @@ void ggnn_handle::grow_lane(DeviceCtx& owner, int lane, DeviceBuffer& b, size_t 
 void ggnn_handle::query_async(const void* d_query, uint64_t Nq, uint32_t D, ggnn_dtype dtype,
                  ggnn_location loc, int q_gpu, uint32_t k_query, float tau_query,
                  uint32_t max_iterations, ggnn_measure measure, int32_t* d_ids, float* d_dists,
-                 uint32_t slot)
+                 uint32_t slot, const int32_t* filter_ids)
 {
   GGNN_REQUIRE(has_graph(), GGNN_INVALID_STATE, "There is no graph to query.");
   check_query(Nq, D, dtype, d_query);
+  GGNN_REQUIRE(!filter_ids || num_filters, GGNN_INVALID_STATE,
+               "There is no filter table the filter ids could refer to (ggnn_set_filters).");
   GGNN_REQUIRE(!Nq || (d_ids != nullptr && d_dists != nullptr), GGNN_INVALID_ARGUMENT,
                "result pointers are null");
   GGNN_REQUIRE(!swapping(), GGNN_UNSUPPORTED,
@@ -363,8 +368,10 @@ void ggnn_handle::query_async(const void* d_query, uint64_t Nq, uint32_t D, ggnn
     for (uint32_t si = 0; si < shards_per_gpu; ++si)
       (void)ensure_prescreen(ctx, si, measure);
     ctx.ensure_shard_streams();
+    // (filter ids: device memory on this GPU like the query, nothing is staged)
     enqueue_local_search(ctx, lane, d_query, nq, k_query, tau_query, max_iterations, measure,
-                         d_ids, d_dists);
+                         d_ids, d_dists, filter_ids ? place_filter_table(ctx) : nullptr,
+                         filter_ids);
     return;
   }
   GGNN_REQUIRE(pad_D == base_D, GGNN_UNSUPPORTED,
@@ -386,6 +393,16 @@ void ggnn_handle::query_async(const void* d_query, uint64_t Nq, uint32_t D, ggnn
       GGNN_HIP_CHECK(hipMemcpyAsync(x.q_stage.p, d_query, qbytes, hipMemcpyDefault, st));
       q_here = x.q_stage.p;
     }
+    // the filter ids follow the query's memory rule: used in place on their own GPU, else copied
+    // on the lane's stream
+    const int32_t* f_here = filter_ids;
+    if (filter_ids && !(loc == GGNN_GPU && q_gpu == ctx.device &&
+                        (reinterpret_cast<uintptr_t>(filter_ids) & 3u) == 0)) {
+      grow_lane(ctx, lane, x.f_stage, Nq * sizeof(int32_t));
+      GGNN_HIP_CHECK(hipMemcpyAsync(x.f_stage.p, filter_ids, Nq * sizeof(int32_t),
+                                    hipMemcpyDefault, st));
+      f_here = x.f_stage.as<int32_t>();
+    }
     // (copy exchange: the first GPU may still be copying this lane's previous rows)
 #ifndef GGNN_EXP_NO_CONSUMED_WAIT  // (test-the-test hook)
     if (&ctx != &devs[0] && devs[0].xb[lane].consumed)
@@ -394,7 +411,8 @@ void ggnn_handle::query_async(const void* d_query, uint64_t Nq, uint32_t D, ggnn
     grow_lane(ctx, lane, x.r_pack, 2 * part * 4);
     int32_t* r = x.r_pack.as<int32_t>();
     enqueue_local_search(ctx, lane, q_here, nq, k_query, tau_query, max_iterations, measure, r,
-                         reinterpret_cast<float*>(r + part));
+                         reinterpret_cast<float*>(r + part),
+                         filter_ids ? place_filter_table(ctx) : nullptr, f_here);
   }
   exchange(lane, nq, k_query, row, d_ids, d_dists, /*blocking=*/false);
 }
@@ -402,7 +420,8 @@ void ggnn_handle::query_async(const void* d_query, uint64_t Nq, uint32_t D, ggnn
 // the shards of one GPU on one lane's stream, nothing waits
 void ggnn_handle::enqueue_local_search(DeviceCtx& ctx, int lane, const void* d_query, uint32_t nq,
                           uint32_t k_query, float tau_query, uint32_t max_iterations,
-                          ggnn_measure measure, int32_t* d_ids, float* d_dists)
+                          ggnn_measure measure, int32_t* d_ids, float* d_dists,
+                          const uint32_t* filter_bits, const int32_t* filter_ids)
 {
   hipStream_t stream = ctx.lane_stream(lane);
   for (uint32_t si = 0; si < shards_per_gpu; ++si) {
@@ -416,8 +435,9 @@ void ggnn_handle::enqueue_local_search(DeviceCtx& ctx, int lane, const void* d_q
       ql.ps_params = sh.ps_params.as<float>();
       ql.ps_Dc = prescreen_code_dim(pad_D);
     }
-    ql.filter_bits = ctx.filter_bits;  // (null outside a filtered blocking call)
+    ql.filter_bits = filter_bits;
     ql.filter_bit_offset = sh.global_id * cfg.N;
+    ql.filter_table = launch_filter_table(ctx, filter_ids);
     launch_query(ql, stream);
   }
   if (shards_per_gpu > 1)
@@ -502,6 +522,7 @@ void ggnn_handle::bf_query(const void* q, uint64_t Nq, uint32_t D, ggnn_dtype dt
   BfLaunch bl{bf_base, sq.ptr, base_dtype, static_cast<uint32_t>(base_N), pad_D, nq, k_gt,
               measure,    d_ids,  d_dists,    ctx.bf_rescanned.as<uint32_t>()};
   bl.filter_bits = stage_filter(ctx);
+  bl.filter_table = launch_filter_table(ctx, ctx.filter_ids);
   EventTimer timer(ctx.stream, ctx.ev_a, ctx.ev_b);
   launch_bf_query(bl, ctx.stream);
   bf_ms = timer.stop();
@@ -534,12 +555,30 @@ void ggnn_handle::begin_filter(const uint32_t* bits, uint64_t n_bits, ggnn_locat
 void ggnn_handle::end_filter()
 {
   active_filter = FilterSpec{};
-  for (DeviceCtx& ctx : devs)
+  active_filter_ids = FilterIdSpec{};
+  for (DeviceCtx& ctx : devs) {
     ctx.filter_bits = nullptr;
+    ctx.filter_ids = nullptr;
+  }
 }
 
 const uint32_t* ggnn_handle::stage_filter(DeviceCtx& ctx)
 {
+  if (const FilterIdSpec& fi = active_filter_ids; fi.ids) {
+    // per-query filters: the resident table, and the id array beside the query
+    const uint32_t* table = place_filter_table(ctx);
+    if (fi.loc == GGNN_GPU && fi.gpu == ctx.device && (reinterpret_cast<uintptr_t>(fi.ids) & 3u) == 0)
+      ctx.filter_ids = fi.ids;
+    else {
+      const size_t bytes = fi.count * sizeof(int32_t);
+      DeviceCtx::grow(ctx.filter_ids_stage, bytes);
+      GGNN_HIP_CHECK(hipMemcpyAsync(ctx.filter_ids_stage.p, fi.ids, bytes,
+                                    fi.loc == GGNN_GPU ? hipMemcpyDefault : hipMemcpyHostToDevice,
+                                    ctx.stream));
+      ctx.filter_ids = ctx.filter_ids_stage.as<int32_t>();
+    }
+    return table;
+  }
   const FilterSpec& f = active_filter;
   if (!f.bits)
     return nullptr;
@@ -579,6 +618,167 @@ void ggnn_handle::bf_query_filtered(const void* q, uint64_t Nq, uint32_t D, ggnn
                                     ggnn_location filter_loc, int filter_gpu)
 {
   begin_filter(bits, n_bits, filter_loc, filter_gpu);
+  FilterScope scope{*this};
+  bf_query(q, Nq, D, dtype, loc, q_gpu, k_gt, measure, ids_out, dists_out, out_loc);
+}
+
+// ---- per-query filters: resident filter table, one filter id per query ------------------------
+void ggnn_handle::drop_filters()
+{
+  synchronize();
+  DeviceRestoreGuard keep;
+  filter_table_host.clear();
+  filter_table_host.shrink_to_fit();
+  num_filters = 0;
+  filter_words = 0;
+  ++filter_epoch;
+  for (DeviceCtx& ctx : devs) {
+    (void)hipSetDevice(ctx.device);
+    ctx.filter_table.release();
+    ctx.filter_table_epoch = 0;
+  }
+}
+
+void ggnn_handle::set_filters(const uint32_t* bits, uint32_t F, uint64_t n_bits, ggnn_location loc,
+                              int gpu)
+{
+  if (F == 0) {
+    drop_filters();
+    return;
+  }
+  GGNN_REQUIRE(bits != nullptr, GGNN_INVALID_ARGUMENT, "the filter table is null");
+  GGNN_REQUIRE(!base_set || n_bits == base_N, GGNN_INVALID_ARGUMENT,
+               "a filter needs one bit per base vector (n_bits must equal N)");
+  GGNN_REQUIRE(base_set, GGNN_INVALID_STATE, "There is no base dataset the filters could refer to.");
+  const uint32_t words = static_cast<uint32_t>((n_bits + 31) / 32);
+  std::vector<uint32_t> table(static_cast<size_t>(F) * words);
+  if (loc == GGNN_GPU) {
+    GGNN_HIP_CHECK(hipSetDevice(gpu));
+    GGNN_HIP_CHECK(hipMemcpy(table.data(), bits, table.size() * sizeof(uint32_t),
+                             hipMemcpyDeviceToHost));
+  }
+  else
+    std::copy(bits, bits + table.size(), table.begin());
+  // batches in flight read the old table: drain them before it is freed
+  synchronize();
+  filter_table_host = std::move(table);
+  num_filters = F;
+  filter_words = words;
+  ++filter_epoch;
+  try {
+    place_filter_tables();
+  }
+  catch (...) {
+    drop_filters();
+    throw;
+  }
+}
+
+void ggnn_handle::update_filter(uint32_t index, const uint32_t* bits, uint64_t n_bits,
+                                ggnn_location loc, int gpu)
+{
+  GGNN_REQUIRE(num_filters != 0, GGNN_INVALID_STATE, "There is no filter table (ggnn_set_filters).");
+  GGNN_REQUIRE(index < num_filters, GGNN_OUT_OF_RANGE,
+               "filter index " + std::to_string(index) + " is outside the table of " +
+                   std::to_string(num_filters) + " filters");
+  GGNN_REQUIRE(bits != nullptr, GGNN_INVALID_ARGUMENT, "the filter bitset is null");
+  GGNN_REQUIRE(n_bits == base_N, GGNN_INVALID_ARGUMENT,
+               "a filter needs one bit per base vector (n_bits must equal N)");
+  uint32_t* row = filter_table_host.data() + static_cast<size_t>(index) * filter_words;
+  const size_t bytes = static_cast<size_t>(filter_words) * sizeof(uint32_t);
+  // no batch in flight may see a half-written row
+  synchronize();
+  if (loc == GGNN_GPU) {
+    GGNN_HIP_CHECK(hipSetDevice(gpu));
+    GGNN_HIP_CHECK(hipMemcpy(row, bits, bytes, hipMemcpyDeviceToHost));
+  }
+  else
+    std::copy(bits, bits + filter_words, row);
+  for (DeviceCtx& ctx : devs) {
+    if (ctx.filter_table_epoch != filter_epoch)
+      continue;  // (not placed yet: placed whole when it is first needed)
+    ctx.activate();
+    GGNN_HIP_CHECK(hipMemcpy(ctx.filter_table.as<uint32_t>() + static_cast<size_t>(index) * filter_words,
+                             row, bytes, hipMemcpyHostToDevice));
+  }
+}
+
+const uint32_t* ggnn_handle::place_filter_table(DeviceCtx& ctx)
+{
+  GGNN_REQUIRE(num_filters != 0, GGNN_INVALID_STATE, "There is no filter table (ggnn_set_filters).");
+  if (ctx.filter_table_epoch == filter_epoch && ctx.filter_table.p)
+    return ctx.filter_table.as<uint32_t>();
+  ctx.activate();
+  const size_t row = static_cast<size_t>(filter_words) * sizeof(uint32_t);
+  const size_t rows = static_cast<size_t>(num_filters);
+  ctx.filter_table_epoch = 0;
+  ctx.filter_table.alloc((rows + 2) * row);
+  uint8_t* p = static_cast<uint8_t*>(ctx.filter_table.p);
+  GGNN_HIP_CHECK(hipMemcpy(p, filter_table_host.data(), rows * row, hipMemcpyHostToDevice));
+  GGNN_HIP_CHECK(hipMemset(p + rows * row, 0xff, row));  // id -1: everything allowed
+  GGNN_HIP_CHECK(hipMemset(p + (rows + 1) * row, 0, row));  // any other id: nothing allowed
+  GGNN_HIP_CHECK(hipDeviceSynchronize());
+  ctx.filter_table_epoch = filter_epoch;
+  return ctx.filter_table.as<uint32_t>();
+}
+
+void ggnn_handle::place_filter_tables()
+{
+  if (!num_filters)
+    return;
+  DeviceRestoreGuard keep;
+  for (DeviceCtx& ctx : devs)
+    (void)place_filter_table(ctx);
+}
+
+FilterTable ggnn_handle::launch_filter_table(const DeviceCtx& ctx, const int32_t* ids) const
+{
+  FilterTable t{};
+  if (!ids)
+    return t;
+  t.ids = ids;
+  t.words = filter_words;
+  t.num_filters = num_filters;
+  t.consts = ctx.filter_table.as<uint32_t>() + static_cast<size_t>(num_filters) * filter_words;
+  return t;
+}
+
+void ggnn_handle::begin_filter_ids(const int32_t* ids, uint64_t Nq, ggnn_location loc, int gpu)
+{
+  GGNN_REQUIRE(num_filters != 0, GGNN_INVALID_STATE,
+               "There is no filter table the filter ids could refer to (ggnn_set_filters).");
+  GGNN_REQUIRE(!Nq || ids != nullptr, GGNN_INVALID_ARGUMENT, "the filter id array is null");
+  if (loc == GGNN_CPU)
+    for (uint64_t i = 0; i < Nq; ++i)
+      GGNN_REQUIRE(ids[i] >= -1 && ids[i] < static_cast<int64_t>(num_filters),
+                   GGNN_INVALID_ARGUMENT,
+                   "filter id " + std::to_string(ids[i]) + " of query " + std::to_string(i) +
+                       " is outside [-1, " + std::to_string(num_filters) + ")");
+  active_filter_ids.ids = ids;
+  active_filter_ids.count = Nq;
+  active_filter_ids.loc = loc;
+  active_filter_ids.gpu = gpu;
+}
+
+void ggnn_handle::query_filtered_by(const void* q, uint64_t Nq, uint32_t D, ggnn_dtype dtype,
+                                    ggnn_location loc, int q_gpu, uint32_t k_query,
+                                    float tau_query, uint32_t max_iterations, ggnn_measure measure,
+                                    int32_t* ids_out, float* dists_out, ggnn_location out_loc,
+                                    const int32_t* filter_ids, ggnn_location ids_loc, int ids_gpu)
+{
+  begin_filter_ids(filter_ids, Nq, ids_loc, ids_gpu);
+  FilterScope scope{*this};
+  query(q, Nq, D, dtype, loc, q_gpu, k_query, tau_query, max_iterations, measure, ids_out,
+        dists_out, out_loc);
+}
+
+void ggnn_handle::bf_query_filtered_by(const void* q, uint64_t Nq, uint32_t D, ggnn_dtype dtype,
+                                       ggnn_location loc, int q_gpu, uint32_t k_gt,
+                                       ggnn_measure measure, int32_t* ids_out, float* dists_out,
+                                       ggnn_location out_loc, const int32_t* filter_ids,
+                                       ggnn_location ids_loc, int ids_gpu)
+{
+  begin_filter_ids(filter_ids, Nq, ids_loc, ids_gpu);
   FilterScope scope{*this};
   bf_query(q, Nq, D, dtype, loc, q_gpu, k_gt, measure, ids_out, dists_out, out_loc);
 }

@@ -165,6 +165,7 @@ void ggnn_handle::prepare(uint32_t KBuild)
       if (slots)
         setup_swap(ctx, slots, base_here);
     }
+    place_filter_tables();  // a filter table set earlier follows the handle to its (new) GPUs
   }
   catch (...) {
     rollback_graph();

@@ -438,8 +438,8 @@ static void launch_query_cfg(const QueryArgs& args, bool use_ps, ggnn_measure me
 void launch_query_16(const QueryArgs& args, ggnn_measure measure, ggnn_dtype dtype,
                      hipStream_t stream);
 // restricted to an allowed-id bitset: query_filtered.hip
-void launch_query_filtered(const QueryArgs& args, bool use_ps, ggnn_measure measure,
-                           ggnn_dtype dtype, hipStream_t stream);
+void launch_query_filtered(const QueryArgs& base, const FilterTable& table, bool use_ps,
+                           ggnn_measure measure, ggnn_dtype dtype, hipStream_t stream);
 
 void launch_query(const QueryLaunch& a, hipStream_t stream)
 {
@@ -529,7 +529,7 @@ void launch_query(const QueryLaunch& a, hipStream_t stream)
   if (a.filter_bits) {
     args.filter_bits = a.filter_bits;
     args.filter_bit_offset = a.filter_bit_offset;
-    launch_query_filtered(args, use_ps, a.measure, a.dtype, stream);
+    launch_query_filtered(args, a.filter_table, use_ps, a.measure, a.dtype, stream);
   }
   else if (dtype_is_16bit(a.dtype)) {
     launch_query_16(args, a.measure, a.dtype, stream);

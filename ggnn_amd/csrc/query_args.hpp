@@ -28,9 +28,17 @@ struct QueryArgs {
   int32_t* ring;
   uint32_t tag_bits;
   // filtered search (query_filtered.hip): allowed-id bitset over the global ids and the first
-  // global id of this shard; null for the unfiltered kernels
+  // global id of this shard; null for the unfiltered kernels (with per-query filters: the table,
+  // see FilteredQueryArgs)
   const uint32_t* filter_bits;
   uint32_t filter_bit_offset;
+};
+
+// Arguments of the filtered kernels (query_filtered.hip): per-query filters make filter_bits a
+// table and add the id array beside it.  A struct of its own, so that the unfiltered kernels keep
+// their argument block -- and stay the same code objects -- whatever the filters grow into.
+struct FilteredQueryArgs : QueryArgs {
+  FilterTable filter_table;
 };
 
 }  // namespace ggnn_amd

@@ -42,7 +42,7 @@ constexpr int filtered_waves()
 template <typename BaseT, int LPR, int NCH, int R, int MODE, class PSC, int HB = 0, bool EARLY = false>
 __global__ void __launch_bounds__(kWave) __attribute__((
     amdgpu_waves_per_eu((R == 1 && NCH <= 3) ? filtered_waves<NCH, MODE, PSC, EARLY>() : 1)))
-query_filtered_kernel(const QueryArgs a)
+query_filtered_kernel(const FilteredQueryArgs a)
 {
   static_assert(HB >= 0, "the filtered kernels keep their visited ring in LDS");
   extern __shared__ __attribute__((aligned(16))) int lds_raw[];
@@ -68,7 +68,9 @@ query_filtered_kernel(const QueryArgs a)
 
   SortedList<R, HB> sl;
   sl.init(a.KQuery, a.sorted, a.cache, xi, lds.known, static_cast<int>(a.vis_slots));
-  IdFilter idf{a.filter_bits, a.filter_bit_offset, kEmptyKey, 0u};
+  // this wave's bitset: the call's, or the row of the table its query's filter id names
+  IdFilter idf{wave_filter_bits(a.filter_bits, a.filter_table, n), a.filter_bit_offset, kEmptyKey,
+               0u};
 
   uint32_t cnt_dist = 0, cnt_pop = 0;
   uint2 cnt_rows = make_uint2(0u, 0u);
@@ -173,7 +175,7 @@ query_filtered_kernel(const QueryArgs a)
 
 // the LDS-resident list (SORTED > 2048, or > 512 with the pre-screen)
 template <typename BaseT, int LPR, int NCH, int MODE, class PSC>
-__global__ void __launch_bounds__(kWave) query_filtered_kernel_lds(const QueryArgs a)
+__global__ void __launch_bounds__(kWave) query_filtered_kernel_lds(const FilteredQueryArgs a)
 {
   extern __shared__ __attribute__((aligned(16))) int lds_raw[];
   int* keys = lds_raw;
@@ -193,7 +195,9 @@ __global__ void __launch_bounds__(kWave) query_filtered_kernel_lds(const QueryAr
   load_prescreen_filtered(ps, a, query + static_cast<size_t>(n) * a.D);
   LdsList sl;
   sl.init(a.KQuery, a.sorted, a.cache, xi, keys, dists);
-  IdFilter idf{a.filter_bits, a.filter_bit_offset, kEmptyKey, 0u};
+  // this wave's bitset: the call's, or the row of the table its query's filter id names
+  IdFilter idf{wave_filter_bits(a.filter_bits, a.filter_table, n), a.filter_bit_offset, kEmptyKey,
+               0u};
   uint32_t cnt_dist = 0, cnt_pop = 0;
   uint2 cnt_rows = make_uint2(0u, 0u);
   for (uint32_t i = 0; i < a.num_start; i += kKBlock) {
@@ -239,7 +243,7 @@ constexpr bool filtered_early_layout()
 }
 
 template <typename BaseT, int LPR, int NCH, int MODE, class PSC>
-static void launch_query_filtered_r(const QueryArgs& args, hipStream_t stream)
+static void launch_query_filtered_r(const FilteredQueryArgs& args, hipStream_t stream)
 {
   const uint32_t sorted = args.sorted;
   const size_t lds = wave_lds_bytes(args.cache);
@@ -287,7 +291,7 @@ static void launch_query_filtered_r(const QueryArgs& args, hipStream_t stream)
 }
 
 template <typename BaseT, int LPR, int NCH>
-static void launch_query_filtered_cfg(const QueryArgs& args, bool use_ps, ggnn_measure measure,
+static void launch_query_filtered_cfg(const FilteredQueryArgs& args, bool use_ps, ggnn_measure measure,
                                       hipStream_t stream)
 {
   if constexpr (std::is_same<BaseT, float>::value) {
@@ -306,13 +310,43 @@ static void launch_query_filtered_cfg(const QueryArgs& args, bool use_ps, ggnn_m
 }
 
 #ifndef GGNN_ROWS_16_TU
-void launch_query_filtered_16(const QueryArgs& args, ggnn_measure measure, ggnn_dtype dtype,
+void launch_query_filtered_16(const FilteredQueryArgs& args, ggnn_measure measure, ggnn_dtype dtype,
                               hipStream_t stream);
 
-// args: filled by launch_query (query.hip), filter_bits set
-void launch_query_filtered(const QueryArgs& args, bool use_ps, ggnn_measure measure,
-                           ggnn_dtype dtype, hipStream_t stream)
+// the all-ones / all-zero rows of a launch with filter ids that brings none (operator seam; the
+// engine keeps them behind its resident table)
+uint32_t* filter_consts_scratch(const FilterTable& t, hipStream_t stream)
 {
+  if (!t.ids || t.consts)
+    return nullptr;
+  const size_t row = static_cast<size_t>(t.words) * sizeof(uint32_t);
+  uint8_t* p = static_cast<uint8_t*>(scratch_alloc(2 * row, stream));
+  GGNN_HIP_CHECK(hipMemsetAsync(p, 0xff, row, stream));
+  GGNN_HIP_CHECK(hipMemsetAsync(p + row, 0, row, stream));
+  return reinterpret_cast<uint32_t*>(p);
+}
+
+// base: filled by launch_query (query.hip), filter_bits set; table: the launch's per-query filters
+void launch_query_filtered(const QueryArgs& base, const FilterTable& table, bool use_ps,
+                           ggnn_measure measure, ggnn_dtype dtype, hipStream_t stream)
+{
+  FilteredQueryArgs args{};
+  static_cast<QueryArgs&>(args) = base;
+  args.filter_table = table;
+  if (table.ids)
+    GGNN_REQUIRE(table.words != 0 && table.num_filters != 0, GGNN_INVALID_ARGUMENT,
+                 "filter ids need a filter table");
+  struct ConstGuard {
+    void* p;
+    hipStream_t s;
+    ~ConstGuard()
+    {
+      if (p)
+        scratch_free(p, s);
+    }
+  } guard{filter_consts_scratch(table, stream), stream};
+  if (guard.p)
+    args.filter_table.consts = static_cast<const uint32_t*>(guard.p);
   if (dtype_is_16bit(dtype)) {
     launch_query_filtered_16(args, measure, dtype, stream);
     return;
@@ -322,7 +356,7 @@ void launch_query_filtered(const QueryArgs& args, bool use_ps, ggnn_measure meas
 #undef GGNN_LAUNCH_QF
 }
 #else
-void launch_query_filtered_16(const QueryArgs& args, ggnn_measure measure, ggnn_dtype dtype,
+void launch_query_filtered_16(const FilteredQueryArgs& args, ggnn_measure measure, ggnn_dtype dtype,
                               hipStream_t stream)
 {
 #define GGNN_LAUNCH_QF(T, LPR, NCH) launch_query_filtered_cfg<T, LPR, NCH>(args, false, measure, stream)

@@ -1644,6 +1644,25 @@ struct IdFilter {
   }
 };
 
+// Filter table (per-query filters): [num_filters x words] bitsets of the format above, one int32
+// id per query.  The wave picks its bitset ONCE, before its loop; everything here is scalar (the
+// query number is wave-uniform), so IdFilter sees one more wave-uniform pointer and nothing else.
+//   ids == nullptr         the per-call form: one row, shared by every query
+//   id in [0, num_filters) that row of the table
+//   id == -1               unfiltered: the constant all-ones row consts[0, words)
+//   anything else          empty result: the constant all-zero row consts[words, 2 * words)
+// No id value leads outside table / consts.  (FilterTable: common.hpp)
+GGNN_DEV const uint32_t* wave_filter_bits(const uint32_t* table, const FilterTable& t,
+                                          const uint32_t n)
+{
+  if (!t.ids)
+    return table;
+  const int32_t f = __builtin_amdgcn_readfirstlane(t.ids[n]);
+  if (static_cast<uint32_t>(f) < t.num_filters)
+    return table + static_cast<size_t>(static_cast<uint32_t>(f)) * t.words;
+  return t.consts + (f == -1 ? 0u : t.words);
+}
+
 // the replay of a fetch (simple_knn_cache.cuh:268-286) under a filter: as replay_lanes() below,
 // a denied candidate is pushed with the flag
 template <class SL>

@@ -202,6 +202,78 @@ def bf_query_filtered(base, query, k_query, filter_bits, measure=EUCLIDEAN, filt
     return ids, dists
 
 
+def _need_filter_table(filter_table, filter_ids, Nq, n_bits_min):
+    _need(filter_table, torch.int32, "filter_table"), _need(filter_ids, torch.int32, "filter_ids")
+    if filter_table.dim() != 2 or filter_table.shape[0] == 0:
+        raise ValueError("filter_table must be [F, words] with F >= 1")
+    if filter_table.shape[1] * 32 < n_bits_min:
+        raise ValueError("the rows of filter_table are shorter than filter_bit_offset + N bits")
+    if filter_ids.dim() != 1 or filter_ids.numel() != Nq:
+        raise ValueError("filter_ids must be 1-dimensional with one entry per query")
+
+
+def query_filtered_by(base, query, graph0, start, nn1_stats, k_query, tau_query, filter_table,
+                      filter_ids, max_iterations=400, measure=EUCLIDEAN, filter_bit_offset=0,
+                      shards_per_gpu=1, on_gpu_shard=0, counters=False, prescreen=None,
+                      rows_read=None):
+    """`query_filtered` with one filter per query: filter_table is [F, words] packed int32 bitsets
+    (ggnn_amd.pack_filters), query n searches under row filter_ids[n] (int32 CUDA tensor); id -1
+    searches unfiltered and any other id outside [0, F) gives an empty result."""
+    _need(base, name="base"), _need(query, base.dtype, "query")
+    _need(graph0, torch.int32, "graph0"), _need(start, torch.int32, "start")
+    _need(nn1_stats, torch.float32, "nn1_stats")
+    Nq = query.shape[0]
+    _need_filter_table(filter_table, filter_ids, Nq, filter_bit_offset + base.shape[0])
+    ids = torch.empty((Nq, k_query * shards_per_gpu), dtype=torch.int32, device=base.device)
+    dists = torch.empty((Nq, k_query * shards_per_gpu), dtype=torch.float32, device=base.device)
+    nd = npop = None
+    if counters:
+        nd = torch.zeros(Nq, dtype=torch.int32, device=base.device)
+        npop = torch.zeros(Nq, dtype=torch.int32, device=base.device)
+    codes, params = prescreen if prescreen is not None else (None, None)
+    if prescreen is not None:
+        _need(base, torch.float32, "base"), _need(codes, torch.uint8, "codes")
+        _need(params, torch.float32, "params")
+    check(lib().ggnn_op_query_filtered_by(
+        _ptr(base), _dtype_code(base), base.shape[0], base.shape[1], _ptr(codes), _ptr(params),
+        _ptr(query), Nq, _ptr(graph0), graph0.shape[1], _ptr(start), start.numel(),
+        _ptr(nn1_stats), k_query, tau_query, max_iterations, measure, shards_per_gpu,
+        on_gpu_shard, _ptr(ids), _ptr(dists), _ptr(nd), _ptr(npop), _ptr(rows_read),
+        _ptr(filter_table), filter_table.shape[0], filter_table.shape[1] * 32, _ptr(filter_ids),
+        filter_bit_offset, _stream()))
+    if counters:
+        return ids, dists, nd, npop
+    return ids, dists
+
+
+def bf_query_filtered_by(base, query, k_query, filter_table, filter_ids, measure=EUCLIDEAN,
+                         filter_bit_offset=0):
+    """`bf_query_filtered` with one filter per query (see query_filtered_by)"""
+    _need(base, name="base"), _need(query, base.dtype, "query")
+    Nq = query.shape[0]
+    _need_filter_table(filter_table, filter_ids, Nq, filter_bit_offset + base.shape[0])
+    ids = torch.empty((Nq, k_query), dtype=torch.int32, device=base.device)
+    dists = torch.empty((Nq, k_query), dtype=torch.float32, device=base.device)
+    check(lib().ggnn_op_bf_query_filtered_by(
+        _ptr(base), _dtype_code(base), base.shape[0], base.shape[1], _ptr(query), Nq, k_query,
+        measure, _ptr(ids), _ptr(dists), _ptr(filter_table), filter_table.shape[0],
+        filter_table.shape[1] * 32, _ptr(filter_ids), filter_bit_offset, _stream()))
+    return ids, dists
+
+
+def pack_filters(masks):
+    """[F, N] boolean CUDA masks -> [F, ceil(N / 32)] int32 bitset words on the same GPU (bit
+    i & 31 of word i >> 5 is mask i; padding bits zero)"""
+    _need(masks, torch.bool, "masks")
+    if masks.dim() != 2:
+        raise ValueError("masks must be [F, N]")
+    F, N = masks.shape
+    words = torch.empty((F, (N + 31) // 32), dtype=torch.int32, device=masks.device)
+    with torch.cuda.device(masks.device):
+        check(lib().ggnn_op_pack_filters(_ptr(masks), F, N, _ptr(words), _stream()))
+    return words
+
+
 def bf_query(base, query, k_query, measure=EUCLIDEAN, rescanned=False):
     """rescanned=True: also return how many queries the matrix-core path handed to the scan"""
     _need(base, name="base"), _need(query, base.dtype, "query")

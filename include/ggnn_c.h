@@ -133,8 +133,8 @@ ggnn_status ggnn_bf_query(ggnn_t* h, const void* query, uint64_t Nq, uint32_t D,
                           ggnn_location out_location);
 
 /* Filtered search (an extension: the reference has no filter).  ggnn_query / ggnn_bf_query
- * restricted to the base vectors a bitset allows: one filter per call, shared by all queries of
- * the batch, over the GLOBAL base ids -- uint32 words, id i is allowed iff bit (i & 31) of word
+ * restricted to the base vectors a bitset allows: here one filter per call, shared by all queries
+ * of the batch (per-query filters: ggnn_set_filters below), over the GLOBAL base ids -- uint32 words, id i is allowed iff bit (i & 31) of word
  * (i >> 5) is set, ceil(n_bits / 32) words, bits at and above n_bits are ignored.  n_bits must
  * equal the base's N (GGNN_INVALID_ARGUMENT otherwise, also for a null bitset).  The bitset
  * may live on the host (filter_location GGNN_CPU; copied per call) or on GPU filter_gpu_id;
@@ -161,6 +161,56 @@ ggnn_status ggnn_bf_query_filtered(ggnn_t* h, const void* query, uint64_t Nq, ui
                                    float* dists_out, ggnn_location out_location,
                                    const uint32_t* allowed_bits, uint64_t n_bits,
                                    ggnn_location filter_location, int filter_gpu_id);
+
+/* Per-query filters: a resident filter table and one filter id per query.
+ * The table is num_filters bitsets of the format above ([num_filters x ceil(n_bits / 32)] words,
+ * n_bits must equal the base's N: GGNN_INVALID_ARGUMENT otherwise and for a null table with
+ * num_filters > 0; GGNN_INVALID_STATE before ggnn_set_base).  ggnn_set_filters COPIES it (from
+ * the host, or from GPU gpu_id): the engine keeps it on the host and places it on every GPU of
+ * the handle as soon as those are known -- again after ggnn_build / ggnn_load / ggnn_set_gpus --
+ * about num_filters * ceil(N / 32) * 4 bytes per GPU (plus two constant rows);
+ * GGNN_OUT_OF_MEMORY if that cannot be allocated.  num_filters == 0 drops the table, and so does
+ * ggnn_set_base.  ggnn_set_filters and ggnn_update_filter (replaces row `index` on every GPU;
+ * GGNN_OUT_OF_RANGE for index >= num_filters) SYNCHRONISE: they first wait for every asynchronous
+ * slot, so no batch in flight sees a half-written row.
+ *
+ * The *_filtered_by calls take one int32 filter id per query (filter_ids[Nq]) instead of a bitset:
+ *   id f in [0, num_filters)  the result of ggnn_query_filtered / ggnn_bf_query_filtered of that
+ *                             query with row f, bit for bit (ids, distances, counters);
+ *   id -1                     unfiltered: the result of ggnn_query / ggnn_bf_query, bit for bit;
+ *   any other id              an empty result: every slot (-1 + id offset, +inf).
+ * No id value makes a kernel read outside the table.  The blocking calls read an id array in host
+ * memory first and answer anything outside [-1, num_filters) with GGNN_INVALID_ARGUMENT (an id
+ * array in device memory is not read back: there the rule above holds).  GGNN_INVALID_STATE
+ * without a table.  Everything else is ggnn_query / ggnn_bf_query: shards, GPUs, exchange modes,
+ * out-of-core shards, result location, counters and timings.
+ * ggnn_query_async_filtered_by is ggnn_query_async with filter ids.  The ids follow the memory
+ * rule of `query` in that call: handle on one GPU -- device memory on that GPU; several GPUs --
+ * device memory of GPU gpu_id or, with gpu_id < 0, page-locked host memory, copied on the slot's
+ * stream.  They must stay alive and untouched until the slot is synchronised.  Nothing is staged
+ * per call but the ids, which is why the table is resident. */
+ggnn_status ggnn_set_filters(ggnn_t* h, const uint32_t* bits, uint32_t num_filters,
+                             uint64_t n_bits, ggnn_location location, int gpu_id);
+ggnn_status ggnn_update_filter(ggnn_t* h, uint32_t index, const uint32_t* bits, uint64_t n_bits,
+                               ggnn_location location, int gpu_id);
+ggnn_status ggnn_get_num_filters(const ggnn_t* h, uint32_t* num_filters);
+ggnn_status ggnn_query_filtered_by(ggnn_t* h, const void* query, uint64_t Nq, uint32_t D,
+                                   ggnn_dtype dtype, ggnn_location location, int gpu_id,
+                                   uint32_t k_query, float tau_query, uint32_t max_iterations,
+                                   ggnn_measure measure, int32_t* ids_out, float* dists_out,
+                                   ggnn_location out_location, const int32_t* filter_ids,
+                                   ggnn_location ids_location, int ids_gpu_id);
+ggnn_status ggnn_bf_query_filtered_by(ggnn_t* h, const void* query, uint64_t Nq, uint32_t D,
+                                      ggnn_dtype dtype, ggnn_location location, int gpu_id,
+                                      uint32_t k_gt, ggnn_measure measure, int32_t* ids_out,
+                                      float* dists_out, ggnn_location out_location,
+                                      const int32_t* filter_ids, ggnn_location ids_location,
+                                      int ids_gpu_id);
+ggnn_status ggnn_query_async_filtered_by(ggnn_t* h, const void* query, uint64_t Nq, uint32_t D,
+                                         ggnn_dtype dtype, int gpu_id, uint32_t k_query,
+                                         float tau_query, uint32_t max_iterations,
+                                         ggnn_measure measure, int32_t* ids_out, float* dists_out,
+                                         uint32_t slot, const int32_t* filter_ids);
 
 /* layout of one graph shard, include/ggnn/base/graph_config.h:31-112 */
 typedef struct {
@@ -411,6 +461,35 @@ ggnn_status ggnn_op_bf_query_filtered(const void* base, ggnn_dtype dtype, uint32
                                       uint32_t k_query, ggnn_measure measure, int32_t* ids,
                                       float* dists, const uint32_t* filter_bits,
                                       uint32_t filter_bit_offset, void* stream);
+
+/* The two calls above with a filter table and one filter id per query (all device memory):
+ * filter_table is [num_filters x ceil(n_bits / 32)] words, n_bits >= filter_bit_offset + N_base;
+ * query n searches under row filter_ids[n], -1 = unfiltered, any other id = empty result (the
+ * constant rows those two read are made in scratch memory of the launch). */
+ggnn_status ggnn_op_query_filtered_by(const void* base, ggnn_dtype dtype, uint32_t N_base,
+                                      uint32_t D, const uint8_t* codes, const float* params,
+                                      const void* query, uint32_t Nq, const int32_t* graph0,
+                                      uint32_t KBuild, const int32_t* start, uint32_t num_start,
+                                      const float* nn1_stats, uint32_t k_query, float tau_query,
+                                      uint32_t max_iterations, ggnn_measure measure,
+                                      uint32_t shards_per_gpu, uint32_t on_gpu_shard, int32_t* ids,
+                                      float* dists, uint32_t* n_dist, uint32_t* n_pop,
+                                      uint32_t* n_rows, const uint32_t* filter_table,
+                                      uint32_t num_filters, uint64_t n_bits,
+                                      const int32_t* filter_ids, uint32_t filter_bit_offset,
+                                      void* stream);
+ggnn_status ggnn_op_bf_query_filtered_by(const void* base, ggnn_dtype dtype, uint32_t N_base,
+                                         uint32_t D, const void* query, uint32_t Nq,
+                                         uint32_t k_query, ggnn_measure measure, int32_t* ids,
+                                         float* dists, const uint32_t* filter_table,
+                                         uint32_t num_filters, uint64_t n_bits,
+                                         const int32_t* filter_ids, uint32_t filter_bit_offset,
+                                         void* stream);
+/* [num_filters x N] byte masks (non-zero: allowed) -> [num_filters x ceil(N / 32)] bitset words,
+ * padding bits zero; both in device memory.  A table made from a label column on the GPU needs
+ * no host round trip. */
+ggnn_status ggnn_op_pack_filters(const uint8_t* masks, uint32_t num_filters, uint64_t N,
+                                 uint32_t* words, void* stream);
 
 /* QueryKernels::bruteForceQuery  query_kernels.cu:188-264 -> bf_query_layer.cu:39-65 */
 ggnn_status ggnn_op_bf_query(const void* base, ggnn_dtype dtype, uint32_t N_base, uint32_t D,

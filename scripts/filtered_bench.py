@@ -6,7 +6,21 @@
 Per share: kernel ms of the filtered call (best of --reps), n_dist and n_pop per query, recall@10
 against bf_query_filtered, and the scan time of that brute force; the first line is the
 unfiltered call of the same handle (the 100 % line against it is the cost of the bit read).
-One JSON line per row."""
+One JSON line per row.
+
+    python scripts/filtered_bench.py --mixed [--tenants 16] [--big-table 1024]
+
+Per-query filters (a resident filter table, one filter id per query), every repeat listed:
+  * "indirection": the 50 % and 10 % bitsets as a one-row table with every id 0 against the
+    per-call query_filtered of the same bitset, alternating: kernel ms;
+  * "mixed": --tenants disjoint tenants of N / tenants rows, ids drawn uniformly: one
+    query_filtered(filter_ids=...) call, the same batch as two query_async slots, and the only way
+    without a table -- one per-call query_filtered per tenant on the queries grouped by tenant,
+    host bitsets staged per call: queries/s end to end (host clock around calls that end
+    synchronised, queries and ids on the GPU), recall@10 against bf_query_filtered(filter_ids=...),
+    bytes staged per batch;
+  * "locality": kernel ms of a mixed batch over --tenants and over --big-table random rows of
+    equal density (1 / tenants), so that only the table's footprint changes."""
 import argparse
 import json
 import os
@@ -28,6 +42,9 @@ def main():
     ap.add_argument("--tau", type=float, default=0.5)
     ap.add_argument("--iters", type=int, default=400)
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--mixed", action="store_true")
+    ap.add_argument("--tenants", type=int, default=16)
+    ap.add_argument("--big-table", type=int, default=1024)
     a = ap.parse_args()
     rs = np.random.default_rng(1)
     centres = rs.normal(size=(256, a.d)).astype(np.float32) * 2
@@ -37,6 +54,9 @@ def main():
     g.set_base(torch.from_numpy(base).cuda())
     g.build(24, 0.5)
     q = torch.from_numpy(query).cuda()
+    if a.mixed:
+        mixed(a, g, q)
+        return
 
     def timed(fn):
         best = float("inf")
@@ -72,6 +92,107 @@ def main():
         print(json.dumps({"filter": share, "allowed": int(mask.sum()), "query_ms": round(ms, 4),
                           "n_dist": round(nd, 1), "n_pop": round(npop, 1),
                           "recall": round(float(rec), 4), "bf_filtered_ms": round(bf_ms, 3)}),
+              flush=True)
+
+
+def mixed(a, g, q):
+    import time
+
+    def recall(ids, gt):
+        ids, gt = ids.cpu().numpy(), gt.cpu().numpy()
+        return float(np.mean([len(set(x[x >= 0].tolist()) & set(y[y >= 0].tolist())) /
+                              max(1, int((y >= 0).sum())) for x, y in zip(ids, gt)]))
+
+    def kernel_ms(fn):
+        fn()
+        return g.last_timing_ms()["query_ms"]
+
+    def wall(fn):
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        return time.perf_counter() - t
+
+    words = (a.n + 31) // 32
+    # ---- cost of the indirection ----------------------------------------------------------------
+    for share in (0.5, 0.1):
+        mask = np.random.default_rng(int(share * 1000)).random(a.n) < share
+        bits = ggnn.pack_filter(mask).cuda()
+        g.set_filters(bits[None, :])
+        zero = torch.zeros(a.queries, dtype=torch.int32, device="cuda")
+        per_call = lambda: g.query_filtered(q, a.k, a.tau, a.iters, filter=bits)  # noqa: E731
+        by_id = lambda: g.query_filtered_by(q, a.k, a.tau, a.iters, filter_ids=zero)  # noqa: E731
+        x, y = per_call(), by_id()
+        assert torch.equal(x[0], y[0]) and torch.equal(x[1], y[1])
+        ms = {"per_call": [], "table": []}
+        for _ in range(a.reps):                               # alternating
+            ms["per_call"].append(round(kernel_ms(per_call), 4))
+            ms["table"].append(round(kernel_ms(by_id), 4))
+        print(json.dumps({"indirection": share, "kernel_ms": ms}), flush=True)
+
+    # ---- what the feature buys ------------------------------------------------------------------
+    F = a.tenants
+    rs = np.random.default_rng(7)
+    tenant = torch.from_numpy(rs.permutation(a.n) % F).cuda()        # disjoint, N / F rows each
+    masks = tenant[None, :] == torch.arange(F, device="cuda")[:, None]
+    table = ggnn.pack_filters(masks)
+    g.set_filters(table)
+    fids_h = rs.integers(0, F, a.queries).astype(np.int32)
+    fids = torch.from_numpy(fids_h).cuda()
+    host_bits = [table[f].cpu() for f in range(F)]
+    groups = [q[torch.from_numpy(np.nonzero(fids_h == f)[0]).cuda()].contiguous() for f in range(F)]
+    half = a.queries // 2
+    parts = [(q[:half], fids[:half]), (q[half:], fids[half:])]
+
+    def one_call():
+        return g.query_filtered_by(q, a.k, a.tau, a.iters, filter_ids=fids)
+
+    def two_slots():
+        t = [g.query_async(x, a.k, a.tau, a.iters, slot=i, filter_ids=f)
+             for i, (x, f) in enumerate(parts)]
+        g.synchronize()
+        return t
+
+    def per_tenant():
+        return [g.query_filtered(groups[f], a.k, a.tau, a.iters, filter=host_bits[f])
+                for f in range(F)]
+
+    gt, _ = g.bf_query_filtered_by(q, a.k, filter_ids=fids)
+    ids, _ = one_call()
+    grouped = per_tenant()
+    ids_grouped = torch.empty_like(ids)
+    for f in range(F):
+        ids_grouped[torch.from_numpy(np.nonzero(fids_h == f)[0])] = grouped[f][0]
+    t = two_slots()
+    ids_async = torch.cat([t[0].ids, t[1].ids])[:, :a.k].cpu()
+    rows = {"one_call": (one_call, ids, 0),
+            "two_async_slots": (two_slots, ids_async, 0),
+            "per_tenant_calls": (per_tenant, ids_grouped, F * words * 4)}
+    secs = {k: [] for k in rows}
+    for _ in range(a.reps):                                   # alternating
+        for k, (fn, _, _) in rows.items():
+            secs[k].append(wall(fn))
+    for k, (fn, r_ids, staged) in rows.items():
+        print(json.dumps({"mixed": k, "tenants": F,
+                          "queries_per_s": [round(a.queries / s) for s in secs[k]],
+                          "recall": round(recall(r_ids, gt), 4),
+                          "bytes_staged_per_batch": staged}), flush=True)
+
+    # ---- table locality -------------------------------------------------------------------------
+    for rows_f in (F, a.big_table):
+        rs = np.random.default_rng(rows_f)
+        tab = torch.empty((rows_f, words), dtype=torch.int32, device="cuda")
+        for r0 in range(0, rows_f, 64):                       # random rows of density 1 / F
+            n_r = min(64, rows_f - r0)
+            m = torch.rand((n_r, a.n), device="cuda") < 1.0 / F
+            tab[r0:r0 + n_r] = ggnn.pack_filters(m)
+        g.set_filters(tab)
+        ids_r = torch.from_numpy(rs.integers(0, rows_f, a.queries).astype(np.int32)).cuda()
+        call = lambda: g.query_filtered_by(q, a.k, a.tau, a.iters, filter_ids=ids_r)  # noqa: E731
+        call()
+        print(json.dumps({"locality": rows_f, "table_mb": round(rows_f * words * 4 / 2 ** 20, 2),
+                          "kernel_ms": [round(kernel_ms(call), 4) for _ in range(a.reps)]}),
               flush=True)
 
 
