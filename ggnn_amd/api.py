@@ -153,6 +153,27 @@ def _filter_ids(filter_ids, Nq):
     return filter_ids.contiguous()
 
 
+_INT32_MIN, _INT32_MAX = -2 ** 31, 2 ** 31 - 1
+
+
+def _labels(labels, n, what="labels", per="base vector"):
+    """a label argument as a contiguous 1-D int32 tensor of length n (CPU or CUDA): int32 is taken
+    as it is, int64 is converted when every value fits int32 (ValueError otherwise)"""
+    if isinstance(labels, np.ndarray):
+        labels = torch.from_numpy(np.ascontiguousarray(labels))
+    if not isinstance(labels, torch.Tensor) or labels.dim() != 1:
+        raise TypeError(f"{what} must be a 1-dimensional numpy array or torch tensor")
+    if labels.dtype not in (torch.int32, torch.int64):
+        raise TypeError(f"{what} must be int32 (or int64 with values that fit int32)")
+    if labels.numel() != n:
+        raise ValueError(f"{what} needs one entry per {per} ({n})")
+    if labels.dtype == torch.int64:
+        if labels.numel() and (int(labels.min()) < _INT32_MIN or int(labels.max()) > _INT32_MAX):
+            raise ValueError(f"{what} has values outside the int32 range")
+        labels = labels.to(torch.int32)
+    return labels.contiguous()
+
+
 def _filter_words(filter, N):
     """the `filter` argument of query_filtered / bf_query_filtered as a contiguous int32 tensor of
     ceil(N / 32) words (CPU or CUDA): a boolean mask of length N is packed on the host, an
@@ -276,8 +297,8 @@ _MAX_TICKETS_PER_SLOT = 64   # query_async batches whose tensors are held per sl
 
 class QueryTicket:
     """Result of `GGNN.query_async`: `ids, dists = ticket` works as before; `query` keeps the
-    input alive (and `filter_ids` the filter ids of a batch that has some); `done` is set by
-    `synchronize()`."""
+    input alive (and `filter_ids` the filter ids, or the query labels, of a batch that has some);
+    `done` is set by `synchronize()`."""
     __slots__ = ("query", "ids", "dists", "slot", "done", "filter_ids")
 
     def __init__(self, query, ids, dists, slot, filter_ids=None):
@@ -449,6 +470,84 @@ class GGNN:
         self._check(lib().ggnn_get_num_filters(self._h, C.byref(n)))
         return int(n.value)
 
+    def set_labels(self, labels):
+        """Extension: label filters.  `labels` is one int32 label per base vector -- 1-D int32 or
+        int64 (values must fit int32) of length N, numpy / torch, CPU or GPU.  The engine copies the
+        column and keeps it on every GPU it drives (4 * N bytes, whatever the number of distinct
+        labels), also across `build` / `load`; queries then carry one label each (`labels=` of
+        `query_labeled`, `bf_query_labeled` and `query_async_labeled`) and are given base vectors of that
+        label only.  `None` drops the labels.  Waits for batches in flight."""
+        if labels is None:
+            self._check(lib().ggnn_set_labels(self._h, None, 0, _lib.CPU, 0))
+            return
+        N = self._N
+        lab = _labels(labels, N)
+        lloc, ldev = _loc(lab)
+        self._check(lib().ggnn_set_labels(self._h, lab.data_ptr(), N, lloc, ldev))
+
+    def update_labels(self, ids, labels):
+        """Extension: relabel some rows, `labels[ids[i]] = labels_new[i]` in order (the last pair
+        of a repeated id wins), on every GPU.  `ids`: 1-D int32 / int64 base ids, `labels`: as many
+        int32 / int64 labels.  Waits for batches in flight."""
+        if isinstance(ids, np.ndarray):
+            ids = torch.from_numpy(np.ascontiguousarray(ids))
+        if not isinstance(ids, torch.Tensor) or ids.dim() != 1 or \
+                ids.dtype not in (torch.int32, torch.int64):
+            raise TypeError("ids must be a 1-dimensional int32 / int64 numpy array or torch tensor")
+        lab = _labels(labels, ids.numel(), per="id")
+        ids = ids.to(device=lab.device, dtype=torch.int64).contiguous()
+        lloc, ldev = _loc(lab)
+        self._check(lib().ggnn_update_labels(self._h, ids.data_ptr(), lab.data_ptr(), ids.numel(),
+                                             lloc, ldev))
+
+    @property
+    def num_labels(self):
+        """length of the resident label column (N), 0 without labels"""
+        n = C.c_uint64(0)
+        self._check(lib().ggnn_get_num_labels(self._h, C.byref(n)))
+        return int(n.value)
+
+    def query_labeled(self, query, k_query, tau_query, max_iterations=400,
+                      measure=DistanceMeasure.Euclidean, labels=None):
+        """Extension: `query` under label filters (`set_labels`).  `labels`: one label per query,
+        1-D int32 / int64 of length Nq, CPU or GPU; query n is given base vectors whose label
+        equals labels[n] -- bit for bit `query_filtered` with the mask `base_labels == labels[n]`
+        -- and label -1 searches unfiltered.  A label no base vector carries gives an empty
+        result (ids -1, distances +inf).  `labels=None` is `query`."""
+        if labels is None:
+            return self.query(query, k_query, tau_query, max_iterations, measure)
+        t = _as_tensor(query, what="query")
+        ql = _labels(labels, t.shape[0], per="query")
+        loc, dev = _loc(t)
+        lloc, ldev = _loc(ql)
+        on_gpu = self._return_results_on_gpu
+        width = int(k_query) * (self._shards if on_gpu else 1)
+        ids, dists = self._out(t.shape[0], width, on_gpu, self._result_device(t) if on_gpu else None)
+        self._check(lib().ggnn_query_labeled(
+            self._h, t.data_ptr(), t.shape[0], t.shape[1], _dtype_code(t), loc, dev, int(k_query),
+            float(tau_query), int(max_iterations), int(measure), ids.data_ptr(), dists.data_ptr(),
+            _lib.GPU if on_gpu else _lib.CPU, ql.data_ptr(), lloc, ldev))
+        return ids, dists
+
+    def bf_query_labeled(self, query, k_gt=100, measure=DistanceMeasure.Euclidean, labels=None):
+        """Extension: the exact `k_gt` nearest among the base vectors that carry the query's label
+        (`labels`: see `query_labeled`); slots beyond their number are (-1, +inf).  `labels=None`
+        is `bf_query`."""
+        if labels is None:
+            return self.bf_query(query, k_gt, measure)
+        t = _as_tensor(query, what="query")
+        ql = _labels(labels, t.shape[0], per="query")
+        loc, dev = _loc(t)
+        lloc, ldev = _loc(ql)
+        on_gpu = self._return_results_on_gpu
+        ids, dists = self._out(t.shape[0], int(k_gt), on_gpu,
+                               self._result_device(t) if on_gpu else None)
+        self._check(lib().ggnn_bf_query_labeled(
+            self._h, t.data_ptr(), t.shape[0], t.shape[1], _dtype_code(t), loc, dev, int(k_gt),
+            int(measure), ids.data_ptr(), dists.data_ptr(), _lib.GPU if on_gpu else _lib.CPU,
+            ql.data_ptr(), lloc, ldev))
+        return ids, dists
+
     def query_filtered(self, query, k_query, tau_query, max_iterations=400,
                        measure=DistanceMeasure.Euclidean, filter=None):
         """Extension: `query` among the base vectors `filter` allows -- a boolean mask of length N
@@ -546,9 +645,25 @@ class GGNN:
 
         `filter_ids`: one row of the filter table (`set_filters`) per query, as in
         `query_filtered_by`; the ids live where the query lives (they are moved there otherwise) and
-        are kept alive with it."""
+        are kept alive with it.  A label per query: `query_async_labeled`."""
+        return self._query_async(query, k_query, tau_query, max_iterations, measure, slot,
+                                 filter_ids, None)
+
+    def query_async_labeled(self, query, k_query, tau_query, max_iterations=400,
+                            measure=DistanceMeasure.Euclidean, slot=0, labels=None):
+        """Extension: `query_async` under label filters (`set_labels`).  `labels`: one label per
+        query, as in `query_labeled`, with the memory and lifetime rules of the `filter_ids` of
+        `query_async` (kept alive on the ticket, `ticket.filter_ids`).  A method of its own, like
+        `query_labeled`: `query_async` keeps its signature.  `labels=None` is `query_async`."""
+        return self._query_async(query, k_query, tau_query, max_iterations, measure, slot, None,
+                                 labels)
+
+    def _query_async(self, query, k_query, tau_query, max_iterations, measure, slot, filter_ids,
+                     labels):
         t = _as_tensor(query, what="query")
         fi = None if filter_ids is None else _filter_ids(filter_ids, t.shape[0])
+        if labels is not None:
+            fi = _labels(labels, t.shape[0], per="query")
         if self._num_gpus > 1 or _lib.get_hook("EXCHANGE") == 1:
             # several GPUs (or the forced RCCL path of the tests): merged [Nq, k] results; host-side tensors are page-locked so that the
             # engine's copies stay asynchronous
@@ -576,7 +691,9 @@ class GGNN:
         if fi is not None:
             if fi.is_cuda:
                 torch.cuda.current_stream(fi.device).synchronize()
-            self._check(lib().ggnn_query_async_filtered_by(
+            call = (lib().ggnn_query_async_labeled if labels is not None
+                    else lib().ggnn_query_async_filtered_by)
+            self._check(call(
                 self._h, t.data_ptr(), t.shape[0], t.shape[1], _dtype_code(t), dev, int(k_query),
                 float(tau_query), int(max_iterations), int(measure), ids.data_ptr(),
                 dists.data_ptr(), int(slot), fi.data_ptr()))

@@ -71,9 +71,60 @@ GGNN_DEV bool bf_row_allowed(const BfArgs& a, uint32_t word, uint32_t i0)
   return true;
 }
 
-template <typename BaseT, int LPR, int NCH, int R, int MODE, bool FILT = false>
+// LAB (label filters, with FILT): the rows whose int32 label equals the label of query n; label -1
+// admits every row.  Kernels of their own (the trailing template argument), so that the bitset
+// kernels keep their code: a read parametrised over both forms costs them registers (DESIGN.md
+// 4.9).  One coalesced dword per row of the batch, issued in front of the rows like the bit words;
+// the shard offset is folded into the wave-uniform pointer and the label addressed as a 32-bit
+// byte offset from it (at most 2^30 rows per scan: kMaxLabeledShardRows, traversal.hpp).
+//   allowed = (label & vmask) == want      label L: vmask ~0u, want L;  label -1: vmask 0, want 0
+struct BfLabelFilter {
+  const uint32_t* labels;  // the column at the first global id of this base
+  uint32_t vmask, want;
+};
+template <bool LAB, class Args>
+GGNN_DEV BfLabelFilter bf_wave_labels(const Args& a, uint32_t n)
+{
+  if constexpr (LAB) {
+    const int32_t L = __builtin_amdgcn_readfirstlane(a.filter_table.query_labels[n]);
+    const uint32_t vmask = (L == -1) ? 0u : ~0u;
+    return BfLabelFilter{a.filter_bits + a.filter_bit_offset, vmask, static_cast<uint32_t>(L) & vmask};
+  }
+  else
+    return BfLabelFilter{nullptr, 0u, 0u};
+}
+GGNN_DEV uint32_t bf_label_word(const BfLabelFilter& f, uint32_t i0, uint32_t end)
+{
+  const uint32_t row = i0 + threadIdx.x;
+  return row < end ? filter_word_at(f.labels, row << 2) : 0u;
+}
+GGNN_DEV bool bf_label_allowed(const BfLabelFilter& f, uint32_t word)
+{
+  return (word & f.vmask) == f.want;
+}
+// the filter word and the verdict of a kernel: the bitset's, or the label's
+template <bool FILT, bool LAB>
+GGNN_DEV uint32_t bf_word(const BfArgs& a, const uint32_t* bits, const BfLabelFilter& f,
+                          uint32_t i0, uint32_t end)
+{
+  if constexpr (LAB)
+    return bf_label_word(f, i0, end);
+  else
+    return bf_filter_word<FILT>(a, bits, i0, end);
+}
+template <bool FILT, bool LAB>
+GGNN_DEV bool bf_allowed(const BfArgs& a, const BfLabelFilter& f, uint32_t word, uint32_t i0)
+{
+  if constexpr (LAB)
+    return bf_label_allowed(f, word);
+  else
+    return bf_row_allowed<FILT>(a, word, i0);
+}
+
+template <typename BaseT, int LPR, int NCH, int R, int MODE, bool FILT = false, bool LAB = false>
 __global__ void __launch_bounds__(kWave) bf_query_kernel(const BfArgsOf<FILT> a)
 {
+  static_assert(FILT || !LAB, "label kernels are filtered kernels");
   constexpr int ROWS = kWave / LPR;
   constexpr int STEPS = StepsOf<LPR, NCH>::value;
   using DE = DistEngine<BaseT, LPR, NCH>;
@@ -109,9 +160,10 @@ __global__ void __launch_bounds__(kWave) bf_query_kernel(const BfArgsOf<FILT> a)
 
   const uint32_t begin = slice * a.rows_per_slice;
   const uint32_t end = min(a.N_base, begin + a.rows_per_slice);
-  const uint32_t* fbits = bf_wave_filter<FILT>(a, n);
+  const uint32_t* fbits = bf_wave_filter<(FILT && !LAB)>(a, n);
+  const BfLabelFilter flab = bf_wave_labels<LAB>(a, n);
   for (uint32_t i0 = begin; i0 < end; i0 += ROWS * STEPS) {
-    const uint32_t fword = bf_filter_word<FILT>(a, fbits, i0, end);
+    const uint32_t fword = bf_word<FILT, LAB>(a, fbits, flab, i0, end);
     Chunk v[STEPS][NCH];
 #pragma unroll
     for (int s = 0; s < STEPS; ++s) {
@@ -140,7 +192,8 @@ __global__ void __launch_bounds__(kWave) bf_query_kernel(const BfArgsOf<FILT> a)
     // visit the batch in base order (bf_query_layer.cu:52-57)
     const uint32_t cnt = min((uint32_t)(ROWS * STEPS), end - i0);
     // a denied row never enters the list
-    const float cd = (lane < (int)cnt && bf_row_allowed<FILT>(a, fword, i0)) ? s_d[lane] : inf_f();
+    const float cd =
+        (lane < (int)cnt && bf_allowed<FILT, LAB>(a, flab, fword, i0)) ? s_d[lane] : inf_f();
     unsigned long long m = __ballot(cd < best.dist_at(a.K - 1));
     while (m) {
       const int j = __ffsll(static_cast<long long>(m)) - 1;
@@ -164,9 +217,10 @@ __global__ void __launch_bounds__(kWave) bf_query_kernel(const BfArgsOf<FILT> a)
 
 // k > 256: the K-best list lives in LDS (dists [K] | ids [K]); stable insertion by a wave-wide
 // shift, rare after the first few thousand rows.
-template <typename BaseT, int LPR, int NCH, int MODE, bool FILT = false>
+template <typename BaseT, int LPR, int NCH, int MODE, bool FILT = false, bool LAB = false>
 __global__ void __launch_bounds__(kWave) bf_query_lds_kernel(const BfArgsOf<FILT> a)
 {
+  static_assert(FILT || !LAB, "label kernels are filtered kernels");
   constexpr int ROWS = kWave / LPR;
   constexpr int STEPS = StepsOf<LPR, NCH>::value;
   using DE = DistEngine<BaseT, LPR, NCH>;
@@ -199,9 +253,10 @@ __global__ void __launch_bounds__(kWave) bf_query_lds_kernel(const BfArgsOf<FILT
 
   const uint32_t begin = slice * a.rows_per_slice;
   const uint32_t end = min(a.N_base, begin + a.rows_per_slice);
-  const uint32_t* fbits = bf_wave_filter<FILT>(a, n);
+  const uint32_t* fbits = bf_wave_filter<(FILT && !LAB)>(a, n);
+  const BfLabelFilter flab = bf_wave_labels<LAB>(a, n);
   for (uint32_t i0 = begin; i0 < end; i0 += ROWS * STEPS) {
-    const uint32_t fword = bf_filter_word<FILT>(a, fbits, i0, end);
+    const uint32_t fword = bf_word<FILT, LAB>(a, fbits, flab, i0, end);
     Chunk v[STEPS][NCH];
 #pragma unroll
     for (int s = 0; s < STEPS; ++s) {
@@ -229,7 +284,8 @@ __global__ void __launch_bounds__(kWave) bf_query_lds_kernel(const BfArgsOf<FILT
     __syncthreads();
     const uint32_t cnt = min((uint32_t)(ROWS * STEPS), end - i0);
     // a denied row never enters the list
-    const float cd = (lane < (int)cnt && bf_row_allowed<FILT>(a, fword, i0)) ? s_d[lane] : inf_f();
+    const float cd =
+        (lane < (int)cnt && bf_allowed<FILT, LAB>(a, flab, fword, i0)) ? s_d[lane] : inf_f();
     unsigned long long m = __ballot(cd < best_d[a.K - 1]);
     while (m) {
       const int j = __ffsll(static_cast<long long>(m)) - 1;
@@ -268,6 +324,22 @@ template <typename BaseT, int LPR, int NCH, int MODE>
 static void launch_bf_r(const BfFilteredArgs& fargs, hipStream_t stream)
 {
   const dim3 grid = grid_for(static_cast<uint64_t>(fargs.Nq) * fargs.slices);
+  if (fargs.filter_bits && fargs.filter_table.query_labels) {
+    const BfFilteredArgs& args = fargs;
+    if (args.K <= 64)
+      hipLaunchKernelGGL((bf_query_kernel<BaseT, LPR, NCH, 1, MODE, true, true>), grid, dim3(kWave),
+                         0, stream, args);
+    else if (args.K <= 128)
+      hipLaunchKernelGGL((bf_query_kernel<BaseT, LPR, NCH, 2, MODE, true, true>), grid, dim3(kWave),
+                         0, stream, args);
+    else if (args.K <= 256)
+      hipLaunchKernelGGL((bf_query_kernel<BaseT, LPR, NCH, 4, MODE, true, true>), grid, dim3(kWave),
+                         0, stream, args);
+    else
+      hipLaunchKernelGGL((bf_query_lds_kernel<BaseT, LPR, NCH, MODE, true, true>), grid,
+                         dim3(kWave), (2 * args.K + 64) * sizeof(int), stream, args);
+    return;
+  }
   if (fargs.filter_bits) {
     const BfFilteredArgs& args = fargs;
     if (args.K <= 64)
@@ -331,6 +403,33 @@ void launch_pack_filters(const uint8_t* masks, uint32_t F, uint64_t N, uint32_t*
   const uint32_t words = static_cast<uint32_t>((N + 31) / 32);
   hipLaunchKernelGGL(pack_filters_kernel, grid_for(static_cast<uint64_t>(F) * chunks), dim3(kWave),
                      0, stream, masks, F, N, chunks, words, words_out);
+  GGNN_HIP_CHECK(hipGetLastError());
+}
+
+// labels[ids[i]] = values[i], one thread per pair.  The engine sends values[i] = the final label of
+// row ids[i], so a repeated id writes one value twice and the result does not depend on the order.
+__global__ void __launch_bounds__(kWave) scatter_labels_kernel(int32_t* labels, uint64_t N,
+                                                               const uint32_t* ids,
+                                                               const int32_t* values, uint64_t count)
+{
+  const uint64_t i =
+      (static_cast<uint64_t>(blockIdx.y) * gridDim.x + blockIdx.x) * kWave + threadIdx.x;
+  if (i >= count)
+    return;
+  const uint32_t row = ids[i];
+  if (row < N)  // (validated on the host; never write outside the column)
+    labels[row] = values[i];
+}
+
+void launch_scatter_labels(int32_t* labels, uint64_t N, const uint32_t* ids, const int32_t* values,
+                           uint64_t count, hipStream_t stream)
+{
+  if (!count)
+    return;
+  GGNN_REQUIRE(labels != nullptr && ids != nullptr && values != nullptr, GGNN_INVALID_ARGUMENT,
+               "scatter_labels: null pointer");
+  hipLaunchKernelGGL(scatter_labels_kernel, grid_for((count + kWave - 1) / kWave), dim3(kWave), 0,
+                     stream, labels, N, ids, values, count);
   GGNN_HIP_CHECK(hipGetLastError());
 }
 
@@ -440,6 +539,11 @@ void launch_bf_query(const BfLaunch& a, hipStream_t stream)
     GGNN_HIP_CHECK(hipMallocAsync(reinterpret_cast<void**>(&tmp_ids), n * sizeof(int32_t), stream));
     GGNN_HIP_CHECK(hipMallocAsync(reinterpret_cast<void**>(&tmp_dists), n * sizeof(float), stream));
   }
+  GGNN_REQUIRE(!a.filter_table.query_labels || (a.filter_bits && !a.filter_table.ids),
+               GGNN_INVALID_ARGUMENT,
+               "query labels need the label column and exclude filter ids");
+  GGNN_REQUIRE(!a.filter_table.query_labels || a.N_base <= kMaxLabeledShardRows, GGNN_UNSUPPORTED,
+               "label filters need at most 2^30 base vectors per scan");
   if (a.filter_bits && a.filter_table.ids) {
     GGNN_REQUIRE(a.filter_table.words != 0 && a.filter_table.num_filters != 0,
                  GGNN_INVALID_ARGUMENT, "filter ids need a filter table");

@@ -131,11 +131,17 @@ extern int g_log_level;
 // result).  ids == nullptr is the per-call form: filter_bits is ONE bitset shared by every query.
 // consts: [2 x words] device words, all ones then all zeros -- what the ids -1 / out of range read;
 // when it is null the launcher makes the two rows in stream-ordered scratch of the launch.
+//
+// Label filters: query_labels != nullptr (ids is then null).  filter_bits of the launch is the
+// label column, one int32 per global base id, and query n with label L = query_labels[n] may be
+// given a base vector iff that vector's label equals L; L == -1 searches unfiltered.  No label
+// value is invalid and none addresses memory: the labels are compared, never used as an index.
 struct FilterTable {
   const int32_t* ids{nullptr};      // [Nq] (device) or null
   const uint32_t* consts{nullptr};  // [2 x words]
   uint32_t words{0};                // words per filter: ceil(bits / 32) over the global ids
   uint32_t num_filters{0};
+  const int32_t* query_labels{nullptr};  // [Nq] (device) or null
 };
 // the two constant rows for a launch that was given none (null if ids is null); free with
 // scratch_free(p, stream) after the launch
@@ -299,6 +305,9 @@ void launch_nn1_stats(const float* nn1, uint32_t N, float* scratch, float* out,
 // [F x N] byte masks (non-zero = allowed) -> [F x ceil(N / 32)] bitset words, padding bits zero
 void launch_pack_filters(const uint8_t* masks, uint32_t F, uint64_t N, uint32_t* words,
                          hipStream_t stream);
+// labels[ids[i]] = values[i] for i < count (device memory; every ids[i] < N)
+void launch_scatter_labels(int32_t* labels, uint64_t N, const uint32_t* ids, const int32_t* values,
+                           uint64_t count, hipStream_t stream);
 void launch_sort_shard_results(uint32_t Nq, uint32_t row_len, int32_t* ids, float* dists,
                                hipStream_t stream);
 void launch_merge_results(uint32_t Nq, uint32_t k, uint32_t num_parts, uint32_t stride,

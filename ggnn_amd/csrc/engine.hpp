@@ -322,6 +322,12 @@ struct DeviceCtx {
   uint64_t filter_table_epoch{0};
   DeviceBuffer filter_ids_stage;
   const int32_t* filter_ids{nullptr};
+  // label filters: this GPU's copy of the handle's label column, int32 [N] over the global ids,
+  // current when labels_epoch equals the handle's.  filter_labeled: the blocking call in progress
+  // is a *_labeled one -- filter_bits is then this column and filter_ids holds the query labels
+  DeviceBuffer labels;
+  uint64_t labels_epoch{0};
+  bool filter_labeled{false};
   std::unique_ptr<SwapState> swap;  // out-of-core shards (null: every shard resident)
   // Result staging of query() / query_async(): grown on demand, kept between calls.  One set per
   // lane: lanes [0, kShardStreams) belong to the asynchronous slots (their streams), lane
@@ -378,6 +384,9 @@ struct DeviceCtx {
     filter_table = std::move(o.filter_table);
     filter_table_epoch = o.filter_table_epoch;
     o.filter_table_epoch = 0;
+    labels = std::move(o.labels);
+    labels_epoch = o.labels_epoch;
+    o.labels_epoch = 0;
     for (int i = 0; i <= kShardStreams; ++i) {
       xb[i].q_stage = std::move(o.xb[i].q_stage);
       xb[i].f_stage = std::move(o.xb[i].f_stage);
@@ -503,7 +512,12 @@ struct ggnn_handle {
     uint64_t count{0};
     ggnn_location loc{GGNN_CPU};
     int gpu{0};
+    bool labeled{false};  // the values are query labels (label filters below), not filter ids
   } active_filter_ids;
+  // label filters.  The label column as ggnn_set_labels copied it, one int32 per base vector on the
+  // host (placed on a GPU when a context exists: place_labels); empty: no labels
+  std::vector<int32_t> labels_host;
+  uint64_t labels_epoch{0};  // counts ggnn_set_labels calls: a context with another value is stale
 
   std::string last_error;
 
@@ -634,9 +648,31 @@ struct ggnn_handle {
   // ctx's copy of the table, placed now if it is missing or stale (synchronous; ctx is active)
   const uint32_t* place_filter_table(DeviceCtx& ctx);
   void place_filter_tables();  // ... on every context there is
-  // filter_table / consts / words / num_filters of a launch on ctx with the id array `ids`
-  FilterTable launch_filter_table(const DeviceCtx& ctx, const int32_t* ids) const;
+  // filter_table / consts / words / num_filters of a launch on ctx with the id array `ids`;
+  // labeled: `ids` are query labels and the launch's filter_bits is the label column
+  FilterTable launch_filter_table(const DeviceCtx& ctx, const int32_t* ids,
+                                  bool labeled = false) const;
   void begin_filter_ids(const int32_t* ids, uint64_t Nq, ggnn_location loc, int gpu);
+
+  // label filters (engine_query.cpp)
+  void set_labels(const int32_t* labels, uint64_t n, ggnn_location loc, int gpu);
+  void update_labels(const int64_t* ids, const int32_t* values, uint64_t count, ggnn_location loc,
+                     int gpu);
+  void drop_labels();
+  // ctx's copy of the label column, placed now if it is missing or stale (synchronous; ctx is
+  // active)
+  const uint32_t* place_labels(DeviceCtx& ctx);
+  void place_labels_everywhere();  // ... on every context there is
+  void begin_query_labels(const int32_t* labels, uint64_t Nq, ggnn_location loc, int gpu);
+  void query_labeled(const void* q, uint64_t Nq, uint32_t D, ggnn_dtype dtype, ggnn_location loc,
+                     int q_gpu, uint32_t k_query, float tau_query, uint32_t max_iterations,
+                     ggnn_measure measure, int32_t* ids_out, float* dists_out,
+                     ggnn_location out_loc, const int32_t* query_labels, ggnn_location labels_loc,
+                     int labels_gpu);
+  void bf_query_labeled(const void* q, uint64_t Nq, uint32_t D, ggnn_dtype dtype,
+                        ggnn_location loc, int q_gpu, uint32_t k_gt, ggnn_measure measure,
+                        int32_t* ids_out, float* dists_out, ggnn_location out_loc,
+                        const int32_t* query_labels, ggnn_location labels_loc, int labels_gpu);
   void query_filtered_by(const void* q, uint64_t Nq, uint32_t D, ggnn_dtype dtype,
                          ggnn_location loc, int q_gpu, uint32_t k_query, float tau_query,
                          uint32_t max_iterations, ggnn_measure measure, int32_t* ids_out,
@@ -676,14 +712,15 @@ struct ggnn_handle {
   void query_async(const void* d_query, uint64_t Nq, uint32_t D, ggnn_dtype dtype,
                    ggnn_location loc, int q_gpu, uint32_t k_query, float tau_query,
                    uint32_t max_iterations, ggnn_measure measure, int32_t* d_ids, float* d_dists,
-                   uint32_t slot, const int32_t* filter_ids = nullptr);
+                   uint32_t slot, const int32_t* filter_ids = nullptr, bool labeled = false);
 
   // filter_bits / filter_ids: the bitset (ids null) or the filter table and the ids of these nq
-  // queries, on ctx's GPU; both null: unfiltered
+  // queries, on ctx's GPU; both null: unfiltered.  labeled: the label column and the query labels
   void enqueue_local_search(DeviceCtx& ctx, int lane, const void* d_query, uint32_t nq,
                             uint32_t k_query, float tau_query, uint32_t max_iterations,
                             ggnn_measure measure, int32_t* d_ids, float* d_dists,
-                            const uint32_t* filter_bits, const int32_t* filter_ids);
+                            const uint32_t* filter_bits, const int32_t* filter_ids,
+                            bool labeled = false);
   void synchronize_slot(uint32_t slot);
   void synchronize();
 

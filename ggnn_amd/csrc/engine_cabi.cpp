@@ -62,6 +62,20 @@ FilterTable seam_filter_table(const uint32_t* filter_table, uint32_t num_filters
   t.num_filters = num_filters;
   return t;
 }
+
+// the label arguments of the *_labeled seam calls as a launch sees them
+FilterTable seam_labels(const int32_t* labels, uint64_t n_labels, const int32_t* query_labels,
+                        uint32_t filter_bit_offset, uint32_t N_base)
+{
+  GGNN_REQUIRE(labels != nullptr, GGNN_INVALID_ARGUMENT, "the label column is null");
+  GGNN_REQUIRE(query_labels != nullptr, GGNN_INVALID_ARGUMENT, "the query label array is null");
+  GGNN_REQUIRE(n_labels >= static_cast<uint64_t>(filter_bit_offset) + N_base &&
+                   n_labels <= 0xffffffffull,
+               GGNN_INVALID_ARGUMENT, "the label column needs filter_bit_offset + N_base entries");
+  FilterTable t{};
+  t.query_labels = query_labels;
+  return t;
+}
 }  // namespace
 
 extern "C" {
@@ -264,6 +278,8 @@ ggnn_status ggnn_set_base(ggnn_t* h, const void* data, uint64_t N, uint32_t D, g
     h->base_dev_copy.release();
     if (h->num_filters)
       h->drop_filters();  // a filter table is over the ids of the base it was set for
+    if (!h->labels_host.empty())
+      h->drop_labels();  // ... and so is a label column
     h->devs.clear();  // a base staged for an earlier bf_query() is stale now
     h->base_src = data;
     h->base_loc = location;
@@ -474,6 +490,76 @@ ggnn_status ggnn_query_async_filtered_by(ggnn_t* h, const void* query, uint64_t 
                  "the filter id array is null");
     h->query_async(query, Nq, D, dtype, gpu_id < 0 ? GGNN_CPU : GGNN_GPU, gpu_id, k_query,
                    tau_query, max_iterations, measure, ids_out, dists_out, slot, filter_ids);
+  });
+}
+
+ggnn_status ggnn_set_labels(ggnn_t* h, const int32_t* labels, uint64_t n, ggnn_location location,
+                            int gpu_id)
+{
+  GGNN_NEED_HANDLE(h);
+  return guarded(h, [&] { h->set_labels(labels, n, location, gpu_id); });
+}
+
+ggnn_status ggnn_update_labels(ggnn_t* h, const int64_t* ids, const int32_t* values,
+                               uint64_t count, ggnn_location location, int gpu_id)
+{
+  GGNN_NEED_HANDLE(h);
+  return guarded(h, [&] { h->update_labels(ids, values, count, location, gpu_id); });
+}
+
+ggnn_status ggnn_get_num_labels(const ggnn_t* h, uint64_t* n)
+{
+  GGNN_NEED_HANDLE(h);
+  if (!n)
+    return GGNN_INVALID_ARGUMENT;
+  *n = h->labels_host.size();
+  return GGNN_OK;
+}
+
+ggnn_status ggnn_query_labeled(ggnn_t* h, const void* query, uint64_t Nq, uint32_t D,
+                               ggnn_dtype dtype, ggnn_location location, int gpu_id,
+                               uint32_t k_query, float tau_query, uint32_t max_iterations,
+                               ggnn_measure measure, int32_t* ids_out, float* dists_out,
+                               ggnn_location out_location, const int32_t* query_labels,
+                               ggnn_location labels_location, int labels_gpu_id)
+{
+  GGNN_NEED_HANDLE(h);
+  return guarded(h, [&] {
+    h->query_labeled(query, Nq, D, dtype, location, gpu_id, k_query, tau_query, max_iterations,
+                     measure, ids_out, dists_out, out_location, query_labels, labels_location,
+                     labels_gpu_id);
+  });
+}
+
+ggnn_status ggnn_bf_query_labeled(ggnn_t* h, const void* query, uint64_t Nq, uint32_t D,
+                                  ggnn_dtype dtype, ggnn_location location, int gpu_id,
+                                  uint32_t k_gt, ggnn_measure measure, int32_t* ids_out,
+                                  float* dists_out, ggnn_location out_location,
+                                  const int32_t* query_labels, ggnn_location labels_location,
+                                  int labels_gpu_id)
+{
+  GGNN_NEED_HANDLE(h);
+  return guarded(h, [&] {
+    h->bf_query_labeled(query, Nq, D, dtype, location, gpu_id, k_gt, measure, ids_out, dists_out,
+                        out_location, query_labels, labels_location, labels_gpu_id);
+  });
+}
+
+ggnn_status ggnn_query_async_labeled(ggnn_t* h, const void* query, uint64_t Nq, uint32_t D,
+                                     ggnn_dtype dtype, int gpu_id, uint32_t k_query,
+                                     float tau_query, uint32_t max_iterations,
+                                     ggnn_measure measure, int32_t* ids_out, float* dists_out,
+                                     uint32_t slot, const int32_t* query_labels)
+{
+  GGNN_NEED_HANDLE(h);
+  return guarded(h, [&] {
+    GGNN_REQUIRE(!h->labels_host.empty(), GGNN_INVALID_STATE,
+                 "There are no labels the query labels could refer to (ggnn_set_labels).");
+    GGNN_REQUIRE(!Nq || query_labels != nullptr, GGNN_INVALID_ARGUMENT,
+                 "the query label array is null");
+    h->query_async(query, Nq, D, dtype, gpu_id < 0 ? GGNN_CPU : GGNN_GPU, gpu_id, k_query,
+                   tau_query, max_iterations, measure, ids_out, dists_out, slot, query_labels,
+                   /*labeled=*/true);
   });
 }
 
@@ -754,6 +840,56 @@ ggnn_status ggnn_op_bf_query_filtered_by(const void* base, ggnn_dtype dtype, uin
     b.filter_table =
         seam_filter_table(filter_table, num_filters, n_bits, filter_ids, filter_bit_offset, N_base);
     b.filter_bits = filter_table;
+    b.filter_bit_offset = filter_bit_offset;
+    launch_bf_query(b, static_cast<hipStream_t>(stream));
+  });
+}
+
+ggnn_status ggnn_op_query_labeled(const void* base, ggnn_dtype dtype, uint32_t N_base, uint32_t D,
+                                  const uint8_t* codes, const float* params, const void* query,
+                                  uint32_t Nq, const int32_t* graph0, uint32_t KBuild,
+                                  const int32_t* start, uint32_t num_start, const float* nn1_stats,
+                                  uint32_t k_query, float tau_query, uint32_t max_iterations,
+                                  ggnn_measure measure, uint32_t shards_per_gpu,
+                                  uint32_t on_gpu_shard, int32_t* ids, float* dists,
+                                  uint32_t* n_dist, uint32_t* n_pop, uint32_t* n_rows,
+                                  const int32_t* labels, uint64_t n_labels,
+                                  const int32_t* query_labels, uint32_t filter_bit_offset,
+                                  void* stream)
+{
+  return guarded(nullptr, [&] {
+    GGNN_REQUIRE(!codes == !params, GGNN_INVALID_ARGUMENT,
+                 "pre-screen codes and params go together");
+    GGNN_REQUIRE(!codes || dtype == GGNN_F32, GGNN_INVALID_ARGUMENT,
+                 "the pre-screen needs a float32 base");
+    QueryLaunch q{base,      query,          dtype,    N_base,         D,         Nq,
+                  graph0,    KBuild,         start,    num_start,      nn1_stats, k_query,
+                  tau_query, max_iterations, measure,  shards_per_gpu, on_gpu_shard, ids,
+                  dists,     n_dist,         n_pop};
+    if (codes) {
+      q.ps_codes = codes;
+      q.ps_params = params;
+      q.ps_Dc = prescreen_code_dim(D);
+    }
+    q.n_rows = n_rows;
+    q.filter_table = seam_labels(labels, n_labels, query_labels, filter_bit_offset, N_base);
+    q.filter_bits = reinterpret_cast<const uint32_t*>(labels);
+    q.filter_bit_offset = filter_bit_offset;
+    launch_query(q, static_cast<hipStream_t>(stream));
+  });
+}
+
+ggnn_status ggnn_op_bf_query_labeled(const void* base, ggnn_dtype dtype, uint32_t N_base,
+                                     uint32_t D, const void* query, uint32_t Nq, uint32_t k_query,
+                                     ggnn_measure measure, int32_t* ids, float* dists,
+                                     const int32_t* labels, uint64_t n_labels,
+                                     const int32_t* query_labels, uint32_t filter_bit_offset,
+                                     void* stream)
+{
+  return guarded(nullptr, [&] {
+    BfLaunch b{base, query, dtype, N_base, D, Nq, k_query, measure, ids, dists};
+    b.filter_table = seam_labels(labels, n_labels, query_labels, filter_bit_offset, N_base);
+    b.filter_bits = reinterpret_cast<const uint32_t*>(labels);
     b.filter_bit_offset = filter_bit_offset;
     launch_bf_query(b, static_cast<hipStream_t>(stream));
   });

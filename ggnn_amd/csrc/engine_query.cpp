@@ -112,7 +112,7 @@ void ggnn_handle::query_device(DeviceCtx& ctx, const void* d_query, uint32_t nq,
     ql.n_rows = c_rows.as<uint32_t>();
     ql.filter_bits = ctx.filter_bits;
     ql.filter_bit_offset = sh.global_id * cfg.N;
-    ql.filter_table = launch_filter_table(ctx, ctx.filter_ids);
+    ql.filter_table = launch_filter_table(ctx, ctx.filter_ids, ctx.filter_labeled);
     if (overlap) {
       launch_query(ql, ctx.shard_stream[si % DeviceCtx::kShardStreams]);
       continue;
@@ -271,7 +271,8 @@ void ggnn_handle::query_split(const void* q, uint32_t nq, uint32_t D, ggnn_dtype
       // (each half sees its own half of the filter ids)
       enqueue_local_search(ctx, lane, qh, count[half], k_query, tau_query, max_iterations,
                            measure, r, reinterpret_cast<float*>(r + part), ctx.filter_bits,
-                           ctx.filter_ids ? ctx.filter_ids + first[half] : nullptr);
+                           ctx.filter_ids ? ctx.filter_ids + first[half] : nullptr,
+                           ctx.filter_labeled);
       GGNN_HIP_CHECK(hipEventRecord(ctx.shard_done[lane], st));
       GGNN_HIP_CHECK(hipStreamWaitEvent(ctx.stream, ctx.shard_done[lane], 0));
     }
@@ -334,12 +335,20 @@ void ggnn_handle::grow_lane(DeviceCtx& owner, int lane, DeviceBuffer& b, size_t 
 void ggnn_handle::query_async(const void* d_query, uint64_t Nq, uint32_t D, ggnn_dtype dtype,
                  ggnn_location loc, int q_gpu, uint32_t k_query, float tau_query,
                  uint32_t max_iterations, ggnn_measure measure, int32_t* d_ids, float* d_dists,
-                 uint32_t slot, const int32_t* filter_ids)
+                 uint32_t slot, const int32_t* filter_ids, bool labeled)
 {
   GGNN_REQUIRE(has_graph(), GGNN_INVALID_STATE, "There is no graph to query.");
   check_query(Nq, D, dtype, d_query);
-  GGNN_REQUIRE(!filter_ids || num_filters, GGNN_INVALID_STATE,
+  GGNN_REQUIRE(!filter_ids || labeled || num_filters, GGNN_INVALID_STATE,
                "There is no filter table the filter ids could refer to (ggnn_set_filters).");
+  GGNN_REQUIRE(!filter_ids || !labeled || !labels_host.empty(), GGNN_INVALID_STATE,
+               "There are no labels the query labels could refer to (ggnn_set_labels).");
+  // the resident table of the ids, or the resident label column of the query labels
+  auto resident = [&](DeviceCtx& ctx) -> const uint32_t* {
+    if (!filter_ids)
+      return nullptr;
+    return labeled ? place_labels(ctx) : place_filter_table(ctx);
+  };
   GGNN_REQUIRE(!Nq || (d_ids != nullptr && d_dists != nullptr), GGNN_INVALID_ARGUMENT,
                "result pointers are null");
   GGNN_REQUIRE(!swapping(), GGNN_UNSUPPORTED,
@@ -370,8 +379,7 @@ void ggnn_handle::query_async(const void* d_query, uint64_t Nq, uint32_t D, ggnn
     ctx.ensure_shard_streams();
     // (filter ids: device memory on this GPU like the query, nothing is staged)
     enqueue_local_search(ctx, lane, d_query, nq, k_query, tau_query, max_iterations, measure,
-                         d_ids, d_dists, filter_ids ? place_filter_table(ctx) : nullptr,
-                         filter_ids);
+                         d_ids, d_dists, resident(ctx), filter_ids, labeled);
     return;
   }
   GGNN_REQUIRE(pad_D == base_D, GGNN_UNSUPPORTED,
@@ -411,8 +419,7 @@ void ggnn_handle::query_async(const void* d_query, uint64_t Nq, uint32_t D, ggnn
     grow_lane(ctx, lane, x.r_pack, 2 * part * 4);
     int32_t* r = x.r_pack.as<int32_t>();
     enqueue_local_search(ctx, lane, q_here, nq, k_query, tau_query, max_iterations, measure, r,
-                         reinterpret_cast<float*>(r + part),
-                         filter_ids ? place_filter_table(ctx) : nullptr, f_here);
+                         reinterpret_cast<float*>(r + part), resident(ctx), f_here, labeled);
   }
   exchange(lane, nq, k_query, row, d_ids, d_dists, /*blocking=*/false);
 }
@@ -421,7 +428,8 @@ void ggnn_handle::query_async(const void* d_query, uint64_t Nq, uint32_t D, ggnn
 void ggnn_handle::enqueue_local_search(DeviceCtx& ctx, int lane, const void* d_query, uint32_t nq,
                           uint32_t k_query, float tau_query, uint32_t max_iterations,
                           ggnn_measure measure, int32_t* d_ids, float* d_dists,
-                          const uint32_t* filter_bits, const int32_t* filter_ids)
+                          const uint32_t* filter_bits, const int32_t* filter_ids,
+                          bool labeled)
 {
   hipStream_t stream = ctx.lane_stream(lane);
   for (uint32_t si = 0; si < shards_per_gpu; ++si) {
@@ -437,7 +445,7 @@ void ggnn_handle::enqueue_local_search(DeviceCtx& ctx, int lane, const void* d_q
     }
     ql.filter_bits = filter_bits;
     ql.filter_bit_offset = sh.global_id * cfg.N;
-    ql.filter_table = launch_filter_table(ctx, filter_ids);
+    ql.filter_table = launch_filter_table(ctx, filter_ids, labeled);
     launch_query(ql, stream);
   }
   if (shards_per_gpu > 1)
@@ -522,7 +530,7 @@ void ggnn_handle::bf_query(const void* q, uint64_t Nq, uint32_t D, ggnn_dtype dt
   BfLaunch bl{bf_base, sq.ptr, base_dtype, static_cast<uint32_t>(base_N), pad_D, nq, k_gt,
               measure,    d_ids,  d_dists,    ctx.bf_rescanned.as<uint32_t>()};
   bl.filter_bits = stage_filter(ctx);
-  bl.filter_table = launch_filter_table(ctx, ctx.filter_ids);
+  bl.filter_table = launch_filter_table(ctx, ctx.filter_ids, ctx.filter_labeled);
   EventTimer timer(ctx.stream, ctx.ev_a, ctx.ev_b);
   launch_bf_query(bl, ctx.stream);
   bf_ms = timer.stop();
@@ -559,14 +567,17 @@ void ggnn_handle::end_filter()
   for (DeviceCtx& ctx : devs) {
     ctx.filter_bits = nullptr;
     ctx.filter_ids = nullptr;
+    ctx.filter_labeled = false;
   }
 }
 
 const uint32_t* ggnn_handle::stage_filter(DeviceCtx& ctx)
 {
   if (const FilterIdSpec& fi = active_filter_ids; fi.ids) {
-    // per-query filters: the resident table, and the id array beside the query
-    const uint32_t* table = place_filter_table(ctx);
+    // per-query filters: the resident table (label filters: the resident label column), and the
+    // id (label) array beside the query
+    const uint32_t* table = fi.labeled ? place_labels(ctx) : place_filter_table(ctx);
+    ctx.filter_labeled = fi.labeled;
     if (fi.loc == GGNN_GPU && fi.gpu == ctx.device && (reinterpret_cast<uintptr_t>(fi.ids) & 3u) == 0)
       ctx.filter_ids = fi.ids;
     else {
@@ -731,11 +742,16 @@ void ggnn_handle::place_filter_tables()
     (void)place_filter_table(ctx);
 }
 
-FilterTable ggnn_handle::launch_filter_table(const DeviceCtx& ctx, const int32_t* ids) const
+FilterTable ggnn_handle::launch_filter_table(const DeviceCtx& ctx, const int32_t* ids,
+                                             bool labeled) const
 {
   FilterTable t{};
   if (!ids)
     return t;
+  if (labeled) {
+    t.query_labels = ids;
+    return t;
+  }
   t.ids = ids;
   t.words = filter_words;
   t.num_filters = num_filters;
@@ -779,6 +795,166 @@ void ggnn_handle::bf_query_filtered_by(const void* q, uint64_t Nq, uint32_t D, g
                                        ggnn_location ids_loc, int ids_gpu)
 {
   begin_filter_ids(filter_ids, Nq, ids_loc, ids_gpu);
+  FilterScope scope{*this};
+  bf_query(q, Nq, D, dtype, loc, q_gpu, k_gt, measure, ids_out, dists_out, out_loc);
+}
+
+// ---- label filters: a resident int32 label per base vector, one label per query ----------------
+void ggnn_handle::drop_labels()
+{
+  synchronize();
+  DeviceRestoreGuard keep;
+  labels_host.clear();
+  labels_host.shrink_to_fit();
+  ++labels_epoch;
+  for (DeviceCtx& ctx : devs) {
+    (void)hipSetDevice(ctx.device);
+    ctx.labels.release();
+    ctx.labels_epoch = 0;
+  }
+}
+
+void ggnn_handle::set_labels(const int32_t* labels, uint64_t n, ggnn_location loc, int gpu)
+{
+  if (!labels) {
+    drop_labels();
+    return;
+  }
+  GGNN_REQUIRE(!base_set || n == base_N, GGNN_INVALID_ARGUMENT,
+               "labels need one entry per base vector (n must equal N)");
+  GGNN_REQUIRE(base_set, GGNN_INVALID_STATE, "There is no base dataset the labels could refer to.");
+  std::vector<int32_t> column(n);
+  if (loc == GGNN_GPU) {
+    GGNN_HIP_CHECK(hipSetDevice(gpu));
+    GGNN_HIP_CHECK(hipMemcpy(column.data(), labels, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+  }
+  else
+    std::copy(labels, labels + n, column.begin());
+  // batches in flight read the old column: drain them before it is freed
+  synchronize();
+  labels_host = std::move(column);
+  ++labels_epoch;
+  try {
+    place_labels_everywhere();
+  }
+  catch (...) {
+    drop_labels();
+    throw;
+  }
+}
+
+void ggnn_handle::update_labels(const int64_t* ids, const int32_t* values, uint64_t count,
+                                ggnn_location loc, int gpu)
+{
+  GGNN_REQUIRE(!labels_host.empty(), GGNN_INVALID_STATE, "There are no labels (ggnn_set_labels).");
+  if (!count)
+    return;
+  GGNN_REQUIRE(ids != nullptr && values != nullptr, GGNN_INVALID_ARGUMENT,
+               "the id or the value array is null");
+  std::vector<int64_t> h_ids(count);
+  std::vector<int32_t> h_values(count);
+  if (loc == GGNN_GPU) {
+    GGNN_HIP_CHECK(hipSetDevice(gpu));
+    GGNN_HIP_CHECK(hipMemcpy(h_ids.data(), ids, count * sizeof(int64_t), hipMemcpyDeviceToHost));
+    GGNN_HIP_CHECK(
+        hipMemcpy(h_values.data(), values, count * sizeof(int32_t), hipMemcpyDeviceToHost));
+  }
+  else {
+    std::copy(ids, ids + count, h_ids.begin());
+    std::copy(values, values + count, h_values.begin());
+  }
+  // validate everything before anything changes
+  const int64_t N = static_cast<int64_t>(labels_host.size());
+  for (uint64_t i = 0; i < count; ++i)
+    GGNN_REQUIRE(h_ids[i] >= 0 && h_ids[i] < N, GGNN_OUT_OF_RANGE,
+                 "label id " + std::to_string(h_ids[i]) + " (pair " + std::to_string(i) +
+                     ") is outside [0, " + std::to_string(N) + ")");
+  // no batch in flight may see a half-relabelled column
+  synchronize();
+  // in order on the host, so the last pair of a repeated id wins; the GPUs are then sent the FINAL
+  // label of every id named, so duplicates write equal values and the scatter is deterministic
+  std::vector<uint32_t> rows(count);
+  for (uint64_t i = 0; i < count; ++i) {
+    rows[i] = static_cast<uint32_t>(h_ids[i]);
+    labels_host[rows[i]] = h_values[i];
+  }
+  for (uint64_t i = 0; i < count; ++i)
+    h_values[i] = labels_host[rows[i]];
+  DeviceRestoreGuard keep;
+  for (DeviceCtx& ctx : devs) {
+    if (ctx.labels_epoch != labels_epoch || !ctx.labels.p)
+      continue;  // (not placed yet: placed whole when it is first needed)
+    ctx.activate();
+    DeviceBuffer d_rows, d_values;
+    d_rows.alloc(count * sizeof(uint32_t));
+    d_values.alloc(count * sizeof(int32_t));
+    GGNN_HIP_CHECK(hipMemcpyAsync(d_rows.p, rows.data(), count * sizeof(uint32_t),
+                                  hipMemcpyHostToDevice, ctx.stream));
+    GGNN_HIP_CHECK(hipMemcpyAsync(d_values.p, h_values.data(), count * sizeof(int32_t),
+                                  hipMemcpyHostToDevice, ctx.stream));
+    launch_scatter_labels(ctx.labels.as<int32_t>(), labels_host.size(), d_rows.as<uint32_t>(),
+                          d_values.as<int32_t>(), count, ctx.stream);
+    GGNN_HIP_CHECK(hipStreamSynchronize(ctx.stream));
+  }
+}
+
+const uint32_t* ggnn_handle::place_labels(DeviceCtx& ctx)
+{
+  GGNN_REQUIRE(!labels_host.empty(), GGNN_INVALID_STATE, "There are no labels (ggnn_set_labels).");
+  if (ctx.labels_epoch == labels_epoch && ctx.labels.p)
+    return ctx.labels.as<uint32_t>();
+  ctx.activate();
+  ctx.labels_epoch = 0;
+  ctx.labels.alloc(labels_host.size() * sizeof(int32_t));
+  GGNN_HIP_CHECK(hipMemcpy(ctx.labels.p, labels_host.data(), labels_host.size() * sizeof(int32_t),
+                           hipMemcpyHostToDevice));
+  GGNN_HIP_CHECK(hipDeviceSynchronize());
+  ctx.labels_epoch = labels_epoch;
+  return ctx.labels.as<uint32_t>();
+}
+
+void ggnn_handle::place_labels_everywhere()
+{
+  if (labels_host.empty())
+    return;
+  DeviceRestoreGuard keep;
+  for (DeviceCtx& ctx : devs)
+    (void)place_labels(ctx);
+}
+
+void ggnn_handle::begin_query_labels(const int32_t* labels, uint64_t Nq, ggnn_location loc, int gpu)
+{
+  GGNN_REQUIRE(!labels_host.empty(), GGNN_INVALID_STATE,
+               "There are no labels the query labels could refer to (ggnn_set_labels).");
+  GGNN_REQUIRE(!Nq || labels != nullptr, GGNN_INVALID_ARGUMENT, "the query label array is null");
+  // (every int32 is a valid label: nothing to validate)
+  active_filter_ids.ids = labels;
+  active_filter_ids.count = Nq;
+  active_filter_ids.loc = loc;
+  active_filter_ids.gpu = gpu;
+  active_filter_ids.labeled = true;
+}
+
+void ggnn_handle::query_labeled(const void* q, uint64_t Nq, uint32_t D, ggnn_dtype dtype,
+                                ggnn_location loc, int q_gpu, uint32_t k_query, float tau_query,
+                                uint32_t max_iterations, ggnn_measure measure, int32_t* ids_out,
+                                float* dists_out, ggnn_location out_loc,
+                                const int32_t* query_labels, ggnn_location labels_loc,
+                                int labels_gpu)
+{
+  begin_query_labels(query_labels, Nq, labels_loc, labels_gpu);
+  FilterScope scope{*this};
+  query(q, Nq, D, dtype, loc, q_gpu, k_query, tau_query, max_iterations, measure, ids_out,
+        dists_out, out_loc);
+}
+
+void ggnn_handle::bf_query_labeled(const void* q, uint64_t Nq, uint32_t D, ggnn_dtype dtype,
+                                   ggnn_location loc, int q_gpu, uint32_t k_gt,
+                                   ggnn_measure measure, int32_t* ids_out, float* dists_out,
+                                   ggnn_location out_loc, const int32_t* query_labels,
+                                   ggnn_location labels_loc, int labels_gpu)
+{
+  begin_query_labels(query_labels, Nq, labels_loc, labels_gpu);
   FilterScope scope{*this};
   bf_query(q, Nq, D, dtype, loc, q_gpu, k_gt, measure, ids_out, dists_out, out_loc);
 }

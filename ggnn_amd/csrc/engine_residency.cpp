@@ -166,6 +166,7 @@ void ggnn_handle::prepare(uint32_t KBuild)
         setup_swap(ctx, slots, base_here);
     }
     place_filter_tables();  // a filter table set earlier follows the handle to its (new) GPUs
+    place_labels_everywhere();  // ... and so does a label column
   }
   catch (...) {
     rollback_graph();

@@ -15,12 +15,41 @@
 //     scan: everything else (KBuild > 24, long rings, wide rows, hook QUERY_EARLY = 0).
 // There is no ring-less / tag-set form: QUERY_GLOBAL_RING and VIS_TAG_SET do nothing here.
 // The float16 / bfloat16 kernels are instantiated by query_filtered_16.hip.
+//
+// Label filters (GGNN_LABELS_TU: query_labeled.hip, query_labeled_16.hip): this file once more with
+// LabelFilter in place of IdFilter, under kernel and launcher names of their own.  The bitset
+// kernels above are not touched by it.
 #include <algorithm>
 
 #include "traversal.hpp"
 #include "query_args.hpp"
 
+#ifdef GGNN_LABELS_TU
+#define query_filtered_kernel query_labeled_kernel
+#define query_filtered_kernel_lds query_labeled_kernel_lds
+#define launch_query_filtered_16 launch_query_labeled_16
+#endif
+
 namespace ggnn_amd {
+
+// the filter of the wave of query n
+namespace {
+#ifdef GGNN_LABELS_TU
+using WaveIdFilter = LabelFilter;
+GGNN_DEV WaveIdFilter wave_id_filter(const FilteredQueryArgs& a, const uint32_t n)
+{
+  return LabelFilter(a.filter_bits, a.filter_bit_offset, a.filter_table, n);
+}
+#else
+using WaveIdFilter = IdFilter;
+// this wave's bitset: the call's, or the row of the table its query's filter id names
+GGNN_DEV WaveIdFilter wave_id_filter(const FilteredQueryArgs& a, const uint32_t n)
+{
+  return IdFilter{wave_filter_bits(a.filter_bits, a.filter_table, n), a.filter_bit_offset, kEmptyKey,
+                  0u};
+}
+#endif
+}  // namespace
 
 template <class PSC, typename BaseT>
 GGNN_DEV void load_prescreen_filtered(PSC& ps, const QueryArgs& a, const BaseT* qrow)
@@ -68,9 +97,7 @@ query_filtered_kernel(const FilteredQueryArgs a)
 
   SortedList<R, HB> sl;
   sl.init(a.KQuery, a.sorted, a.cache, xi, lds.known, static_cast<int>(a.vis_slots));
-  // this wave's bitset: the call's, or the row of the table its query's filter id names
-  IdFilter idf{wave_filter_bits(a.filter_bits, a.filter_table, n), a.filter_bit_offset, kEmptyKey,
-               0u};
+  WaveIdFilter idf = wave_id_filter(a, n);
 
   uint32_t cnt_dist = 0, cnt_pop = 0;
   uint2 cnt_rows = make_uint2(0u, 0u);
@@ -195,9 +222,7 @@ __global__ void __launch_bounds__(kWave) query_filtered_kernel_lds(const Filtere
   load_prescreen_filtered(ps, a, query + static_cast<size_t>(n) * a.D);
   LdsList sl;
   sl.init(a.KQuery, a.sorted, a.cache, xi, keys, dists);
-  // this wave's bitset: the call's, or the row of the table its query's filter id names
-  IdFilter idf{wave_filter_bits(a.filter_bits, a.filter_table, n), a.filter_bit_offset, kEmptyKey,
-               0u};
+  WaveIdFilter idf = wave_id_filter(a, n);
   uint32_t cnt_dist = 0, cnt_pop = 0;
   uint2 cnt_rows = make_uint2(0u, 0u);
   for (uint32_t i = 0; i < a.num_start; i += kKBlock) {
@@ -313,6 +338,30 @@ static void launch_query_filtered_cfg(const FilteredQueryArgs& args, bool use_ps
 void launch_query_filtered_16(const FilteredQueryArgs& args, ggnn_measure measure, ggnn_dtype dtype,
                               hipStream_t stream);
 
+#ifdef GGNN_LABELS_TU
+// base: filled by launch_query (query.hip), filter_bits = the label column; table: query_labels set
+void launch_query_labeled(const QueryArgs& base, const FilterTable& table, bool use_ps,
+                          ggnn_measure measure, ggnn_dtype dtype, hipStream_t stream)
+{
+  GGNN_REQUIRE(table.query_labels != nullptr && !table.ids, GGNN_INVALID_ARGUMENT,
+               "query labels are missing, or given together with filter ids");
+  GGNN_REQUIRE(base.N_base <= kMaxLabeledShardRows, GGNN_UNSUPPORTED,
+               "label filters need shards of at most 2^30 base vectors");
+  FilteredQueryArgs args{};
+  static_cast<QueryArgs&>(args) = base;
+  args.filter_table = table;
+  if (dtype_is_16bit(dtype)) {
+    launch_query_filtered_16(args, measure, dtype, stream);
+    return;
+  }
+#define GGNN_LAUNCH_QF(T, LPR, NCH) launch_query_filtered_cfg<T, LPR, NCH>(args, use_ps, measure, stream)
+  GGNN_DISPATCH_DIST_32_8(dtype, args.D, GGNN_LAUNCH_QF);
+#undef GGNN_LAUNCH_QF
+}
+#else
+void launch_query_labeled(const QueryArgs& base, const FilterTable& table, bool use_ps,
+                          ggnn_measure measure, ggnn_dtype dtype, hipStream_t stream);
+
 // the all-ones / all-zero rows of a launch with filter ids that brings none (operator seam; the
 // engine keeps them behind its resident table)
 uint32_t* filter_consts_scratch(const FilterTable& t, hipStream_t stream)
@@ -336,6 +385,10 @@ void launch_query_filtered(const QueryArgs& base, const FilterTable& table, bool
   if (table.ids)
     GGNN_REQUIRE(table.words != 0 && table.num_filters != 0, GGNN_INVALID_ARGUMENT,
                  "filter ids need a filter table");
+  if (table.query_labels) {  // label filters: kernels of their own (query_labeled.hip)
+    launch_query_labeled(base, table, use_ps, measure, dtype, stream);
+    return;
+  }
   struct ConstGuard {
     void* p;
     hipStream_t s;
@@ -355,6 +408,7 @@ void launch_query_filtered(const QueryArgs& base, const FilterTable& table, bool
   GGNN_DISPATCH_DIST_32_8(dtype, args.D, GGNN_LAUNCH_QF);
 #undef GGNN_LAUNCH_QF
 }
+#endif
 #else
 void launch_query_filtered_16(const FilteredQueryArgs& args, ggnn_measure measure, ggnn_dtype dtype,
                               hipStream_t stream)

@@ -1663,11 +1663,60 @@ GGNN_DEV const uint32_t* wave_filter_bits(const uint32_t* table, const FilterTab
   return t.consts + (f == -1 ? 0u : t.words);
 }
 
+// Label filters: one int32 label per base vector, one per query; a candidate is denied iff its
+// label differs from the query's (FilterTable, common.hpp).  The class has the interface of IdFilter
+// -- the same one-dword gather per lane in front of the first-read rows, the verdict at the replay
+// -- and is a class of its own, instantiated in translation units of their own (query_labeled.hip,
+// query_labeled_16.hip), because a filter read parametrised over both forms costs registers in the
+// bitset kernels: those stay instruction for instruction what they were.
+//   word   = labels[id + offset]
+//   denied = (word & vmask) != want        label L: vmask ~0u, want L;  label -1: vmask 0, want 0
+// The shard offset is folded into the wave-uniform pointer and the word is addressed as a 32-bit
+// BYTE offset from it (scalar base + lane offset, the form of the bitset gather; a 64-bit index
+// would cost an address register pair per lane): a shard holds at most 2^30 vectors under labels
+// (kMaxLabeledShardRows, checked by the launchers).  Label -1 still reads its in-bounds word.
+constexpr uint32_t kMaxLabeledShardRows = 1u << 30;
+GGNN_DEV uint32_t filter_word_at(const void* words, const uint32_t byte_offset)
+{
+  return *reinterpret_cast<const uint32_t*>(static_cast<const char*>(words) + byte_offset);
+}
+struct LabelFilter {
+  static constexpr bool enabled = true;
+  const int32_t* labels;  // the column at the shard's first global id
+  uint32_t vmask, want;
+  int key;        // the candidate this lane asked for (or EMPTY)
+  uint32_t word;  // its label
+  // the filter of the wave of query n (scalar: the query number is wave-uniform)
+  GGNN_DEV LabelFilter(const uint32_t* column, const uint32_t offset, const FilterTable& t,
+                       const uint32_t n)
+      : labels(reinterpret_cast<const int32_t*>(column) + offset), key(kEmptyKey), word(0u)
+  {
+    const int32_t L = __builtin_amdgcn_readfirstlane(t.query_labels[n]);
+    vmask = (L == -1) ? 0u : ~0u;
+    want = static_cast<uint32_t>(L) & vmask;
+  }
+  GGNN_DEV void request(const int cand)
+  {
+    key = cand;
+    // EMPTY slots read the label of the shard's first id (verdict ignored)
+    word = filter_word_at(labels, static_cast<uint32_t>(max(cand, 0)) << 2);
+  }
+  // lanes whose candidate is denied
+  GGNN_DEV unsigned long long denied_lanes() const
+  {
+    return __ballot(key != kEmptyKey && (word & vmask) != want);
+  }
+  GGNN_DEV bool denied(const unsigned long long dl, const int k) const
+  {
+    return (__ballot(key == k) & dl) != 0ull;
+  }
+};
+
 // the replay of a fetch (simple_knn_cache.cuh:268-286) under a filter: as replay_lanes() below,
 // a denied candidate is pushed with the flag
-template <class SL>
+template <class SL, class IDF>
 GGNN_DEV void replay_lanes_filtered(SL& sl, unsigned long long m, const int k_of, const float d_of,
-                                    const IdFilter& filt)
+                                    const IDF& filt)
 {
   const unsigned long long dl = filt.denied_lanes();
   while (m) {

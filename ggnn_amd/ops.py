@@ -261,6 +261,61 @@ def bf_query_filtered_by(base, query, k_query, filter_table, filter_ids, measure
     return ids, dists
 
 
+def _need_labels(labels, query_labels, Nq, n_min):
+    _need(labels, torch.int32, "labels"), _need(query_labels, torch.int32, "query_labels")
+    if labels.dim() != 1 or labels.numel() < n_min:
+        raise ValueError("labels must be 1-dimensional with at least bit_offset + N entries")
+    if query_labels.dim() != 1 or query_labels.numel() != Nq:
+        raise ValueError("query_labels must be 1-dimensional with one entry per query")
+
+
+def query_labeled(base, query, graph0, start, nn1_stats, k_query, tau_query, labels,
+                  query_labels, max_iterations=400, measure=EUCLIDEAN, bit_offset=0,
+                  shards_per_gpu=1, on_gpu_shard=0, counters=False, prescreen=None,
+                  rows_read=None):
+    """`query_filtered` under label filters: labels is the int32 label column over the global ids
+    (local id i has labels[i + bit_offset]), query n may be given the rows whose label equals
+    query_labels[n] (int32 CUDA tensor); label -1 searches unfiltered."""
+    _need(base, name="base"), _need(query, base.dtype, "query")
+    _need(graph0, torch.int32, "graph0"), _need(start, torch.int32, "start")
+    _need(nn1_stats, torch.float32, "nn1_stats")
+    Nq = query.shape[0]
+    _need_labels(labels, query_labels, Nq, bit_offset + base.shape[0])
+    ids = torch.empty((Nq, k_query * shards_per_gpu), dtype=torch.int32, device=base.device)
+    dists = torch.empty((Nq, k_query * shards_per_gpu), dtype=torch.float32, device=base.device)
+    nd = npop = None
+    if counters:
+        nd = torch.zeros(Nq, dtype=torch.int32, device=base.device)
+        npop = torch.zeros(Nq, dtype=torch.int32, device=base.device)
+    codes, params = prescreen if prescreen is not None else (None, None)
+    if prescreen is not None:
+        _need(base, torch.float32, "base"), _need(codes, torch.uint8, "codes")
+        _need(params, torch.float32, "params")
+    check(lib().ggnn_op_query_labeled(
+        _ptr(base), _dtype_code(base), base.shape[0], base.shape[1], _ptr(codes), _ptr(params),
+        _ptr(query), Nq, _ptr(graph0), graph0.shape[1], _ptr(start), start.numel(),
+        _ptr(nn1_stats), k_query, tau_query, max_iterations, measure, shards_per_gpu,
+        on_gpu_shard, _ptr(ids), _ptr(dists), _ptr(nd), _ptr(npop), _ptr(rows_read),
+        _ptr(labels), labels.numel(), _ptr(query_labels), bit_offset, _stream()))
+    if counters:
+        return ids, dists, nd, npop
+    return ids, dists
+
+
+def bf_query_labeled(base, query, k_query, labels, query_labels, measure=EUCLIDEAN, bit_offset=0):
+    """`bf_query_filtered` under label filters (see query_labeled)"""
+    _need(base, name="base"), _need(query, base.dtype, "query")
+    Nq = query.shape[0]
+    _need_labels(labels, query_labels, Nq, bit_offset + base.shape[0])
+    ids = torch.empty((Nq, k_query), dtype=torch.int32, device=base.device)
+    dists = torch.empty((Nq, k_query), dtype=torch.float32, device=base.device)
+    check(lib().ggnn_op_bf_query_labeled(
+        _ptr(base), _dtype_code(base), base.shape[0], base.shape[1], _ptr(query), Nq, k_query,
+        measure, _ptr(ids), _ptr(dists), _ptr(labels), labels.numel(), _ptr(query_labels),
+        bit_offset, _stream()))
+    return ids, dists
+
+
 def pack_filters(masks):
     """[F, N] boolean CUDA masks -> [F, ceil(N / 32)] int32 bitset words on the same GPU (bit
     i & 31 of word i >> 5 is mask i; padding bits zero)"""

@@ -212,6 +212,53 @@ ggnn_status ggnn_query_async_filtered_by(ggnn_t* h, const void* query, uint64_t 
                                          ggnn_measure measure, int32_t* ids_out, float* dists_out,
                                          uint32_t slot, const int32_t* filter_ids);
 
+/* Label filters: one int32 label per base vector and one int32 label per query.
+ * For many categories (tenants) the filter table above costs num_filters * N / 8 bytes per GPU; a
+ * label column costs 4 * N bytes whatever the number of categories.  A base vector may be reported
+ * to a query iff their labels are EQUAL.  Query n with label L gives, bit for bit (ids, distances,
+ * counters), the result of ggnn_query_filtered / ggnn_bf_query_filtered of that query with the
+ * bitset (labels == L); label -1 searches unfiltered (ggnn_query / ggnn_bf_query), whatever the
+ * base labels are.  There is no invalid label value: a label that no row carries gives an empty
+ * result, every slot (-1 + id offset, +inf).  Labels are int32 only and a query selects by
+ * equality only.
+ *
+ * ggnn_set_labels COPIES labels[n] (int32 over the global base ids, from the host or from GPU
+ * gpu_id; n must equal the base's N: GGNN_INVALID_ARGUMENT otherwise, GGNN_INVALID_STATE before
+ * ggnn_set_base): the engine keeps the column on the host and places it on every GPU of the handle
+ * as soon as those are known -- again after ggnn_build / ggnn_load / ggnn_set_gpus, and on first
+ * use by a ggnn_bf_query_labeled without a graph -- 4 * N bytes per GPU; GGNN_OUT_OF_MEMORY if
+ * that cannot be allocated.  A null pointer drops the labels, and so does ggnn_set_base.
+ * ggnn_update_labels relabels `count` rows: labels[ids[i]] = values[i], applied in order (the last
+ * pair of a repeated id wins).  An id outside [0, N) is GGNN_OUT_OF_RANGE and nothing is changed;
+ * GGNN_INVALID_STATE when no labels are set.  Both calls SYNCHRONISE: they first wait for every
+ * asynchronous slot.  ggnn_get_num_labels gives N, or 0 when no labels are set.
+ *
+ * The *_labeled calls are the *_filtered_by calls with query_labels[Nq] in place of filter_ids --
+ * the same memory rules, nothing is validated because every value is valid -- and
+ * GGNN_INVALID_STATE without labels.  Labels and a bitset cannot be combined in one call. */
+ggnn_status ggnn_set_labels(ggnn_t* h, const int32_t* labels, uint64_t n, ggnn_location location,
+                            int gpu_id);
+ggnn_status ggnn_update_labels(ggnn_t* h, const int64_t* ids, const int32_t* values,
+                               uint64_t count, ggnn_location location, int gpu_id);
+ggnn_status ggnn_get_num_labels(const ggnn_t* h, uint64_t* n);
+ggnn_status ggnn_query_labeled(ggnn_t* h, const void* query, uint64_t Nq, uint32_t D,
+                               ggnn_dtype dtype, ggnn_location location, int gpu_id,
+                               uint32_t k_query, float tau_query, uint32_t max_iterations,
+                               ggnn_measure measure, int32_t* ids_out, float* dists_out,
+                               ggnn_location out_location, const int32_t* query_labels,
+                               ggnn_location labels_location, int labels_gpu_id);
+ggnn_status ggnn_bf_query_labeled(ggnn_t* h, const void* query, uint64_t Nq, uint32_t D,
+                                  ggnn_dtype dtype, ggnn_location location, int gpu_id,
+                                  uint32_t k_gt, ggnn_measure measure, int32_t* ids_out,
+                                  float* dists_out, ggnn_location out_location,
+                                  const int32_t* query_labels, ggnn_location labels_location,
+                                  int labels_gpu_id);
+ggnn_status ggnn_query_async_labeled(ggnn_t* h, const void* query, uint64_t Nq, uint32_t D,
+                                     ggnn_dtype dtype, int gpu_id, uint32_t k_query,
+                                     float tau_query, uint32_t max_iterations,
+                                     ggnn_measure measure, int32_t* ids_out, float* dists_out,
+                                     uint32_t slot, const int32_t* query_labels);
+
 /* layout of one graph shard, include/ggnn/base/graph_config.h:31-112 */
 typedef struct {
   uint32_t N, D, KBuild;
@@ -485,6 +532,27 @@ ggnn_status ggnn_op_bf_query_filtered_by(const void* base, ggnn_dtype dtype, uin
                                          uint32_t num_filters, uint64_t n_bits,
                                          const int32_t* filter_ids, uint32_t filter_bit_offset,
                                          void* stream);
+/* ggnn_op_query_filtered / ggnn_op_bf_query_filtered with a label column and one label per query
+ * (all device memory): labels is int32 [n_labels], n_labels >= filter_bit_offset + N_base, local
+ * id i has the label labels[i + filter_bit_offset]; query n may be given the rows whose label
+ * equals query_labels[n], -1 = unfiltered. */
+ggnn_status ggnn_op_query_labeled(const void* base, ggnn_dtype dtype, uint32_t N_base, uint32_t D,
+                                  const uint8_t* codes, const float* params, const void* query,
+                                  uint32_t Nq, const int32_t* graph0, uint32_t KBuild,
+                                  const int32_t* start, uint32_t num_start, const float* nn1_stats,
+                                  uint32_t k_query, float tau_query, uint32_t max_iterations,
+                                  ggnn_measure measure, uint32_t shards_per_gpu,
+                                  uint32_t on_gpu_shard, int32_t* ids, float* dists,
+                                  uint32_t* n_dist, uint32_t* n_pop, uint32_t* n_rows,
+                                  const int32_t* labels, uint64_t n_labels,
+                                  const int32_t* query_labels, uint32_t filter_bit_offset,
+                                  void* stream);
+ggnn_status ggnn_op_bf_query_labeled(const void* base, ggnn_dtype dtype, uint32_t N_base,
+                                     uint32_t D, const void* query, uint32_t Nq, uint32_t k_query,
+                                     ggnn_measure measure, int32_t* ids, float* dists,
+                                     const int32_t* labels, uint64_t n_labels,
+                                     const int32_t* query_labels, uint32_t filter_bit_offset,
+                                     void* stream);
 /* [num_filters x N] byte masks (non-zero: allowed) -> [num_filters x ceil(N / 32)] bitset words,
  * padding bits zero; both in device memory.  A table made from a label column on the GPU needs
  * no host round trip. */

@@ -20,7 +20,15 @@ Per-query filters (a resident filter table, one filter id per query), every repe
     synchronised, queries and ids on the GPU), recall@10 against bf_query_filtered(filter_ids=...),
     bytes staged per batch;
   * "locality": kernel ms of a mixed batch over --tenants and over --big-table random rows of
-    equal density (1 / tenants), so that only the table's footprint changes."""
+    equal density (1 / tenants), so that only the table's footprint changes.
+
+    python scripts/filtered_bench.py --labels [--label-tenants 16 1024]
+
+Label filters (one int32 label per base vector, one per query) against the filter table of the
+same tenants on the same handle and graph; per tenant count T: T disjoint tenants of N / T rows,
+query labels drawn uniformly.  Kernel ms of the mixed batch through `query_labeled` and through a
+T-row table (`query_filtered_by`), alternating, every repeat listed; recall@10 of the labelled
+call against `bf_query_labeled`; resident bytes per GPU of both forms."""
 import argparse
 import json
 import os
@@ -45,6 +53,8 @@ def main():
     ap.add_argument("--mixed", action="store_true")
     ap.add_argument("--tenants", type=int, default=16)
     ap.add_argument("--big-table", type=int, default=1024)
+    ap.add_argument("--labels", action="store_true")
+    ap.add_argument("--label-tenants", type=int, nargs="+", default=[16, 1024])
     a = ap.parse_args()
     rs = np.random.default_rng(1)
     centres = rs.normal(size=(256, a.d)).astype(np.float32) * 2
@@ -56,6 +66,9 @@ def main():
     q = torch.from_numpy(query).cuda()
     if a.mixed:
         mixed(a, g, q)
+        return
+    if a.labels:
+        labeled(a, g, q)
         return
 
     def timed(fn):
@@ -194,6 +207,41 @@ def mixed(a, g, q):
         print(json.dumps({"locality": rows_f, "table_mb": round(rows_f * words * 4 / 2 ** 20, 2),
                           "kernel_ms": [round(kernel_ms(call), 4) for _ in range(a.reps)]}),
               flush=True)
+
+
+def labeled(a, g, q):
+    words = (a.n + 31) // 32
+    for T in a.label_tenants:
+        rs = np.random.default_rng(T)
+        tenant = torch.from_numpy((rs.permutation(a.n) % T).astype(np.int32)).cuda()
+        qlab = torch.from_numpy(rs.integers(0, T, a.queries).astype(np.int32)).cuda()
+        g.set_labels(tenant)
+        table = torch.empty((T, words), dtype=torch.int32, device="cuda")
+        for r0 in range(0, T, 64):                            # [64, N] masks at a time
+            rows = torch.arange(r0, min(T, r0 + 64), device="cuda", dtype=torch.int32)
+            table[r0:r0 + len(rows)] = ggnn.pack_filters(tenant[None, :] == rows[:, None])
+        g.set_filters(table)
+        by_label = lambda: g.query_labeled(q, a.k, a.tau, a.iters, labels=qlab)  # noqa: E731
+        by_table = lambda: g.query_filtered_by(q, a.k, a.tau, a.iters, filter_ids=qlab)  # noqa: E731
+        x, y = by_label(), by_table()
+        assert torch.equal(x[0], y[0]) and torch.equal(x[1], y[1])
+        ms = {"labels": [], "table": []}
+        for _ in range(a.reps):                               # alternating
+            by_label()
+            ms["labels"].append(round(g.last_timing_ms()["query_ms"], 4))
+            by_table()
+            ms["table"].append(round(g.last_timing_ms()["query_ms"], 4))
+        gt, _ = g.bf_query_labeled(q, a.k, labels=qlab)
+        bf_ms = g.last_timing_ms()["bf_query_ms"]
+        ids, gt = x[0].cpu().numpy(), gt.cpu().numpy()
+        rec = float(np.mean([len(set(u[u >= 0].tolist()) & set(v[v >= 0].tolist())) /
+                             max(1, int((v >= 0).sum())) for u, v in zip(ids, gt)]))
+        print(json.dumps({"labels": T, "kernel_ms": ms, "recall": round(rec, 4),
+                          "bf_labeled_ms": round(bf_ms, 3),
+                          "resident_bytes": {"labels": 4 * a.n, "table": (T + 2) * words * 4}}),
+              flush=True)
+        g.set_filters(None)
+        g.set_labels(None)
 
 
 if __name__ == "__main__":
