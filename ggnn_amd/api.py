@@ -420,19 +420,34 @@ class GGNN:
             return torch.device("cuda", view.gpu_id)
         return torch.device("cuda", torch.cuda.current_device())
 
+    def _blocking(self, call, t, params, tail=(), shards=1):
+        """one blocking call of the C-ABI: query tensor `t`, its location, the result tensors, then
+        `call` with the search parameters `params` (k first) and the filter arguments `tail`.
+        `shards`: rows per query that results kept on the GPU have (a graph search: one per shard)"""
+        loc, dev = _loc(t)
+        on_gpu = self._return_results_on_gpu
+        width = params[0] * (shards if on_gpu else 1)
+        ids, dists = self._out(t.shape[0], width, on_gpu, self._result_device(t) if on_gpu else None)
+        self._check(call(self._h, t.data_ptr(), t.shape[0], t.shape[1], _dtype_code(t), loc, dev,
+                         *params, ids.data_ptr(), dists.data_ptr(),
+                         _lib.GPU if on_gpu else _lib.CPU, *tail))
+        return ids, dists
+
+    @staticmethod
+    def _search(k_query, tau_query, max_iterations, measure):
+        return int(k_query), float(tau_query), int(max_iterations), int(measure)
+
+    @staticmethod
+    def _where(x):
+        """a filter tensor as the C-ABI takes it: pointer, location, GPU"""
+        return (x.data_ptr(), *_loc(x))
+
     def query(self, query, k_query, tau_query, max_iterations=400,
               measure=DistanceMeasure.Euclidean):
         """Run a query and return indices and distances."""
-        t = _as_tensor(query, what="query")
-        loc, dev = _loc(t)
-        on_gpu = self._return_results_on_gpu
-        width = int(k_query) * (self._shards if on_gpu else 1)
-        ids, dists = self._out(t.shape[0], width, on_gpu, self._result_device(t) if on_gpu else None)
-        self._check(lib().ggnn_query(self._h, t.data_ptr(), t.shape[0], t.shape[1],
-                                     _dtype_code(t), loc, dev, int(k_query), float(tau_query),
-                                     int(max_iterations), int(measure), ids.data_ptr(),
-                                     dists.data_ptr(), _lib.GPU if on_gpu else _lib.CPU))
-        return ids, dists
+        return self._blocking(lib().ggnn_query, _as_tensor(query, what="query"),
+                              self._search(k_query, tau_query, max_iterations, measure),
+                              shards=self._shards)
 
     @property
     def _N(self):
@@ -518,16 +533,9 @@ class GGNN:
             return self.query(query, k_query, tau_query, max_iterations, measure)
         t = _as_tensor(query, what="query")
         ql = _labels(labels, t.shape[0], per="query")
-        loc, dev = _loc(t)
-        lloc, ldev = _loc(ql)
-        on_gpu = self._return_results_on_gpu
-        width = int(k_query) * (self._shards if on_gpu else 1)
-        ids, dists = self._out(t.shape[0], width, on_gpu, self._result_device(t) if on_gpu else None)
-        self._check(lib().ggnn_query_labeled(
-            self._h, t.data_ptr(), t.shape[0], t.shape[1], _dtype_code(t), loc, dev, int(k_query),
-            float(tau_query), int(max_iterations), int(measure), ids.data_ptr(), dists.data_ptr(),
-            _lib.GPU if on_gpu else _lib.CPU, ql.data_ptr(), lloc, ldev))
-        return ids, dists
+        return self._blocking(lib().ggnn_query_labeled, t,
+                              self._search(k_query, tau_query, max_iterations, measure),
+                              self._where(ql), self._shards)
 
     def bf_query_labeled(self, query, k_gt=100, measure=DistanceMeasure.Euclidean, labels=None):
         """Extension: the exact `k_gt` nearest among the base vectors that carry the query's label
@@ -537,16 +545,8 @@ class GGNN:
             return self.bf_query(query, k_gt, measure)
         t = _as_tensor(query, what="query")
         ql = _labels(labels, t.shape[0], per="query")
-        loc, dev = _loc(t)
-        lloc, ldev = _loc(ql)
-        on_gpu = self._return_results_on_gpu
-        ids, dists = self._out(t.shape[0], int(k_gt), on_gpu,
-                               self._result_device(t) if on_gpu else None)
-        self._check(lib().ggnn_bf_query_labeled(
-            self._h, t.data_ptr(), t.shape[0], t.shape[1], _dtype_code(t), loc, dev, int(k_gt),
-            int(measure), ids.data_ptr(), dists.data_ptr(), _lib.GPU if on_gpu else _lib.CPU,
-            ql.data_ptr(), lloc, ldev))
-        return ids, dists
+        return self._blocking(lib().ggnn_bf_query_labeled, t, (int(k_gt), int(measure)),
+                              self._where(ql))
 
     def query_filtered(self, query, k_query, tau_query, max_iterations=400,
                        measure=DistanceMeasure.Euclidean, filter=None):
@@ -570,28 +570,15 @@ class GGNN:
         if filter is None and filter_ids is None:
             return self.query(query, k_query, tau_query, max_iterations, measure)
         t = _as_tensor(query, what="query")
-        N = self._N
-        loc, dev = _loc(t)
-        on_gpu = self._return_results_on_gpu
-        width = int(k_query) * (self._shards if on_gpu else 1)
+        params = self._search(k_query, tau_query, max_iterations, measure)
         if filter_ids is not None:
             fi = _filter_ids(filter_ids, t.shape[0])
-            iloc, idev = _loc(fi)
-            ids, dists = self._out(t.shape[0], width, on_gpu,
-                                   self._result_device(t) if on_gpu else None)
-            self._check(lib().ggnn_query_filtered_by(
-                self._h, t.data_ptr(), t.shape[0], t.shape[1], _dtype_code(t), loc, dev,
-                int(k_query), float(tau_query), int(max_iterations), int(measure), ids.data_ptr(),
-                dists.data_ptr(), _lib.GPU if on_gpu else _lib.CPU, fi.data_ptr(), iloc, idev))
-            return ids, dists
-        f = _filter_words(filter, N)
-        floc, fdev = _loc(f)
-        ids, dists = self._out(t.shape[0], width, on_gpu, self._result_device(t) if on_gpu else None)
-        self._check(lib().ggnn_query_filtered(
-            self._h, t.data_ptr(), t.shape[0], t.shape[1], _dtype_code(t), loc, dev, int(k_query),
-            float(tau_query), int(max_iterations), int(measure), ids.data_ptr(), dists.data_ptr(),
-            _lib.GPU if on_gpu else _lib.CPU, f.data_ptr(), N, floc, fdev))
-        return ids, dists
+            return self._blocking(lib().ggnn_query_filtered_by, t, params, self._where(fi),
+                                  self._shards)
+        f = _filter_words(filter, self._N)
+        ptr, floc, fdev = self._where(f)
+        return self._blocking(lib().ggnn_query_filtered, t, params, (ptr, self._N, floc, fdev),
+                              self._shards)
 
     def bf_query_filtered(self, query, k_gt=100, measure=DistanceMeasure.Euclidean, filter=None):
         """Extension: the exact `k_gt` nearest among the base vectors `filter` allows (see
@@ -607,26 +594,13 @@ class GGNN:
         if filter is None and filter_ids is None:
             return self.bf_query(query, k_gt, measure)
         t = _as_tensor(query, what="query")
-        N = self._N
-        loc, dev = _loc(t)
-        on_gpu = self._return_results_on_gpu
-        ids, dists = self._out(t.shape[0], int(k_gt), on_gpu,
-                               self._result_device(t) if on_gpu else None)
+        params = (int(k_gt), int(measure))
         if filter_ids is not None:
             fi = _filter_ids(filter_ids, t.shape[0])
-            iloc, idev = _loc(fi)
-            self._check(lib().ggnn_bf_query_filtered_by(
-                self._h, t.data_ptr(), t.shape[0], t.shape[1], _dtype_code(t), loc, dev, int(k_gt),
-                int(measure), ids.data_ptr(), dists.data_ptr(), _lib.GPU if on_gpu else _lib.CPU,
-                fi.data_ptr(), iloc, idev))
-            return ids, dists
-        f = _filter_words(filter, N)
-        floc, fdev = _loc(f)
-        self._check(lib().ggnn_bf_query_filtered(
-            self._h, t.data_ptr(), t.shape[0], t.shape[1], _dtype_code(t), loc, dev, int(k_gt),
-            int(measure), ids.data_ptr(), dists.data_ptr(), _lib.GPU if on_gpu else _lib.CPU,
-            f.data_ptr(), N, floc, fdev))
-        return ids, dists
+            return self._blocking(lib().ggnn_bf_query_filtered_by, t, params, self._where(fi))
+        f = _filter_words(filter, self._N)
+        ptr, floc, fdev = self._where(f)
+        return self._blocking(lib().ggnn_bf_query_filtered, t, params, (ptr, self._N, floc, fdev))
 
     def query_async(self, query, k_query, tau_query, max_iterations=400,
                     measure=DistanceMeasure.Euclidean, slot=0, filter_ids=None):
@@ -728,16 +702,8 @@ class GGNN:
 
     def bf_query(self, query, k_gt=100, measure=DistanceMeasure.Euclidean):
         """Run a brute-force query and indices and distances."""
-        t = _as_tensor(query, what="query")
-        loc, dev = _loc(t)
-        on_gpu = self._return_results_on_gpu
-        ids, dists = self._out(t.shape[0], int(k_gt), on_gpu,
-                               self._result_device(t) if on_gpu else None)
-        self._check(lib().ggnn_bf_query(self._h, t.data_ptr(), t.shape[0], t.shape[1],
-                                        _dtype_code(t), loc, dev, int(k_gt), int(measure),
-                                        ids.data_ptr(), dists.data_ptr(),
-                                        _lib.GPU if on_gpu else _lib.CPU))
-        return ids, dists
+        return self._blocking(lib().ggnn_bf_query, _as_tensor(query, what="query"),
+                              (int(k_gt), int(measure)))
 
     def get_graph(self, on_gpu_shard_id=0):
         """Access the GGNN graph."""

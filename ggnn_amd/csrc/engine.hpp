@@ -310,24 +310,18 @@ struct DeviceCtx {
   hipEvent_t shard_done[kShardStreams] = {nullptr, nullptr, nullptr, nullptr};
   hipEvent_t ev_ready{nullptr};
   DeviceBuffer bf_rescanned;    // one uint32: queries of the last bf_query answered by the scan
-  // filtered call in progress (query_filtered / bf_query_filtered): the whole allowed-id bitset on
-  // this GPU (the caller's own memory or filter_stage); null otherwise
-  DeviceBuffer filter_stage;
-  const uint32_t* filter_bits{nullptr};
+  // staging of a blocking call's filter when the caller's memory is not on this GPU (resolve_filter):
+  // the allowed-id bitset, and the filter ids / query labels
+  DeviceBuffer filter_stage, filter_ids_stage;
   // per-query filters: this GPU's copy of the handle's filter table, [(F + 2) x words] -- the F
   // rows, then the all-ones and the all-zero row that the ids -1 / out of range read -- current when
-  // filter_table_epoch equals the handle's; and the id array of the blocking call in progress
-  // (the caller's own device memory or filter_ids_stage; with it, filter_bits is the table)
+  // filter_table_epoch equals the handle's
   DeviceBuffer filter_table;
   uint64_t filter_table_epoch{0};
-  DeviceBuffer filter_ids_stage;
-  const int32_t* filter_ids{nullptr};
   // label filters: this GPU's copy of the handle's label column, int32 [N] over the global ids,
-  // current when labels_epoch equals the handle's.  filter_labeled: the blocking call in progress
-  // is a *_labeled one -- filter_bits is then this column and filter_ids holds the query labels
+  // current when labels_epoch equals the handle's
   DeviceBuffer labels;
   uint64_t labels_epoch{0};
-  bool filter_labeled{false};
   std::unique_ptr<SwapState> swap;  // out-of-core shards (null: every shard resident)
   // Result staging of query() / query_async(): grown on demand, kept between calls.  One set per
   // lane: lanes [0, kShardStreams) belong to the asynchronous slots (their streams), lane
@@ -449,6 +443,64 @@ struct DeviceCtx {
   }
 };
 
+struct ggnn_handle;
+
+// One blocking or asynchronous call as the C-ABI received it: the query set, the search parameters
+// and where the results go (bf_query reads neither tau nor max_iterations).
+struct QueryRequest {
+  const void* q;
+  uint64_t Nq;
+  uint32_t D;
+  ggnn_dtype dtype;
+  ggnn_location loc;
+  int gpu;
+  uint32_t k;
+  ggnn_measure measure;
+  int32_t* ids_out;
+  float* dists_out;
+  ggnn_location out_loc;
+  float tau{0.f};
+  uint32_t max_iterations{0};
+};
+
+// The filter of one call as the caller gave it: nothing, one allowed-id bitset for the whole batch
+// (count = n_bits), a row of the resident filter table per query, or a label per query (count =
+// Nq).  The three constructors validate against the handle; a search is filtered iff it is handed
+// one of these, never by anything the handle remembers.
+struct QueryFilter {
+  enum Kind { None, Bitset, TableIds, Labels } kind{None};
+  const void* ptr{nullptr};
+  uint64_t count{0};
+  ggnn_location loc{GGNN_CPU};
+  int gpu{0};
+  static QueryFilter bitset(const ggnn_handle& h, const uint32_t* bits, uint64_t n_bits,
+                            ggnn_location loc, int gpu);
+  // read_host_ids: ids in host memory are range-checked here (the blocking calls; the asynchronous
+  // ones do not read them, include/ggnn_c.h)
+  static QueryFilter table_ids(const ggnn_handle& h, const int32_t* ids, uint64_t Nq,
+                               ggnn_location loc, int gpu, bool read_host_ids = true);
+  static QueryFilter labels(const ggnn_handle& h, const int32_t* query_labels, uint64_t Nq,
+                            ggnn_location loc, int gpu);
+};
+
+// A QueryFilter on one GPU, as a launch takes it (filter_bits / filter_table of QueryLaunch and
+// BfLaunch): bits is the bitset, the resident table (table.ids set) or the resident label column
+// (table.query_labels set); all null: unfiltered.
+struct DeviceFilter {
+  const uint32_t* bits{nullptr};
+  FilterTable table{};
+  // ... of the queries from `first` on (a half-batch; a bitset is shared by all queries)
+  DeviceFilter from(uint32_t first) const
+  {
+    DeviceFilter d = *this;
+    if (d.table.ids)
+      d.table.ids += first;
+    if (d.table.query_labels)
+      d.table.query_labels += first;
+    return d;
+  }
+};
+
 struct ggnn_handle {
   // configuration (GGNNConfig, ggnn.cu:52-59)
   std::filesystem::path graph_dir{};
@@ -493,27 +545,12 @@ struct ggnn_handle {
   ggnn_build_work build_work{};  // collect_counters during build(): see ggnn_last_build_work
   std::mutex build_work_mutex;   // one host thread per GPU accounts into it
   uint32_t last_bf_rescanned{0};
-  // allowed-id bitset of the filtered call in progress as the caller gave it (null: no filter)
-  struct FilterSpec {
-    const uint32_t* bits{nullptr};
-    uint64_t n_bits{0};
-    ggnn_location loc{GGNN_CPU};
-    int gpu{0};
-  } active_filter;
   // per-query filters.  The table as ggnn_set_filters copied it, [num_filters x filter_words]
-  // words on the host (placed on a GPU when a context exists: place_filter_table), and the id array
-  // of the blocking *_filtered_by call in progress as the caller gave it (null: none)
+  // words on the host (placed on a GPU when a context exists: place_filter_table)
   std::vector<uint32_t> filter_table_host;
   uint32_t num_filters{0};
   uint32_t filter_words{0};
   uint64_t filter_epoch{0};  // counts ggnn_set_filters calls: a context with another value is stale
-  struct FilterIdSpec {
-    const int32_t* ids{nullptr};
-    uint64_t count{0};
-    ggnn_location loc{GGNN_CPU};
-    int gpu{0};
-    bool labeled{false};  // the values are query labels (label filters below), not filter ids
-  } active_filter_ids;
   // label filters.  The label column as ggnn_set_labels copied it, one int32 per base vector on the
   // host (placed on a GPU when a context exists: place_labels); empty: no labels
   std::vector<int32_t> labels_host;
@@ -614,31 +651,21 @@ struct ggnn_handle {
 
   bool ensure_prescreen(DeviceCtx& ctx, uint32_t si, ggnn_measure measure);
 
-  void query_device(DeviceCtx& ctx, const void* d_query, uint32_t nq, uint32_t k_query,
-                    float tau_query, uint32_t max_iterations, ggnn_measure measure,
-                    int32_t* d_ids, float* d_dists);
+  // the filter of a call on ctx's GPU: the caller's memory where it lives there, else copied on
+  // the lane's stream (blocking lane: ctx.filter_stage / filter_ids_stage, a slot's lane: its
+  // f_stage); the resident table or label column is placed if it is missing or stale
+  DeviceFilter resolve_filter(DeviceCtx& ctx, const QueryFilter& f, int lane);
 
-  void query(const void* q, uint64_t Nq, uint32_t D, ggnn_dtype dtype, ggnn_location loc,
-             int q_gpu, uint32_t k_query, float tau_query, uint32_t max_iterations,
-             ggnn_measure measure, int32_t* ids_out, float* dists_out, ggnn_location out_loc);
+  // the search of local shard si for nq queries of request r, without work counters
+  QueryLaunch shard_launch(const DeviceCtx& ctx, uint32_t si, const QueryRequest& r,
+                           const void* d_query, uint32_t nq, int32_t* d_ids, float* d_dists,
+                           bool use_prescreen, const DeviceFilter& df) const;
 
-  // filtered calls: the blocking query() / bf_query() with an allowed-id bitset over the global
-  // base ids (n_bits == base_N), shared by all queries of the batch
-  void query_filtered(const void* q, uint64_t Nq, uint32_t D, ggnn_dtype dtype, ggnn_location loc,
-                      int q_gpu, uint32_t k_query, float tau_query, uint32_t max_iterations,
-                      ggnn_measure measure, int32_t* ids_out, float* dists_out,
-                      ggnn_location out_loc, const uint32_t* bits, uint64_t n_bits,
-                      ggnn_location filter_loc, int filter_gpu);
-  void bf_query_filtered(const void* q, uint64_t Nq, uint32_t D, ggnn_dtype dtype,
-                         ggnn_location loc, int q_gpu, uint32_t k_gt, ggnn_measure measure,
-                         int32_t* ids_out, float* dists_out, ggnn_location out_loc,
-                         const uint32_t* bits, uint64_t n_bits, ggnn_location filter_loc,
-                         int filter_gpu);
-  void begin_filter(const uint32_t* bits, uint64_t n_bits, ggnn_location loc, int gpu);
-  void end_filter();
-  // the active filter on ctx's GPU, copied on ctx.stream unless it already lives there (null: none);
-  // with filter ids active: the resident table, and ctx.filter_ids is staged beside it
-  const uint32_t* stage_filter(DeviceCtx& ctx);
+  void query_device(DeviceCtx& ctx, const QueryRequest& r, const void* d_query, int32_t* d_ids,
+                    float* d_dists, const QueryFilter& filter);
+
+  void query(const QueryRequest& r, const QueryFilter& filter);
+  void query_split(const QueryRequest& r, const QueryFilter& filter);
 
   // per-query filters (engine_query.cpp)
   void set_filters(const uint32_t* bits, uint32_t F, uint64_t n_bits, ggnn_location loc, int gpu);
@@ -648,11 +675,6 @@ struct ggnn_handle {
   // ctx's copy of the table, placed now if it is missing or stale (synchronous; ctx is active)
   const uint32_t* place_filter_table(DeviceCtx& ctx);
   void place_filter_tables();  // ... on every context there is
-  // filter_table / consts / words / num_filters of a launch on ctx with the id array `ids`;
-  // labeled: `ids` are query labels and the launch's filter_bits is the label column
-  FilterTable launch_filter_table(const DeviceCtx& ctx, const int32_t* ids,
-                                  bool labeled = false) const;
-  void begin_filter_ids(const int32_t* ids, uint64_t Nq, ggnn_location loc, int gpu);
 
   // label filters (engine_query.cpp)
   void set_labels(const int32_t* labels, uint64_t n, ggnn_location loc, int gpu);
@@ -661,31 +683,8 @@ struct ggnn_handle {
   void drop_labels();
   // ctx's copy of the label column, placed now if it is missing or stale (synchronous; ctx is
   // active)
-  const uint32_t* place_labels(DeviceCtx& ctx);
+  const int32_t* place_labels(DeviceCtx& ctx);
   void place_labels_everywhere();  // ... on every context there is
-  void begin_query_labels(const int32_t* labels, uint64_t Nq, ggnn_location loc, int gpu);
-  void query_labeled(const void* q, uint64_t Nq, uint32_t D, ggnn_dtype dtype, ggnn_location loc,
-                     int q_gpu, uint32_t k_query, float tau_query, uint32_t max_iterations,
-                     ggnn_measure measure, int32_t* ids_out, float* dists_out,
-                     ggnn_location out_loc, const int32_t* query_labels, ggnn_location labels_loc,
-                     int labels_gpu);
-  void bf_query_labeled(const void* q, uint64_t Nq, uint32_t D, ggnn_dtype dtype,
-                        ggnn_location loc, int q_gpu, uint32_t k_gt, ggnn_measure measure,
-                        int32_t* ids_out, float* dists_out, ggnn_location out_loc,
-                        const int32_t* query_labels, ggnn_location labels_loc, int labels_gpu);
-  void query_filtered_by(const void* q, uint64_t Nq, uint32_t D, ggnn_dtype dtype,
-                         ggnn_location loc, int q_gpu, uint32_t k_query, float tau_query,
-                         uint32_t max_iterations, ggnn_measure measure, int32_t* ids_out,
-                         float* dists_out, ggnn_location out_loc, const int32_t* filter_ids,
-                         ggnn_location ids_loc, int ids_gpu);
-  void bf_query_filtered_by(const void* q, uint64_t Nq, uint32_t D, ggnn_dtype dtype,
-                            ggnn_location loc, int q_gpu, uint32_t k_gt, ggnn_measure measure,
-                            int32_t* ids_out, float* dists_out, ggnn_location out_loc,
-                            const int32_t* filter_ids, ggnn_location ids_loc, int ids_gpu);
-
-  void query_split(const void* q, uint32_t nq, uint32_t D, ggnn_dtype dtype, ggnn_location loc,
-                   int q_gpu, uint32_t k_query, float tau_query, uint32_t max_iterations,
-                   ggnn_measure measure, int32_t* ids_out, float* dists_out);
 
   void grow_lane(DeviceCtx& owner, int lane, DeviceBuffer& b, size_t bytes);
 
@@ -709,24 +708,14 @@ struct ggnn_handle {
   void exchange_gather_copies(int lane, uint32_t nq, uint32_t k_query, size_t row, int32_t* ids_out,
                               float* dists_out);
 
-  void query_async(const void* d_query, uint64_t Nq, uint32_t D, ggnn_dtype dtype,
-                   ggnn_location loc, int q_gpu, uint32_t k_query, float tau_query,
-                   uint32_t max_iterations, ggnn_measure measure, int32_t* d_ids, float* d_dists,
-                   uint32_t slot, const int32_t* filter_ids = nullptr, bool labeled = false);
+  void query_async(const QueryRequest& r, uint32_t slot, const QueryFilter& filter);
 
-  // filter_bits / filter_ids: the bitset (ids null) or the filter table and the ids of these nq
-  // queries, on ctx's GPU; both null: unfiltered.  labeled: the label column and the query labels
-  void enqueue_local_search(DeviceCtx& ctx, int lane, const void* d_query, uint32_t nq,
-                            uint32_t k_query, float tau_query, uint32_t max_iterations,
-                            ggnn_measure measure, int32_t* d_ids, float* d_dists,
-                            const uint32_t* filter_bits, const int32_t* filter_ids,
-                            bool labeled = false);
+  void enqueue_local_search(DeviceCtx& ctx, int lane, const QueryRequest& r, const void* d_query,
+                            uint32_t nq, int32_t* d_ids, float* d_dists, const DeviceFilter& df);
   void synchronize_slot(uint32_t slot);
   void synchronize();
 
-  void bf_query(const void* q, uint64_t Nq, uint32_t D, ggnn_dtype dtype, ggnn_location loc,
-                int q_gpu, uint32_t k_gt, ggnn_measure measure, int32_t* ids_out,
-                float* dists_out, ggnn_location out_loc);
+  void bf_query(const QueryRequest& r, const QueryFilter& filter);
 
   std::filesystem::path part_file(uint32_t shard) const;
 

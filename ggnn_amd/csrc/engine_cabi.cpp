@@ -45,6 +45,42 @@ ggnn_status guarded(ggnn_t* h, F&& f)
   if (!(h))                 \
   return GGNN_INVALID_ARGUMENT
 
+// the request of the ggnn_query_async* calls: the query lives on GPU gpu_id or (gpu_id < 0) in host
+// memory, and the results go where the exchange puts them
+QueryRequest async_request(const void* query, uint64_t Nq, uint32_t D, ggnn_dtype dtype,
+                           int gpu_id, uint32_t k_query, float tau_query, uint32_t max_iterations,
+                           ggnn_measure measure, int32_t* ids_out, float* dists_out)
+{
+  return {query, Nq, D, dtype, gpu_id < 0 ? GGNN_CPU : GGNN_GPU, gpu_id, k_query, measure,
+          ids_out, dists_out, GGNN_GPU, tau_query, max_iterations};
+}
+
+// the QueryLaunch of the ggnn_op_query* seam calls (codes / params / n_rows may be null)
+QueryLaunch seam_query(const void* base, ggnn_dtype dtype, uint32_t N_base, uint32_t D,
+                       const uint8_t* codes, const float* params, const void* query, uint32_t Nq,
+                       const int32_t* graph0, uint32_t KBuild, const int32_t* start,
+                       uint32_t num_start, const float* nn1_stats, uint32_t k_query,
+                       float tau_query, uint32_t max_iterations, ggnn_measure measure,
+                       uint32_t shards_per_gpu, uint32_t on_gpu_shard, int32_t* ids, float* dists,
+                       uint32_t* n_dist, uint32_t* n_pop, uint32_t* n_rows)
+{
+  GGNN_REQUIRE(!codes == !params, GGNN_INVALID_ARGUMENT,
+               "pre-screen codes and params go together");
+  GGNN_REQUIRE(!codes || dtype == GGNN_F32, GGNN_INVALID_ARGUMENT,
+               "the pre-screen needs a float32 base");
+  QueryLaunch q{base,      query,          dtype,    N_base,         D,         Nq,
+                graph0,    KBuild,         start,    num_start,      nn1_stats, k_query,
+                tau_query, max_iterations, measure,  shards_per_gpu, on_gpu_shard, ids,
+                dists,     n_dist,         n_pop};
+  if (codes) {
+    q.ps_codes = codes;
+    q.ps_params = params;
+    q.ps_Dc = prescreen_code_dim(D);
+  }
+  q.n_rows = n_rows;
+  return q;
+}
+
 // the table arguments of the *_filtered_by seam calls as a launch sees them
 FilterTable seam_filter_table(const uint32_t* filter_table, uint32_t num_filters, uint64_t n_bits,
                               const int32_t* filter_ids, uint32_t filter_bit_offset,
@@ -354,8 +390,9 @@ ggnn_status ggnn_query(ggnn_t* h, const void* query, uint64_t Nq, uint32_t D, gg
 {
   GGNN_NEED_HANDLE(h);
   return guarded(h, [&] {
-    h->query(query, Nq, D, dtype, location, gpu_id, k_query, tau_query, max_iterations, measure,
-             ids_out, dists_out, out_location);
+    h->query({query, Nq, D, dtype, location, gpu_id, k_query, measure, ids_out, dists_out,
+              out_location, tau_query, max_iterations},
+             QueryFilter{});
   });
 }
 
@@ -366,8 +403,9 @@ ggnn_status ggnn_query_async(ggnn_t* h, const void* query, uint64_t Nq, uint32_t
 {
   GGNN_NEED_HANDLE(h);
   return guarded(h, [&] {
-    h->query_async(query, Nq, D, dtype, gpu_id < 0 ? GGNN_CPU : GGNN_GPU, gpu_id, k_query,
-                   tau_query, max_iterations, measure, ids_out, dists_out, slot);
+    h->query_async(async_request(query, Nq, D, dtype, gpu_id, k_query, tau_query, max_iterations,
+                                 measure, ids_out, dists_out),
+                   slot, QueryFilter{});
   });
 }
 
@@ -390,11 +428,14 @@ ggnn_status ggnn_bf_query(ggnn_t* h, const void* query, uint64_t Nq, uint32_t D,
 {
   GGNN_NEED_HANDLE(h);
   return guarded(h, [&] {
-    h->bf_query(query, Nq, D, dtype, location, gpu_id, k_gt, measure, ids_out, dists_out,
-                out_location);
+    h->bf_query({query, Nq, D, dtype, location, gpu_id, k_gt, measure, ids_out, dists_out,
+                 out_location},
+                QueryFilter{});
   });
 }
 
+// The filtered calls: the filter is an argument of query() / bf_query() like the request.  Its
+// constructor runs before the call, so a filter that is wrong is reported before anything else.
 ggnn_status ggnn_query_filtered(ggnn_t* h, const void* query, uint64_t Nq, uint32_t D,
                                 ggnn_dtype dtype, ggnn_location location, int gpu_id,
                                 uint32_t k_query, float tau_query, uint32_t max_iterations,
@@ -404,9 +445,9 @@ ggnn_status ggnn_query_filtered(ggnn_t* h, const void* query, uint64_t Nq, uint3
 {
   GGNN_NEED_HANDLE(h);
   return guarded(h, [&] {
-    h->query_filtered(query, Nq, D, dtype, location, gpu_id, k_query, tau_query, max_iterations,
-                      measure, ids_out, dists_out, out_location, allowed_bits, n_bits,
-                      filter_location, filter_gpu_id);
+    h->query({query, Nq, D, dtype, location, gpu_id, k_query, measure, ids_out, dists_out,
+              out_location, tau_query, max_iterations},
+             QueryFilter::bitset(*h, allowed_bits, n_bits, filter_location, filter_gpu_id));
   });
 }
 
@@ -419,8 +460,9 @@ ggnn_status ggnn_bf_query_filtered(ggnn_t* h, const void* query, uint64_t Nq, ui
 {
   GGNN_NEED_HANDLE(h);
   return guarded(h, [&] {
-    h->bf_query_filtered(query, Nq, D, dtype, location, gpu_id, k_gt, measure, ids_out, dists_out,
-                         out_location, allowed_bits, n_bits, filter_location, filter_gpu_id);
+    h->bf_query({query, Nq, D, dtype, location, gpu_id, k_gt, measure, ids_out, dists_out,
+                 out_location},
+                QueryFilter::bitset(*h, allowed_bits, n_bits, filter_location, filter_gpu_id));
   });
 }
 
@@ -456,9 +498,9 @@ ggnn_status ggnn_query_filtered_by(ggnn_t* h, const void* query, uint64_t Nq, ui
 {
   GGNN_NEED_HANDLE(h);
   return guarded(h, [&] {
-    h->query_filtered_by(query, Nq, D, dtype, location, gpu_id, k_query, tau_query,
-                         max_iterations, measure, ids_out, dists_out, out_location, filter_ids,
-                         ids_location, ids_gpu_id);
+    h->query({query, Nq, D, dtype, location, gpu_id, k_query, measure, ids_out, dists_out,
+              out_location, tau_query, max_iterations},
+             QueryFilter::table_ids(*h, filter_ids, Nq, ids_location, ids_gpu_id));
   });
 }
 
@@ -471,8 +513,9 @@ ggnn_status ggnn_bf_query_filtered_by(ggnn_t* h, const void* query, uint64_t Nq,
 {
   GGNN_NEED_HANDLE(h);
   return guarded(h, [&] {
-    h->bf_query_filtered_by(query, Nq, D, dtype, location, gpu_id, k_gt, measure, ids_out,
-                            dists_out, out_location, filter_ids, ids_location, ids_gpu_id);
+    h->bf_query({query, Nq, D, dtype, location, gpu_id, k_gt, measure, ids_out, dists_out,
+                 out_location},
+                QueryFilter::table_ids(*h, filter_ids, Nq, ids_location, ids_gpu_id));
   });
 }
 
@@ -484,12 +527,11 @@ ggnn_status ggnn_query_async_filtered_by(ggnn_t* h, const void* query, uint64_t 
 {
   GGNN_NEED_HANDLE(h);
   return guarded(h, [&] {
-    GGNN_REQUIRE(h->num_filters != 0, GGNN_INVALID_STATE,
-                 "There is no filter table the filter ids could refer to (ggnn_set_filters).");
-    GGNN_REQUIRE(!Nq || filter_ids != nullptr, GGNN_INVALID_ARGUMENT,
-                 "the filter id array is null");
-    h->query_async(query, Nq, D, dtype, gpu_id < 0 ? GGNN_CPU : GGNN_GPU, gpu_id, k_query,
-                   tau_query, max_iterations, measure, ids_out, dists_out, slot, filter_ids);
+    const QueryRequest r = async_request(query, Nq, D, dtype, gpu_id, k_query, tau_query,
+                                         max_iterations, measure, ids_out, dists_out);
+    // (the ids live where the query lives and are not read on the host)
+    h->query_async(r, slot, QueryFilter::table_ids(*h, filter_ids, Nq, r.loc, r.gpu,
+                                                   /*read_host_ids=*/false));
   });
 }
 
@@ -525,9 +567,9 @@ ggnn_status ggnn_query_labeled(ggnn_t* h, const void* query, uint64_t Nq, uint32
 {
   GGNN_NEED_HANDLE(h);
   return guarded(h, [&] {
-    h->query_labeled(query, Nq, D, dtype, location, gpu_id, k_query, tau_query, max_iterations,
-                     measure, ids_out, dists_out, out_location, query_labels, labels_location,
-                     labels_gpu_id);
+    h->query({query, Nq, D, dtype, location, gpu_id, k_query, measure, ids_out, dists_out,
+              out_location, tau_query, max_iterations},
+             QueryFilter::labels(*h, query_labels, Nq, labels_location, labels_gpu_id));
   });
 }
 
@@ -540,8 +582,9 @@ ggnn_status ggnn_bf_query_labeled(ggnn_t* h, const void* query, uint64_t Nq, uin
 {
   GGNN_NEED_HANDLE(h);
   return guarded(h, [&] {
-    h->bf_query_labeled(query, Nq, D, dtype, location, gpu_id, k_gt, measure, ids_out, dists_out,
-                        out_location, query_labels, labels_location, labels_gpu_id);
+    h->bf_query({query, Nq, D, dtype, location, gpu_id, k_gt, measure, ids_out, dists_out,
+                 out_location},
+                QueryFilter::labels(*h, query_labels, Nq, labels_location, labels_gpu_id));
   });
 }
 
@@ -553,13 +596,9 @@ ggnn_status ggnn_query_async_labeled(ggnn_t* h, const void* query, uint64_t Nq, 
 {
   GGNN_NEED_HANDLE(h);
   return guarded(h, [&] {
-    GGNN_REQUIRE(!h->labels_host.empty(), GGNN_INVALID_STATE,
-                 "There are no labels the query labels could refer to (ggnn_set_labels).");
-    GGNN_REQUIRE(!Nq || query_labels != nullptr, GGNN_INVALID_ARGUMENT,
-                 "the query label array is null");
-    h->query_async(query, Nq, D, dtype, gpu_id < 0 ? GGNN_CPU : GGNN_GPU, gpu_id, k_query,
-                   tau_query, max_iterations, measure, ids_out, dists_out, slot, query_labels,
-                   /*labeled=*/true);
+    const QueryRequest r = async_request(query, Nq, D, dtype, gpu_id, k_query, tau_query,
+                                         max_iterations, measure, ids_out, dists_out);
+    h->query_async(r, slot, QueryFilter::labels(*h, query_labels, Nq, r.loc, r.gpu));
   });
 }
 
@@ -675,11 +714,11 @@ ggnn_status ggnn_op_query(const void* base, ggnn_dtype dtype, uint32_t N_base, u
                           float* dists, uint32_t* n_dist, uint32_t* n_pop, void* stream)
 {
   return guarded(nullptr, [&] {
-    QueryLaunch q{base,      query,          dtype,         N_base,       D,       Nq,
-                  graph0,    KBuild,         start,         num_start,    nn1_stats, k_query,
-                  tau_query, max_iterations, measure,       shards_per_gpu, on_gpu_shard, ids,
-                  dists,     n_dist,         n_pop};
-    launch_query(q, static_cast<hipStream_t>(stream));
+    launch_query(seam_query(base, dtype, N_base, D, nullptr, nullptr, query, Nq, graph0, KBuild,
+                            start, num_start, nn1_stats, k_query, tau_query, max_iterations,
+                            measure, shards_per_gpu, on_gpu_shard, ids, dists, n_dist, n_pop,
+                            nullptr),
+                 static_cast<hipStream_t>(stream));
   });
 }
 
@@ -731,15 +770,11 @@ ggnn_status ggnn_op_query_prescreened(const float* base, uint32_t N_base, uint32
 {
   return guarded(nullptr, [&] {
     GGNN_REQUIRE(codes && params, GGNN_INVALID_ARGUMENT, "pre-screen buffers are null");
-    QueryLaunch q{base,      query,          GGNN_F32, N_base,         D,         Nq,
-                  graph0,    KBuild,         start,    num_start,      nn1_stats, k_query,
-                  tau_query, max_iterations, measure,  shards_per_gpu, on_gpu_shard, ids,
-                  dists,     n_dist,         n_pop};
-    q.ps_codes = codes;
-    q.ps_params = params;
-    q.ps_Dc = prescreen_code_dim(D);
-    q.n_rows = n_rows;
-    launch_query(q, static_cast<hipStream_t>(stream));
+    launch_query(seam_query(base, GGNN_F32, N_base, D, codes, params, query, Nq, graph0, KBuild,
+                            start, num_start, nn1_stats, k_query, tau_query, max_iterations,
+                            measure, shards_per_gpu, on_gpu_shard, ids, dists, n_dist, n_pop,
+                            n_rows),
+                 static_cast<hipStream_t>(stream));
   });
 }
 
@@ -756,20 +791,10 @@ ggnn_status ggnn_op_query_filtered(const void* base, ggnn_dtype dtype, uint32_t 
 {
   return guarded(nullptr, [&] {
     GGNN_REQUIRE(filter_bits != nullptr, GGNN_INVALID_ARGUMENT, "the filter bitset is null");
-    GGNN_REQUIRE(!codes == !params, GGNN_INVALID_ARGUMENT,
-                 "pre-screen codes and params go together");
-    GGNN_REQUIRE(!codes || dtype == GGNN_F32, GGNN_INVALID_ARGUMENT,
-                 "the pre-screen needs a float32 base");
-    QueryLaunch q{base,      query,          dtype,    N_base,         D,         Nq,
-                  graph0,    KBuild,         start,    num_start,      nn1_stats, k_query,
-                  tau_query, max_iterations, measure,  shards_per_gpu, on_gpu_shard, ids,
-                  dists,     n_dist,         n_pop};
-    if (codes) {
-      q.ps_codes = codes;
-      q.ps_params = params;
-      q.ps_Dc = prescreen_code_dim(D);
-    }
-    q.n_rows = n_rows;
+    QueryLaunch q = seam_query(base, dtype, N_base, D, codes, params, query, Nq, graph0, KBuild,
+                               start, num_start, nn1_stats, k_query, tau_query, max_iterations,
+                               measure, shards_per_gpu, on_gpu_shard, ids, dists, n_dist, n_pop,
+                               n_rows);
     q.filter_bits = filter_bits;
     q.filter_bit_offset = filter_bit_offset;
     launch_query(q, static_cast<hipStream_t>(stream));
@@ -805,20 +830,10 @@ ggnn_status ggnn_op_query_filtered_by(const void* base, ggnn_dtype dtype, uint32
                                       void* stream)
 {
   return guarded(nullptr, [&] {
-    GGNN_REQUIRE(!codes == !params, GGNN_INVALID_ARGUMENT,
-                 "pre-screen codes and params go together");
-    GGNN_REQUIRE(!codes || dtype == GGNN_F32, GGNN_INVALID_ARGUMENT,
-                 "the pre-screen needs a float32 base");
-    QueryLaunch q{base,      query,          dtype,    N_base,         D,         Nq,
-                  graph0,    KBuild,         start,    num_start,      nn1_stats, k_query,
-                  tau_query, max_iterations, measure,  shards_per_gpu, on_gpu_shard, ids,
-                  dists,     n_dist,         n_pop};
-    if (codes) {
-      q.ps_codes = codes;
-      q.ps_params = params;
-      q.ps_Dc = prescreen_code_dim(D);
-    }
-    q.n_rows = n_rows;
+    QueryLaunch q = seam_query(base, dtype, N_base, D, codes, params, query, Nq, graph0, KBuild,
+                               start, num_start, nn1_stats, k_query, tau_query, max_iterations,
+                               measure, shards_per_gpu, on_gpu_shard, ids, dists, n_dist, n_pop,
+                               n_rows);
     q.filter_table =
         seam_filter_table(filter_table, num_filters, n_bits, filter_ids, filter_bit_offset, N_base);
     q.filter_bits = filter_table;
@@ -858,20 +873,10 @@ ggnn_status ggnn_op_query_labeled(const void* base, ggnn_dtype dtype, uint32_t N
                                   void* stream)
 {
   return guarded(nullptr, [&] {
-    GGNN_REQUIRE(!codes == !params, GGNN_INVALID_ARGUMENT,
-                 "pre-screen codes and params go together");
-    GGNN_REQUIRE(!codes || dtype == GGNN_F32, GGNN_INVALID_ARGUMENT,
-                 "the pre-screen needs a float32 base");
-    QueryLaunch q{base,      query,          dtype,    N_base,         D,         Nq,
-                  graph0,    KBuild,         start,    num_start,      nn1_stats, k_query,
-                  tau_query, max_iterations, measure,  shards_per_gpu, on_gpu_shard, ids,
-                  dists,     n_dist,         n_pop};
-    if (codes) {
-      q.ps_codes = codes;
-      q.ps_params = params;
-      q.ps_Dc = prescreen_code_dim(D);
-    }
-    q.n_rows = n_rows;
+    QueryLaunch q = seam_query(base, dtype, N_base, D, codes, params, query, Nq, graph0, KBuild,
+                               start, num_start, nn1_stats, k_query, tau_query, max_iterations,
+                               measure, shards_per_gpu, on_gpu_shard, ids, dists, n_dist, n_pop,
+                               n_rows);
     q.filter_table = seam_labels(labels, n_labels, query_labels, filter_bit_offset, N_base);
     q.filter_bits = reinterpret_cast<const uint32_t*>(labels);
     q.filter_bit_offset = filter_bit_offset;

@@ -39,15 +39,55 @@ ggnn_handle::Staged ggnn_handle::stage_query(DeviceCtx& ctx, const void* q, uint
   return s;
 }
 
+// the one place that fills a shard's QueryLaunch (the caller that collects counters adds them)
+QueryLaunch ggnn_handle::shard_launch(const DeviceCtx& ctx, uint32_t si, const QueryRequest& r,
+                                      const void* d_query, uint32_t nq, int32_t* d_ids,
+                                      float* d_dists, bool use_prescreen,
+                                      const DeviceFilter& df) const
+{
+  const Shard& sh = ctx.shards[si];
+  QueryLaunch ql{shard_base(ctx, si),
+                 d_query,
+                 base_dtype,
+                 cfg.N,
+                 pad_D,
+                 nq,
+                 sh.graph,
+                 cfg.KBuild,
+                 sh.translation + cfg.STs_offsets[kLayers - 1],
+                 cfg.S,
+                 sh.nn1_stats,
+                 r.k,
+                 r.tau,
+                 r.max_iterations,
+                 r.measure,
+                 shards_per_gpu,
+                 si,
+                 d_ids,
+                 d_dists,
+                 nullptr,
+                 nullptr};
+  if (use_prescreen) {
+    ql.ps_codes = sh.ps_codes.as<uint8_t>();
+    ql.ps_params = sh.ps_params.as<float>();
+    ql.ps_Dc = prescreen_code_dim(pad_D);
+  }
+  ql.filter_bits = df.bits;
+  ql.filter_bit_offset = sh.global_id * cfg.N;
+  ql.filter_table = df.table;
+  return ql;
+}
+
 // GPUInstance::query, gpu_instance.cu:626-743: all shards of one GPU into d_ids/d_dists
 // [Nq, K * shards_per_gpu]
-void ggnn_handle::query_device(DeviceCtx& ctx, const void* d_query, uint32_t nq, uint32_t k_query,
-                  float tau_query, uint32_t max_iterations, ggnn_measure measure,
-                  int32_t* d_ids, float* d_dists)
+void ggnn_handle::query_device(DeviceCtx& ctx, const QueryRequest& r, const void* d_query,
+                               int32_t* d_ids, float* d_dists, const QueryFilter& filter)
 {
   hipStream_t stream = ctx.stream;
   const uint32_t spg = shards_per_gpu;
-  ctx.filter_bits = stage_filter(ctx);
+  const uint32_t nq = static_cast<uint32_t>(r.Nq);
+  const ggnn_measure measure = r.measure;
+  const DeviceFilter df = resolve_filter(ctx, filter, DeviceCtx::kBlockingLane);
   DeviceBuffer c_dist, c_pop, c_rows;
   if (collect_counters) {
     c_dist.alloc(static_cast<size_t>(nq) * 4);
@@ -83,36 +123,10 @@ void ggnn_handle::query_device(DeviceCtx& ctx, const void* d_query, uint32_t nq,
     }
     const bool use_ps = ensure_prescreen(ctx, si, measure);
     const Shard& sh = ctx.shards[si];
-    QueryLaunch ql{shard_base(ctx, si),
-                   d_query,
-                   base_dtype,
-                   cfg.N,
-                   pad_D,
-                   nq,
-                   sh.graph,
-                   cfg.KBuild,
-                   sh.translation + cfg.STs_offsets[kLayers - 1],
-                   cfg.S,
-                   sh.nn1_stats,
-                   k_query,
-                   tau_query,
-                   max_iterations,
-                   measure,
-                   spg,
-                   si,
-                   d_ids,
-                   d_dists,
-                   c_dist.as<uint32_t>(),
-                   c_pop.as<uint32_t>()};
-    if (use_ps) {
-      ql.ps_codes = sh.ps_codes.as<uint8_t>();
-      ql.ps_params = sh.ps_params.as<float>();
-      ql.ps_Dc = prescreen_code_dim(pad_D);
-    }
+    QueryLaunch ql = shard_launch(ctx, si, r, d_query, nq, d_ids, d_dists, use_ps, df);
+    ql.n_dist = c_dist.as<uint32_t>();
+    ql.n_pop = c_pop.as<uint32_t>();
     ql.n_rows = c_rows.as<uint32_t>();
-    ql.filter_bits = ctx.filter_bits;
-    ql.filter_bit_offset = sh.global_id * cfg.N;
-    ql.filter_table = launch_filter_table(ctx, ctx.filter_ids, ctx.filter_labeled);
     if (overlap) {
       launch_query(ql, ctx.shard_stream[si % DeviceCtx::kShardStreams]);
       continue;
@@ -150,7 +164,7 @@ void ggnn_handle::query_device(DeviceCtx& ctx, const void* d_query, uint32_t nq,
     GGNN_HIP_CHECK(hipEventRecord(ctx.ev_b, stream));
   }
   if (spg > 1)
-    launch_sort_shard_results(nq, k_query * spg, d_ids, d_dists, stream);
+    launch_sort_shard_results(nq, r.k * spg, d_ids, d_dists, stream);
   GGNN_HIP_CHECK(hipStreamSynchronize(stream));
   if (overlap) {
     GGNN_HIP_CHECK(hipEventElapsedTime(&ctx.query_ms, ctx.ev_a, ctx.ev_b));
@@ -160,20 +174,21 @@ void ggnn_handle::query_device(DeviceCtx& ctx, const void* d_query, uint32_t nq,
 }
 
 // GGNNImpl::queryImpl, ggnn.cu:278-330
-void ggnn_handle::query(const void* q, uint64_t Nq, uint32_t D, ggnn_dtype dtype, ggnn_location loc,
-           int q_gpu, uint32_t k_query, float tau_query, uint32_t max_iterations,
-           ggnn_measure measure, int32_t* ids_out, float* dists_out, ggnn_location out_loc)
+void ggnn_handle::query(const QueryRequest& r, const QueryFilter& filter)
 {
   GGNN_REQUIRE(has_graph(), GGNN_INVALID_STATE, "There is no graph to query.");
-  check_query(Nq, D, dtype, q);
-  const bool direct = (out_loc == GGNN_GPU);
+  check_query(r.Nq, r.D, r.dtype, r.q);
+  const bool direct = (r.out_loc == GGNN_GPU);
   GGNN_REQUIRE(!(direct && devs.size() > 1), GGNN_INVALID_STATE,
                "Returning query results on GPU is only possible when using a single GPU.");
   query_ms = 0.f;
   last_n_dist = last_n_pop = last_float_rows = last_code_rows = 0;
-  if (!Nq)
+  if (!r.Nq)
     return;
-  const uint32_t nq = static_cast<uint32_t>(Nq);
+  const uint32_t nq = static_cast<uint32_t>(r.Nq);
+  const uint32_t k_query = r.k;
+  int32_t* const ids_out = r.ids_out;
+  float* const dists_out = r.dists_out;
   const size_t row = static_cast<size_t>(k_query) * shards_per_gpu;
   const size_t part = nq * row;
 
@@ -188,15 +203,14 @@ void ggnn_handle::query(const void* q, uint64_t Nq, uint32_t D, ggnn_dtype dtype
     const bool several = devs.size() > 1 || hook(kHookExchange) == 1;
     const bool want = split >= 0 ? split == 1 : nq >= 4096;
     if (several && !direct && !collect_counters && want && nq >= 2 && !swapping()) {
-      query_split(q, nq, D, dtype, loc, q_gpu, k_query, tau_query, max_iterations, measure,
-                  ids_out, dists_out);
+      query_split(r, filter);
       return;
     }
   }
 
   constexpr int lane = DeviceCtx::kBlockingLane;
   for_each_device([&](DeviceCtx& ctx) {
-    Staged sq = stage_query(ctx, q, Nq, D, dtype, loc, q_gpu);
+    Staged sq = stage_query(ctx, r.q, r.Nq, r.D, r.dtype, r.loc, r.gpu);
     int32_t* d_ids = ids_out;
     float* d_dists = dists_out;
     if (!direct) {
@@ -204,7 +218,7 @@ void ggnn_handle::query(const void* q, uint64_t Nq, uint32_t D, ggnn_dtype dtype
       d_ids = ctx.xb[lane].r_pack.as<int32_t>();
       d_dists = reinterpret_cast<float*>(d_ids + part);
     }
-    query_device(ctx, sq.ptr, nq, k_query, tau_query, max_iterations, measure, d_ids, d_dists);
+    query_device(ctx, r, sq.ptr, d_ids, d_dists, filter);
   });
   for (const DeviceCtx& ctx : devs) {
     query_ms = std::max(query_ms, ctx.query_ms);  // GPUs run concurrently
@@ -221,10 +235,10 @@ void ggnn_handle::query(const void* q, uint64_t Nq, uint32_t D, ggnn_dtype dtype
     // ResultMerger::merge for one GPU: first K of each pre-sorted row (result_merger.cpp:55-73)
     DeviceCtx& d0 = devs[0];
     d0.activate();
-    const int32_t* r = d0.xb[lane].r_pack.as<int32_t>();
-    GGNN_HIP_CHECK(hipMemcpy2DAsync(ids_out, k_query * 4ull, r, row * 4, k_query * 4ull, nq,
+    const int32_t* rows = d0.xb[lane].r_pack.as<int32_t>();
+    GGNN_HIP_CHECK(hipMemcpy2DAsync(ids_out, k_query * 4ull, rows, row * 4, k_query * 4ull, nq,
                                     hipMemcpyDeviceToHost, d0.stream));
-    GGNN_HIP_CHECK(hipMemcpy2DAsync(dists_out, k_query * 4ull, r + part, row * 4,
+    GGNN_HIP_CHECK(hipMemcpy2DAsync(dists_out, k_query * 4ull, rows + part, row * 4,
                                     k_query * 4ull, nq, hipMemcpyDeviceToHost, d0.stream));
     GGNN_HIP_CHECK(hipStreamSynchronize(d0.stream));
     last_exchange = "none";
@@ -234,12 +248,12 @@ void ggnn_handle::query(const void* q, uint64_t Nq, uint32_t D, ggnn_dtype dtype
 }
 
 // blocking multi-GPU query as two half-batches on the asynchronous lanes 0 and 1 (see query())
-void ggnn_handle::query_split(const void* q, uint32_t nq, uint32_t D, ggnn_dtype dtype, ggnn_location loc,
-                 int q_gpu, uint32_t k_query, float tau_query, uint32_t max_iterations,
-                 ggnn_measure measure, int32_t* ids_out, float* dists_out)
+void ggnn_handle::query_split(const QueryRequest& r, const QueryFilter& filter)
 {
+  const uint32_t nq = static_cast<uint32_t>(r.Nq);
+  const uint32_t k_query = r.k;
   const size_t row = static_cast<size_t>(k_query) * shards_per_gpu;
-  const size_t es = dtype_size(dtype);
+  const size_t es = dtype_size(r.dtype);
   const uint32_t first[2] = {0u, nq / 2};
   const uint32_t count[2] = {nq / 2, nq - nq / 2};
   std::vector<Staged> staged(devs.size());
@@ -248,10 +262,10 @@ void ggnn_handle::query_split(const void* q, uint32_t nq, uint32_t D, ggnn_dtype
     DeviceCtx& ctx = devs[g];
     ctx.activate();
     for (uint32_t si = 0; si < shards_per_gpu; ++si)
-      (void)ensure_prescreen(ctx, si, measure);
+      (void)ensure_prescreen(ctx, si, r.measure);
     ctx.ensure_shard_streams();
-    staged[g] = stage_query(ctx, q, nq, D, dtype, loc, q_gpu);
-    ctx.filter_bits = stage_filter(ctx);
+    staged[g] = stage_query(ctx, r.q, nq, r.D, r.dtype, r.loc, r.gpu);
+    const DeviceFilter df = resolve_filter(ctx, filter, DeviceCtx::kBlockingLane);
     GGNN_HIP_CHECK(hipEventRecord(ctx.ev_ready, ctx.stream));
     GGNN_HIP_CHECK(hipEventRecord(ctx.ev_a, ctx.stream));
     for (int half = 0; half < 2; ++half) {
@@ -265,14 +279,12 @@ void ggnn_handle::query_split(const void* q, uint32_t nq, uint32_t D, ggnn_dtype
         GGNN_HIP_CHECK(hipStreamWaitEvent(st, devs[0].xb[lane].consumed, 0));
       const size_t part = count[half] * row;
       grow_lane(ctx, lane, x.r_pack, 2 * part * 4);
-      int32_t* r = x.r_pack.as<int32_t>();
+      int32_t* rows = x.r_pack.as<int32_t>();
       const uint8_t* qh = static_cast<const uint8_t*>(staged[g].ptr) +
                           static_cast<size_t>(first[half]) * pad_D * es;
       // (each half sees its own half of the filter ids)
-      enqueue_local_search(ctx, lane, qh, count[half], k_query, tau_query, max_iterations,
-                           measure, r, reinterpret_cast<float*>(r + part), ctx.filter_bits,
-                           ctx.filter_ids ? ctx.filter_ids + first[half] : nullptr,
-                           ctx.filter_labeled);
+      enqueue_local_search(ctx, lane, r, qh, count[half], rows,
+                           reinterpret_cast<float*>(rows + part), df.from(first[half]));
       GGNN_HIP_CHECK(hipEventRecord(ctx.shard_done[lane], st));
       GGNN_HIP_CHECK(hipStreamWaitEvent(ctx.stream, ctx.shard_done[lane], 0));
     }
@@ -281,8 +293,9 @@ void ggnn_handle::query_split(const void* q, uint32_t nq, uint32_t D, ggnn_dtype
   // the first half is exchanged, merged and copied out while the second is still being searched
   for (int half = 0; half < 2; ++half)
     if (count[half])
-      exchange(half, count[half], k_query, row, ids_out + static_cast<size_t>(first[half]) * k_query,
-               dists_out + static_cast<size_t>(first[half]) * k_query, /*blocking=*/true);
+      exchange(half, count[half], k_query, row,
+               r.ids_out + static_cast<size_t>(first[half]) * k_query,
+               r.dists_out + static_cast<size_t>(first[half]) * k_query, /*blocking=*/true);
   for (DeviceCtx& ctx : devs) {
     ctx.activate();
     GGNN_HIP_CHECK(hipStreamSynchronize(ctx.stream));
@@ -332,23 +345,18 @@ void ggnn_handle::grow_lane(DeviceCtx& owner, int lane, DeviceBuffer& b, size_t 
 // thread; a blocking call does not wait for batches in flight (its buffers and stream are its
 // own), and a call that has to re-code the pre-screen copy for another measure first drains
 // every slot.
-void ggnn_handle::query_async(const void* d_query, uint64_t Nq, uint32_t D, ggnn_dtype dtype,
-                 ggnn_location loc, int q_gpu, uint32_t k_query, float tau_query,
-                 uint32_t max_iterations, ggnn_measure measure, int32_t* d_ids, float* d_dists,
-                 uint32_t slot, const int32_t* filter_ids, bool labeled)
+void ggnn_handle::query_async(const QueryRequest& r, uint32_t slot, const QueryFilter& filter)
 {
+  const void* const d_query = r.q;
+  const uint64_t Nq = r.Nq;
+  const ggnn_location loc = r.loc;
+  const int q_gpu = r.gpu;
+  const uint32_t k_query = r.k;
+  const ggnn_measure measure = r.measure;
+  int32_t* const d_ids = r.ids_out;
+  float* const d_dists = r.dists_out;
   GGNN_REQUIRE(has_graph(), GGNN_INVALID_STATE, "There is no graph to query.");
-  check_query(Nq, D, dtype, d_query);
-  GGNN_REQUIRE(!filter_ids || labeled || num_filters, GGNN_INVALID_STATE,
-               "There is no filter table the filter ids could refer to (ggnn_set_filters).");
-  GGNN_REQUIRE(!filter_ids || !labeled || !labels_host.empty(), GGNN_INVALID_STATE,
-               "There are no labels the query labels could refer to (ggnn_set_labels).");
-  // the resident table of the ids, or the resident label column of the query labels
-  auto resident = [&](DeviceCtx& ctx) -> const uint32_t* {
-    if (!filter_ids)
-      return nullptr;
-    return labeled ? place_labels(ctx) : place_filter_table(ctx);
-  };
+  check_query(Nq, r.D, r.dtype, d_query);
   GGNN_REQUIRE(!Nq || (d_ids != nullptr && d_dists != nullptr), GGNN_INVALID_ARGUMENT,
                "result pointers are null");
   GGNN_REQUIRE(!swapping(), GGNN_UNSUPPORTED,
@@ -377,16 +385,16 @@ void ggnn_handle::query_async(const void* d_query, uint64_t Nq, uint32_t D, ggnn
     for (uint32_t si = 0; si < shards_per_gpu; ++si)
       (void)ensure_prescreen(ctx, si, measure);
     ctx.ensure_shard_streams();
-    // (filter ids: device memory on this GPU like the query, nothing is staged)
-    enqueue_local_search(ctx, lane, d_query, nq, k_query, tau_query, max_iterations, measure,
-                         d_ids, d_dists, resident(ctx), filter_ids, labeled);
+    // (filter ids: device memory on this GPU like the query, used in place)
+    enqueue_local_search(ctx, lane, r, d_query, nq, d_ids, d_dists,
+                         resolve_filter(ctx, filter, lane));
     return;
   }
   GGNN_REQUIRE(pad_D == base_D, GGNN_UNSUPPORTED,
                "asynchronous queries need 16-byte rows (no padding is staged)");
   const size_t row = static_cast<size_t>(k_query) * shards_per_gpu;
   const size_t part = nq * row;
-  const size_t qbytes = Nq * static_cast<size_t>(pad_D) * dtype_size(dtype);
+  const size_t qbytes = Nq * static_cast<size_t>(pad_D) * dtype_size(r.dtype);
   for (DeviceCtx& ctx : devs) {
     ctx.activate();
     for (uint32_t si = 0; si < shards_per_gpu; ++si)
@@ -403,53 +411,32 @@ void ggnn_handle::query_async(const void* d_query, uint64_t Nq, uint32_t D, ggnn
     }
     // the filter ids follow the query's memory rule: used in place on their own GPU, else copied
     // on the lane's stream
-    const int32_t* f_here = filter_ids;
-    if (filter_ids && !(loc == GGNN_GPU && q_gpu == ctx.device &&
-                        (reinterpret_cast<uintptr_t>(filter_ids) & 3u) == 0)) {
-      grow_lane(ctx, lane, x.f_stage, Nq * sizeof(int32_t));
-      GGNN_HIP_CHECK(hipMemcpyAsync(x.f_stage.p, filter_ids, Nq * sizeof(int32_t),
-                                    hipMemcpyDefault, st));
-      f_here = x.f_stage.as<int32_t>();
-    }
+    const DeviceFilter df = resolve_filter(ctx, filter, lane);
     // (copy exchange: the first GPU may still be copying this lane's previous rows)
 #ifndef GGNN_EXP_NO_CONSUMED_WAIT  // (test-the-test hook)
     if (&ctx != &devs[0] && devs[0].xb[lane].consumed)
       GGNN_HIP_CHECK(hipStreamWaitEvent(st, devs[0].xb[lane].consumed, 0));
 #endif
     grow_lane(ctx, lane, x.r_pack, 2 * part * 4);
-    int32_t* r = x.r_pack.as<int32_t>();
-    enqueue_local_search(ctx, lane, q_here, nq, k_query, tau_query, max_iterations, measure, r,
-                         reinterpret_cast<float*>(r + part), resident(ctx), f_here, labeled);
+    int32_t* rows = x.r_pack.as<int32_t>();
+    enqueue_local_search(ctx, lane, r, q_here, nq, rows, reinterpret_cast<float*>(rows + part), df);
   }
   exchange(lane, nq, k_query, row, d_ids, d_dists, /*blocking=*/false);
 }
 
 // the shards of one GPU on one lane's stream, nothing waits
-void ggnn_handle::enqueue_local_search(DeviceCtx& ctx, int lane, const void* d_query, uint32_t nq,
-                          uint32_t k_query, float tau_query, uint32_t max_iterations,
-                          ggnn_measure measure, int32_t* d_ids, float* d_dists,
-                          const uint32_t* filter_bits, const int32_t* filter_ids,
-                          bool labeled)
+void ggnn_handle::enqueue_local_search(DeviceCtx& ctx, int lane, const QueryRequest& r,
+                                       const void* d_query, uint32_t nq, int32_t* d_ids,
+                                       float* d_dists, const DeviceFilter& df)
 {
   hipStream_t stream = ctx.lane_stream(lane);
   for (uint32_t si = 0; si < shards_per_gpu; ++si) {
     const Shard& sh = ctx.shards[si];
-    QueryLaunch ql{shard_base(ctx, si), d_query, base_dtype, cfg.N, pad_D, nq, sh.graph,
-                   cfg.KBuild, sh.translation + cfg.STs_offsets[kLayers - 1], cfg.S,
-                   sh.nn1_stats, k_query, tau_query, max_iterations, measure, shards_per_gpu, si,
-                   d_ids, d_dists, nullptr, nullptr};
-    if (sh.ps_state > 0 && sh.ps_measure == measure) {
-      ql.ps_codes = sh.ps_codes.as<uint8_t>();
-      ql.ps_params = sh.ps_params.as<float>();
-      ql.ps_Dc = prescreen_code_dim(pad_D);
-    }
-    ql.filter_bits = filter_bits;
-    ql.filter_bit_offset = sh.global_id * cfg.N;
-    ql.filter_table = launch_filter_table(ctx, filter_ids, labeled);
-    launch_query(ql, stream);
+    const bool use_ps = sh.ps_state > 0 && sh.ps_measure == r.measure;
+    launch_query(shard_launch(ctx, si, r, d_query, nq, d_ids, d_dists, use_ps, df), stream);
   }
   if (shards_per_gpu > 1)
-    launch_sort_shard_results(nq, k_query * shards_per_gpu, d_ids, d_dists, stream);
+    launch_sort_shard_results(nq, r.k * shards_per_gpu, d_ids, d_dists, stream);
 }
 
 // wait for the batches enqueued on one slot only (the other slots keep running)
@@ -475,15 +462,17 @@ void ggnn_handle::synchronize()
 }
 
 // GGNNImpl::bfQueryImpl, ggnn.cu:332-390
-void ggnn_handle::bf_query(const void* q, uint64_t Nq, uint32_t D, ggnn_dtype dtype, ggnn_location loc,
-              int q_gpu, uint32_t k_gt, ggnn_measure measure, int32_t* ids_out,
-              float* dists_out, ggnn_location out_loc)
+void ggnn_handle::bf_query(const QueryRequest& r, const QueryFilter& filter)
 {
+  const uint64_t Nq = r.Nq;
+  const uint32_t k_gt = r.k;
+  int32_t* const ids_out = r.ids_out;
+  float* const dists_out = r.dists_out;
   GGNN_REQUIRE(base_set, GGNN_INVALID_STATE,
                "There is no base dataset loaded which could be queried.");
   GGNN_REQUIRE(devs.size() <= 1, GGNN_INVALID_STATE,
                "The brute-force query only supports a single GPU.");
-  check_query(Nq, D, dtype, q);
+  check_query(Nq, r.D, r.dtype, r.q);
   if (devs.empty()) {
     // no graph yet: make the whole base resident on the (first) selected GPU
     const std::vector<int> gpus = resolve_gpus();
@@ -513,9 +502,9 @@ void ggnn_handle::bf_query(const void* q, uint64_t Nq, uint32_t D, ggnn_dtype dt
       GGNN_HIP_CHECK(hipMemcpyAsync(whole_base.p, base_src, whole_base.bytes, kind, ctx.stream));
     bf_base = whole_base.p;
   }
-  Staged sq = stage_query(ctx, q, Nq, D, dtype, loc, q_gpu);
+  Staged sq = stage_query(ctx, r.q, Nq, r.D, r.dtype, r.loc, r.gpu);
   const uint32_t nq = static_cast<uint32_t>(Nq);
-  const bool direct = (out_loc == GGNN_GPU);
+  const bool direct = (r.out_loc == GGNN_GPU);
   DeviceBuffer r_ids, r_dists;
   int32_t* d_ids = ids_out;
   float* d_dists = dists_out;
@@ -528,9 +517,10 @@ void ggnn_handle::bf_query(const void* q, uint64_t Nq, uint32_t D, ggnn_dtype dt
   if (!ctx.bf_rescanned.p)
     ctx.bf_rescanned.alloc(sizeof(uint32_t));
   BfLaunch bl{bf_base, sq.ptr, base_dtype, static_cast<uint32_t>(base_N), pad_D, nq, k_gt,
-              measure,    d_ids,  d_dists,    ctx.bf_rescanned.as<uint32_t>()};
-  bl.filter_bits = stage_filter(ctx);
-  bl.filter_table = launch_filter_table(ctx, ctx.filter_ids, ctx.filter_labeled);
+              r.measure,  d_ids,  d_dists,    ctx.bf_rescanned.as<uint32_t>()};
+  const DeviceFilter df = resolve_filter(ctx, filter, DeviceCtx::kBlockingLane);
+  bl.filter_bits = df.bits;
+  bl.filter_table = df.table;
   EventTimer timer(ctx.stream, ctx.ev_a, ctx.ev_b);
   launch_bf_query(bl, ctx.stream);
   bf_ms = timer.stop();
@@ -547,90 +537,84 @@ void ggnn_handle::bf_query(const void* q, uint64_t Nq, uint32_t D, ggnn_dtype dt
   GGNN_HIP_CHECK(hipStreamSynchronize(ctx.stream));
 }
 
-// ---- filtered calls ---------------------------------------------------------------------------
-void ggnn_handle::begin_filter(const uint32_t* bits, uint64_t n_bits, ggnn_location loc, int gpu)
+// ---- the filter of one call: validated as the caller gave it, then resolved per GPU -------------
+QueryFilter QueryFilter::bitset(const ggnn_handle& h, const uint32_t* bits, uint64_t n_bits,
+                                ggnn_location loc, int gpu)
 {
   GGNN_REQUIRE(bits != nullptr, GGNN_INVALID_ARGUMENT, "the filter bitset is null");
-  GGNN_REQUIRE(!base_set || n_bits == base_N, GGNN_INVALID_ARGUMENT,
+  GGNN_REQUIRE(!h.base_set || n_bits == h.base_N, GGNN_INVALID_ARGUMENT,
                "the filter needs one bit per base vector (n_bits must equal N)");
-  GGNN_REQUIRE(base_set, GGNN_INVALID_STATE, "There is no base dataset the filter could refer to.");
-  active_filter.bits = bits;
-  active_filter.n_bits = n_bits;
-  active_filter.loc = loc;
-  active_filter.gpu = gpu;
+  GGNN_REQUIRE(h.base_set, GGNN_INVALID_STATE, "There is no base dataset the filter could refer to.");
+  return {Bitset, bits, n_bits, loc, gpu};
 }
 
-void ggnn_handle::end_filter()
+QueryFilter QueryFilter::table_ids(const ggnn_handle& h, const int32_t* ids, uint64_t Nq,
+                                   ggnn_location loc, int gpu, bool read_host_ids)
 {
-  active_filter = FilterSpec{};
-  active_filter_ids = FilterIdSpec{};
-  for (DeviceCtx& ctx : devs) {
-    ctx.filter_bits = nullptr;
-    ctx.filter_ids = nullptr;
-    ctx.filter_labeled = false;
+  GGNN_REQUIRE(h.num_filters != 0, GGNN_INVALID_STATE,
+               "There is no filter table the filter ids could refer to (ggnn_set_filters).");
+  GGNN_REQUIRE(!Nq || ids != nullptr, GGNN_INVALID_ARGUMENT, "the filter id array is null");
+  if (read_host_ids && loc == GGNN_CPU)
+    for (uint64_t i = 0; i < Nq; ++i)
+      GGNN_REQUIRE(ids[i] >= -1 && ids[i] < static_cast<int64_t>(h.num_filters),
+                   GGNN_INVALID_ARGUMENT,
+                   "filter id " + std::to_string(ids[i]) + " of query " + std::to_string(i) +
+                       " is outside [-1, " + std::to_string(h.num_filters) + ")");
+  return {TableIds, ids, Nq, loc, gpu};
+}
+
+QueryFilter QueryFilter::labels(const ggnn_handle& h, const int32_t* query_labels, uint64_t Nq,
+                                ggnn_location loc, int gpu)
+{
+  GGNN_REQUIRE(!h.labels_host.empty(), GGNN_INVALID_STATE,
+               "There are no labels the query labels could refer to (ggnn_set_labels).");
+  GGNN_REQUIRE(!Nq || query_labels != nullptr, GGNN_INVALID_ARGUMENT,
+               "the query label array is null");
+  // (every int32 is a valid label: nothing to validate)
+  return {Labels, query_labels, Nq, loc, gpu};
+}
+
+DeviceFilter ggnn_handle::resolve_filter(DeviceCtx& ctx, const QueryFilter& f, int lane)
+{
+  DeviceFilter d;
+  if (f.kind == QueryFilter::None)
+    return d;
+  // what is resident: the filter table, or the label column (the kernels read it through
+  // filter_bits, common.hpp: the only place that casts it)
+  if (f.kind == QueryFilter::TableIds) {
+    d.bits = place_filter_table(ctx);
+    d.table.words = filter_words;
+    d.table.num_filters = num_filters;
+    d.table.consts = d.bits + static_cast<size_t>(num_filters) * filter_words;
   }
-}
-
-const uint32_t* ggnn_handle::stage_filter(DeviceCtx& ctx)
-{
-  if (const FilterIdSpec& fi = active_filter_ids; fi.ids) {
-    // per-query filters: the resident table (label filters: the resident label column), and the
-    // id (label) array beside the query
-    const uint32_t* table = fi.labeled ? place_labels(ctx) : place_filter_table(ctx);
-    ctx.filter_labeled = fi.labeled;
-    if (fi.loc == GGNN_GPU && fi.gpu == ctx.device && (reinterpret_cast<uintptr_t>(fi.ids) & 3u) == 0)
-      ctx.filter_ids = fi.ids;
-    else {
-      const size_t bytes = fi.count * sizeof(int32_t);
-      DeviceCtx::grow(ctx.filter_ids_stage, bytes);
-      GGNN_HIP_CHECK(hipMemcpyAsync(ctx.filter_ids_stage.p, fi.ids, bytes,
-                                    fi.loc == GGNN_GPU ? hipMemcpyDefault : hipMemcpyHostToDevice,
-                                    ctx.stream));
-      ctx.filter_ids = ctx.filter_ids_stage.as<int32_t>();
-    }
-    return table;
+  else if (f.kind == QueryFilter::Labels)
+    d.bits = reinterpret_cast<const uint32_t*>(place_labels(ctx));
+  // what the caller brought (bitset words, filter ids, query labels): used in place on its own
+  // GPU, else copied on the lane's stream
+  const bool blocking = lane == DeviceCtx::kBlockingLane;
+  const void* here = f.ptr;
+  if (!(f.loc == GGNN_GPU && f.gpu == ctx.device && (reinterpret_cast<uintptr_t>(f.ptr) & 3u) == 0)) {
+    const bool bitset = f.kind == QueryFilter::Bitset;
+    const size_t bytes = static_cast<size_t>(bitset ? (f.count + 31) / 32 : f.count) * 4;
+    DeviceBuffer& stage = bitset     ? ctx.filter_stage
+                          : blocking ? ctx.filter_ids_stage
+                                     : ctx.xb[lane].f_stage;
+    if (blocking)
+      DeviceCtx::grow(stage, bytes);
+    else
+      grow_lane(ctx, lane, stage, bytes);
+    GGNN_HIP_CHECK(hipMemcpyAsync(stage.p, f.ptr, bytes,
+                                  f.loc == GGNN_GPU ? hipMemcpyDefault : hipMemcpyHostToDevice,
+                                  ctx.lane_stream(lane)));
+    here = stage.p;
   }
-  const FilterSpec& f = active_filter;
-  if (!f.bits)
-    return nullptr;
-  if (f.loc == GGNN_GPU && f.gpu == ctx.device && (reinterpret_cast<uintptr_t>(f.bits) & 3u) == 0)
-    return f.bits;
-  const size_t bytes = static_cast<size_t>((f.n_bits + 31) / 32) * sizeof(uint32_t);
-  DeviceCtx::grow(ctx.filter_stage, bytes);
-  GGNN_HIP_CHECK(hipMemcpyAsync(ctx.filter_stage.p, f.bits, bytes,
-                                f.loc == GGNN_GPU ? hipMemcpyDefault : hipMemcpyHostToDevice,
-                                ctx.stream));
-  return ctx.filter_stage.as<uint32_t>();
-}
-
-namespace {
-struct FilterScope {
-  ggnn_handle& h;
-  ~FilterScope() { h.end_filter(); }
-};
-}  // namespace
-
-void ggnn_handle::query_filtered(const void* q, uint64_t Nq, uint32_t D, ggnn_dtype dtype,
-                                 ggnn_location loc, int q_gpu, uint32_t k_query, float tau_query,
-                                 uint32_t max_iterations, ggnn_measure measure, int32_t* ids_out,
-                                 float* dists_out, ggnn_location out_loc, const uint32_t* bits,
-                                 uint64_t n_bits, ggnn_location filter_loc, int filter_gpu)
-{
-  begin_filter(bits, n_bits, filter_loc, filter_gpu);
-  FilterScope scope{*this};
-  query(q, Nq, D, dtype, loc, q_gpu, k_query, tau_query, max_iterations, measure, ids_out,
-        dists_out, out_loc);
-}
-
-void ggnn_handle::bf_query_filtered(const void* q, uint64_t Nq, uint32_t D, ggnn_dtype dtype,
-                                    ggnn_location loc, int q_gpu, uint32_t k_gt,
-                                    ggnn_measure measure, int32_t* ids_out, float* dists_out,
-                                    ggnn_location out_loc, const uint32_t* bits, uint64_t n_bits,
-                                    ggnn_location filter_loc, int filter_gpu)
-{
-  begin_filter(bits, n_bits, filter_loc, filter_gpu);
-  FilterScope scope{*this};
-  bf_query(q, Nq, D, dtype, loc, q_gpu, k_gt, measure, ids_out, dists_out, out_loc);
+  switch (f.kind) {
+    case QueryFilter::Bitset: d.bits = static_cast<const uint32_t*>(here); break;
+    case QueryFilter::TableIds: d.table.ids = static_cast<const int32_t*>(here); break;
+    case QueryFilter::Labels: d.table.query_labels = static_cast<const int32_t*>(here); break;
+    case QueryFilter::None: break;
+  }
+  return d;
 }
 
 // ---- per-query filters: resident filter table, one filter id per query ------------------------
@@ -742,63 +726,6 @@ void ggnn_handle::place_filter_tables()
     (void)place_filter_table(ctx);
 }
 
-FilterTable ggnn_handle::launch_filter_table(const DeviceCtx& ctx, const int32_t* ids,
-                                             bool labeled) const
-{
-  FilterTable t{};
-  if (!ids)
-    return t;
-  if (labeled) {
-    t.query_labels = ids;
-    return t;
-  }
-  t.ids = ids;
-  t.words = filter_words;
-  t.num_filters = num_filters;
-  t.consts = ctx.filter_table.as<uint32_t>() + static_cast<size_t>(num_filters) * filter_words;
-  return t;
-}
-
-void ggnn_handle::begin_filter_ids(const int32_t* ids, uint64_t Nq, ggnn_location loc, int gpu)
-{
-  GGNN_REQUIRE(num_filters != 0, GGNN_INVALID_STATE,
-               "There is no filter table the filter ids could refer to (ggnn_set_filters).");
-  GGNN_REQUIRE(!Nq || ids != nullptr, GGNN_INVALID_ARGUMENT, "the filter id array is null");
-  if (loc == GGNN_CPU)
-    for (uint64_t i = 0; i < Nq; ++i)
-      GGNN_REQUIRE(ids[i] >= -1 && ids[i] < static_cast<int64_t>(num_filters),
-                   GGNN_INVALID_ARGUMENT,
-                   "filter id " + std::to_string(ids[i]) + " of query " + std::to_string(i) +
-                       " is outside [-1, " + std::to_string(num_filters) + ")");
-  active_filter_ids.ids = ids;
-  active_filter_ids.count = Nq;
-  active_filter_ids.loc = loc;
-  active_filter_ids.gpu = gpu;
-}
-
-void ggnn_handle::query_filtered_by(const void* q, uint64_t Nq, uint32_t D, ggnn_dtype dtype,
-                                    ggnn_location loc, int q_gpu, uint32_t k_query,
-                                    float tau_query, uint32_t max_iterations, ggnn_measure measure,
-                                    int32_t* ids_out, float* dists_out, ggnn_location out_loc,
-                                    const int32_t* filter_ids, ggnn_location ids_loc, int ids_gpu)
-{
-  begin_filter_ids(filter_ids, Nq, ids_loc, ids_gpu);
-  FilterScope scope{*this};
-  query(q, Nq, D, dtype, loc, q_gpu, k_query, tau_query, max_iterations, measure, ids_out,
-        dists_out, out_loc);
-}
-
-void ggnn_handle::bf_query_filtered_by(const void* q, uint64_t Nq, uint32_t D, ggnn_dtype dtype,
-                                       ggnn_location loc, int q_gpu, uint32_t k_gt,
-                                       ggnn_measure measure, int32_t* ids_out, float* dists_out,
-                                       ggnn_location out_loc, const int32_t* filter_ids,
-                                       ggnn_location ids_loc, int ids_gpu)
-{
-  begin_filter_ids(filter_ids, Nq, ids_loc, ids_gpu);
-  FilterScope scope{*this};
-  bf_query(q, Nq, D, dtype, loc, q_gpu, k_gt, measure, ids_out, dists_out, out_loc);
-}
-
 // ---- label filters: a resident int32 label per base vector, one label per query ----------------
 void ggnn_handle::drop_labels()
 {
@@ -898,11 +825,11 @@ void ggnn_handle::update_labels(const int64_t* ids, const int32_t* values, uint6
   }
 }
 
-const uint32_t* ggnn_handle::place_labels(DeviceCtx& ctx)
+const int32_t* ggnn_handle::place_labels(DeviceCtx& ctx)
 {
   GGNN_REQUIRE(!labels_host.empty(), GGNN_INVALID_STATE, "There are no labels (ggnn_set_labels).");
   if (ctx.labels_epoch == labels_epoch && ctx.labels.p)
-    return ctx.labels.as<uint32_t>();
+    return ctx.labels.as<int32_t>();
   ctx.activate();
   ctx.labels_epoch = 0;
   ctx.labels.alloc(labels_host.size() * sizeof(int32_t));
@@ -910,7 +837,7 @@ const uint32_t* ggnn_handle::place_labels(DeviceCtx& ctx)
                            hipMemcpyHostToDevice));
   GGNN_HIP_CHECK(hipDeviceSynchronize());
   ctx.labels_epoch = labels_epoch;
-  return ctx.labels.as<uint32_t>();
+  return ctx.labels.as<int32_t>();
 }
 
 void ggnn_handle::place_labels_everywhere()
@@ -920,41 +847,4 @@ void ggnn_handle::place_labels_everywhere()
   DeviceRestoreGuard keep;
   for (DeviceCtx& ctx : devs)
     (void)place_labels(ctx);
-}
-
-void ggnn_handle::begin_query_labels(const int32_t* labels, uint64_t Nq, ggnn_location loc, int gpu)
-{
-  GGNN_REQUIRE(!labels_host.empty(), GGNN_INVALID_STATE,
-               "There are no labels the query labels could refer to (ggnn_set_labels).");
-  GGNN_REQUIRE(!Nq || labels != nullptr, GGNN_INVALID_ARGUMENT, "the query label array is null");
-  // (every int32 is a valid label: nothing to validate)
-  active_filter_ids.ids = labels;
-  active_filter_ids.count = Nq;
-  active_filter_ids.loc = loc;
-  active_filter_ids.gpu = gpu;
-  active_filter_ids.labeled = true;
-}
-
-void ggnn_handle::query_labeled(const void* q, uint64_t Nq, uint32_t D, ggnn_dtype dtype,
-                                ggnn_location loc, int q_gpu, uint32_t k_query, float tau_query,
-                                uint32_t max_iterations, ggnn_measure measure, int32_t* ids_out,
-                                float* dists_out, ggnn_location out_loc,
-                                const int32_t* query_labels, ggnn_location labels_loc,
-                                int labels_gpu)
-{
-  begin_query_labels(query_labels, Nq, labels_loc, labels_gpu);
-  FilterScope scope{*this};
-  query(q, Nq, D, dtype, loc, q_gpu, k_query, tau_query, max_iterations, measure, ids_out,
-        dists_out, out_loc);
-}
-
-void ggnn_handle::bf_query_labeled(const void* q, uint64_t Nq, uint32_t D, ggnn_dtype dtype,
-                                   ggnn_location loc, int q_gpu, uint32_t k_gt,
-                                   ggnn_measure measure, int32_t* ids_out, float* dists_out,
-                                   ggnn_location out_loc, const int32_t* query_labels,
-                                   ggnn_location labels_loc, int labels_gpu)
-{
-  begin_query_labels(query_labels, Nq, labels_loc, labels_gpu);
-  FilterScope scope{*this};
-  bf_query(q, Nq, D, dtype, loc, q_gpu, k_gt, measure, ids_out, dists_out, out_loc);
 }

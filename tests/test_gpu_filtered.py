@@ -377,3 +377,67 @@ def test_handle_query_filtered_out_of_core(orc):
     assert np.array_equal(d, r_d)
     fin = np.isfinite(d)
     assert fin.any() and allowed[ids[fin]].all()
+
+
+def test_calls_of_one_handle_do_not_leak_into_one_another(tmp_path):
+    """Every query mode in turn on ONE handle, a failing filtered call and an asynchronous batch in
+    flight among them: each filtered result equals, bit for bit, the same call made alone on a
+    freshly loaded handle of the same graph, and the plain query before and after them is
+    untouched -- whether a search is filtered depends on its own arguments only."""
+    import ggnn_amd as ggnn
+    torch = _torch()
+    K, tau, iters, nq, F = 10, 0.7, 200, 50, 3
+    rs = np.random.default_rng(4711)
+    base = rs.integers(0, 128, (N, D)).astype(np.float32)
+    q = rs.integers(0, 128, (nq, D)).astype(np.float32)
+    mask = rs.random(N) < 0.3
+    table = rs.random((F, N)) < 0.4
+    fids = rs.integers(-1, F, nq).astype(np.int32)
+    labels = rs.integers(0, 4, N).astype(np.int32)
+    qlabels = rs.integers(0, 4, nq).astype(np.int32)
+
+    def handle(load):
+        e = ggnn.GGNN()
+        e.set_base(base)
+        e.set_working_directory(str(tmp_path))
+        if load:
+            e.load(24)
+        else:
+            e.build(24, 0.5, 1)
+            e.store()
+        e.set_filters(table)
+        e.set_labels(labels)
+        return e
+
+    def same(a, b):
+        return torch.equal(a[0].cpu(), b[0].cpu()) and torch.equal(a[1].cpu(), b[1].cpu())
+
+    eng = handle(load=False)
+    plain = eng.query(q, K, tau, iters)
+    by_mask = eng.query_filtered(q, K, tau, iters, filter=mask)
+    by_ids = eng.query_filtered_by(q, K, tau, iters, filter_ids=fids)
+    by_label = eng.query_labeled(q, K, tau, iters, labels=qlabels)
+    bf_ids, bf_d = eng.bf_query_filtered(q, K, filter=mask)
+    assert mask[bf_ids.numpy()].all() and np.isfinite(bf_d.numpy()).all()
+    with pytest.raises(RuntimeError, match="query dimension does not match the base"):
+        eng.query_filtered(q[:, :D - 16].copy(), K, tau, iters, filter=mask)
+    plain_again = eng.query(q, K, tau, iters)
+    d_q = torch.from_numpy(q).cuda()
+    ticket = eng.query_async_labeled(d_q, K, tau, iters, slot=0, labels=qlabels)
+    by_ids_meanwhile = eng.query_filtered_by(q, K, tau, iters, filter_ids=fids)
+    eng.synchronize()
+
+    alone = handle(load=True)
+    assert same(by_mask, alone.query_filtered(q, K, tau, iters, filter=mask))
+    alone = handle(load=True)
+    assert same(by_ids, alone.query_filtered_by(q, K, tau, iters, filter_ids=fids))
+    assert same(by_ids_meanwhile, by_ids)
+    alone = handle(load=True)
+    assert same(by_label, alone.query_labeled(q, K, tau, iters, labels=qlabels))
+    alone.set_return_results_on_gpu(True)
+    on_gpu = alone.query_labeled(d_q, K, tau, iters, labels=qlabels)
+    assert ticket.ids.is_cuda and ticket.ids.shape == on_gpu[0].shape
+    assert same((ticket.ids, ticket.dists), on_gpu)
+    assert same(plain, plain_again)
+    for filtered in (by_mask, by_ids, by_label):
+        assert not same(plain, filtered)      # (or the above would hold vacuously)
