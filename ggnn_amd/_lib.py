@@ -167,6 +167,17 @@ SIGNATURES = {
     "ggnn_op_bf_query_certified": (_int, [_vp, _int, _u32, _u32, _vp, _u32, _u32, _int, _vp, _vp,
                                           _vp, _vp]),
     "ggnn_last_bf_query_rescanned": (_int, [_vp, C.POINTER(_u32)]),
+    "ggnn_last_bf_query_matrix_path": (_int, [_vp, C.POINTER(C.c_int)]),
+    # the filtered brute-force calls + (n_rescanned: device, matrix_path: host int)
+    "ggnn_op_bf_query_filtered_certified": (_int, [_vp, _int, _u32, _u32, _vp, _u32, _u32, _int,
+                                                   _vp, _vp, _vp, _u32, _vp, C.POINTER(C.c_int),
+                                                   _vp]),
+    "ggnn_op_bf_query_filtered_by_certified": (_int, [_vp, _int, _u32, _u32, _vp, _u32, _u32, _int,
+                                                      _vp, _vp, _vp, _u32, _u64, _vp, _u32, _vp,
+                                                      C.POINTER(C.c_int), _vp]),
+    "ggnn_op_bf_query_labeled_certified": (_int, [_vp, _int, _u32, _u32, _vp, _u32, _u32, _int,
+                                                  _vp, _vp, _vp, _u64, _vp, _u32, _vp,
+                                                  C.POINTER(C.c_int), _vp]),
     "ggnn_last_exchange": (C.c_char_p, [_vp]),
     "ggnn_op_top": (_int, [_vp, _int, _u32, _int, _u32, _vp, _u32, _u32, _u32, _u32, _vp, _vp,
                            _vp]),

@@ -799,6 +799,13 @@ class GGNN:
         self._check(lib().ggnn_last_bf_query_rescanned(self._h, C.byref(n)))
         return int(n.value)
 
+    def last_bf_query_matrix_path(self):
+        """1 if the last bf_query* call (filtered or not) ran the matrix-core tile kernel on every
+        shard, else 0 (the scan kernels); results are bit-identical on either path"""
+        n = C.c_int()
+        self._check(lib().ggnn_last_bf_query_matrix_path(self._h, C.byref(n)))
+        return int(n.value)
+
     def last_query_counters(self):
         d, p = C.c_uint64(), C.c_uint64()
         self._check(lib().ggnn_last_query_counters(self._h, C.byref(d), C.byref(p)))

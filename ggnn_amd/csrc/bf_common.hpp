@@ -36,6 +36,46 @@ struct BfMfmaArgs {
   uint64_t total_tiles;      // query blocks * tiles_per_q
 };
 
+// Filter mode of bf_mfma_kernel (template parameter FM).  The filtered instantiations live in
+// translation units of their own (bf_mfma_bits.hip, bf_mfma_labels.hip); the unfiltered kernels
+// keep their argument block.
+//   kBfBits    a bitset row per query: the call's one bitset for every query, or the row of the
+//              filter table that the query's filter id names
+//   kBfLabels  an int32 label per base row against one per query
+constexpr int kBfNoFilter = 0, kBfBits = 1, kBfLabels = 2;
+struct BfMfmaFilteredArgs : BfMfmaArgs {
+  const uint32_t* filter_bits;  // bitset / filter table / label column (BfLaunch)
+  uint32_t filter_bit_offset;   // kBfBits: a multiple of 32
+  FilterTable filter_table;
+};
+template <int FM>
+using BfMfmaArgsOf = std::conditional_t<FM != kBfNoFilter, BfMfmaFilteredArgs, BfMfmaArgs>;
+// LDS words behind the thresholds (single chunk) / the group norms (chunked) of a filtered kernel
+//   kBfBits    verdict words of the block's 128 queries: [2][128], chunked [2][T][128]
+//   kBfLabels  128 query labels; chunked: + [2][T][32] row labels beside the group norms
+constexpr uint32_t bf_filter_lds_words(int fm, uint32_t T)
+{
+  return fm == kBfBits     ? 2u * T * kBfQueriesPerBlock
+         : fm == kBfLabels ? kBfQueriesPerBlock + (T > 1 ? 2u * T * kBfTileRows : 0u)
+                           : 0u;
+}
+// The filtered SINGLE-CHUNK kernels exist with the list length as a compile-time constant only
+// (KPC = 18: k <= 10, shorter lists are rounded up -- any list longer than k is exact).  With a
+// run-time list length the single-chunk kernels do not hold three waves per SIMD without a private
+// segment (the unfiltered ones keep 12 to 52 bytes at NU = 12 / 16, the filtered ones came out at
+// 12 to 76; longer constants, 64 and 120, made the compiler unroll the list loops and spill
+// hundreds of bytes).  A filtered call with k > 10 and D <= 128 therefore runs the CHUNKED kernel
+// with its one chunk of 128 columns (columns past D are zero in the query operand): two waves per
+// SIMD, run-time list length, private segment 0.
+constexpr uint32_t kBfFilteredSingleChunkKP = 18;
+constexpr bool bf_filtered_runs_chunked(uint32_t D, uint32_t k_query)
+{
+  return D > 128 || k_query + 8 > kBfFilteredSingleChunkKP;
+}
+// the filtered tile kernel of a launch (defined in the filtered translation units)
+const void* bf_mfma_bits_kernel(ggnn_dtype dtype, ggnn_measure measure, int T, int NU, int KPC);
+const void* bf_mfma_labels_kernel(ggnn_dtype dtype, ggnn_measure measure, int T, int NU, int KPC);
+
 typedef int i32x16 __attribute__((ext_vector_type(16)));
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 constexpr uint32_t kBfI8RowStride = 144;

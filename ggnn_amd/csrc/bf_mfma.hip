@@ -34,6 +34,20 @@
 //   (2D+8)u of the true |1 - cos| in absolute terms (|cos| <= 1), so E = 2.02 (2D+8) u.
 //   uint8 rows on the i8 path: every quantity is an exact integer < 2^24, a left-out row is
 //   preceded by KP > K rows of its own slice in exact (distance, index) order: nothing to check.
+//
+// Under a filter (FM = kBfBits / kBfLabels: a bitset row or a label per query, FilterStage below)
+//   A (query, row) pair the filter denies gets d_e = +inf before the threshold ballot, nothing
+//   else changes: the lists keep the KP smallest ALLOWED (d_e, index).  The certificate holds as
+//   it stands:
+//     - a left-out allowed row of slice s still has d_e >= w_s;
+//     - the maximum row norm is taken over ALL rows, at least the maximum over the allowed ones,
+//       so E can only grow: the test stays conservative;
+//     - count < K means that some list of every part is not full, so every allowed row of that
+//       query is a candidate; unfilled result slots are (kEmptyKey, +inf), the filtered convention;
+//     - queries without a certificate are answered by the FILTERED scan kernels (bf_query.hip:
+//       launch_bf_rescan forwards the launch's filter with the query list, and a re-scanned query
+//       picks its filter by its real index qlist[i], not by its position i).
+//   Filtered launches that keep the scan: launch_bf_query (bf_query.hip).
 #include <cstdlib>
 
 #include "bf_common.hpp"
@@ -130,6 +144,7 @@ __global__ void __launch_bounds__(256) row_norms_kernel(const BaseT* data, uint3
   }
 }
 
+#ifndef GGNN_BF_FILTER_TU  // (kernels and host code that exist once: not in the filtered units)
 // out = fl(in - mean), row by row: the query set is shifted once, up front (it is small), so that
 // the tile kernels load their A operand without touching the mean
 __global__ void __launch_bounds__(256) shift_rows_kernel(const float* in, uint64_t n4, uint32_t D,
@@ -188,6 +203,7 @@ __global__ void __launch_bounds__(256) col_mean_final_kernel(const float* partia
   // data the mean of which is not finite is left unshifted (the certificate then decides)
   mean[c] = (fabsf(m) < inf_f()) ? m : 0.f;
 }
+#endif  // GGNN_BF_FILTER_TU
 
 // ---- 2. tile kernel -------------------------------------------------------------------------------
 // The K dimension is processed in chunks of CW = 2*Dh columns (Dh = 64 when D > 128, otherwise
@@ -652,6 +668,90 @@ GGNN_DEV float bf_expand(float dot, float qn, float bn, bool jvalid)
   return jvalid ? d : inf_f();
 }
 
+// What a filtered kernel (FM, bf_common.hpp) stages beside a tile, with the tile's own schedule:
+// loaded with the tile (an unconditional, clamped load like the row norm: see TileStage<float>::load),
+// stored to LDS with it, read by the epilogue from LDS -- the tile loop gains no global load that
+// is first used inside the loop.  A (query, base row) pair that the filter denies gets the
+// expanded-form distance +inf before the threshold ballot: it never enters a list.
+//   store_single: single-chunk kernel, buffer buf of the double-buffered tile
+//   store_group:  chunked kernel, slot = group parity * T + tile of the group (as bn_grp)
+template <int FM>
+struct FilterStage {  // kBfNoFilter: nothing
+  GGNN_DEV void open(const BfMfmaArgs&, uint32_t) {}
+  GGNN_DEV void load(const BfMfmaArgs&, uint32_t, uint32_t) {}
+  GGNN_DEV void store_single(float*, uint32_t, uint32_t, uint32_t*, uint32_t) const {}
+  GGNN_DEV void store_group(uint32_t*, uint32_t) const {}
+};
+// kBfBits: a tile is 32 consecutive rows that start at a multiple of 32 and the bit offset is a
+// multiple of 32 (the launcher sends every other offset to the scan), so ONE word of a query's
+// bitset holds its verdicts for the whole tile.  Thread t stages the word of query t & 127 of the
+// block (both halves of the workgroup load, threads 0..127 store).  The bitset is chosen once per
+// segment, as wave_filter_bits() chooses it: the call's bitset without filter ids, otherwise the
+// table row of an id in [0, num_filters) -- an UNSIGNED compare --, the all-ones row for -1 and
+// the all-zero row for everything else.  No id value forms an address outside table / consts.
+template <>
+struct FilterStage<kBfBits> {
+  const uint32_t* row;
+  uint32_t w;
+  GGNN_DEV void open(const BfMfmaFilteredArgs& a, uint32_t qblock)
+  {
+    const FilterTable& t = a.filter_table;
+    row = a.filter_bits;
+    if (t.ids) {
+      // (padding queries read the filter of the last query: nothing ever enters their lists)
+      const uint32_t q = min(qblock * kBfQueriesPerBlock + (threadIdx.x & 127u), a.Nq - 1);
+      const int32_t f = t.ids[q];
+      const uint32_t* c = t.consts + (f == -1 ? 0u : t.words);
+      row = static_cast<uint32_t>(f) < t.num_filters
+                ? a.filter_bits + static_cast<size_t>(static_cast<uint32_t>(f)) * t.words
+                : c;
+    }
+  }
+  // (row0 >= end: a group's padding tile re-reads the word of the last row)
+  GGNN_DEV void load(const BfMfmaFilteredArgs& a, uint32_t row0, uint32_t end)
+  {
+    w = row[(min(row0, end - 1) + a.filter_bit_offset) >> 5];
+  }
+  GGNN_DEV void store_single(float*, uint32_t, uint32_t, uint32_t* filt, uint32_t buf) const
+  {
+    if (threadIdx.x < (uint32_t)kBfQueriesPerBlock)
+      filt[buf * kBfQueriesPerBlock + threadIdx.x] = w;
+  }
+  GGNN_DEV void store_group(uint32_t* filt, uint32_t slot) const
+  {
+    if (threadIdx.x < (uint32_t)kBfQueriesPerBlock)
+      filt[slot * kBfQueriesPerBlock + threadIdx.x] = w;
+  }
+};
+// kBfLabels: the label of tile row threadIdx.x & 31, staged beside its norm -- the spare word
+// [CW + 1] of the tile row (DP - CW >= 4, the norm sits at [CW]) in the single-chunk kernel, a
+// sibling of bn_grp behind the 128 query labels in the chunked one.  Labels are compared, never
+// used as an index (LabelFilter, traversal.hpp):  denied = (ql != -1) && (ql != row label).
+template <>
+struct FilterStage<kBfLabels> {
+  int32_t w;
+  GGNN_DEV void open(const BfMfmaFilteredArgs&, uint32_t) {}
+  GGNN_DEV void load(const BfMfmaFilteredArgs& a, uint32_t row0, uint32_t end)
+  {
+    const int32_t* labels = reinterpret_cast<const int32_t*>(a.filter_bits) + a.filter_bit_offset;
+    w = labels[min(row0 + (threadIdx.x & 31u), end - 1)];
+  }
+  GGNN_DEV void store_single(float* tile, uint32_t DP, uint32_t CW, uint32_t*, uint32_t) const
+  {
+    if (threadIdx.x < (uint32_t)kBfTileRows)
+      reinterpret_cast<int32_t*>(tile)[threadIdx.x * DP + CW + 1] = w;
+  }
+  GGNN_DEV void store_group(uint32_t* filt, uint32_t slot) const
+  {
+    if (threadIdx.x < (uint32_t)kBfTileRows)
+      filt[kBfQueriesPerBlock + slot * kBfTileRows + threadIdx.x] = static_cast<uint32_t>(w);
+  }
+};
+GGNN_DEV bool bf_label_denied(int32_t ql, int32_t row_label)
+{
+  return ql != -1 && ql != row_label;
+}
+
 // T = base tiles per group whose accumulators stay in registers while the K chunks stream by
 // (T = 1 for D <= 128: a single chunk, the query tile is loaded once per workgroup).
 // NU (T = 1 only): float4 steps per half row, Dh = 4*NU -- a compile-time trip count keeps the
@@ -659,9 +759,12 @@ GGNN_DEV float bf_expand(float dot, float qn, float bn, bool jvalid)
 // ahead of the MFMAs that consume them.
 // KPC: the list length KP as a compile-time constant (0: a.KP at run time) -- every list address
 // of the epilogue and of the insertions is then a constant offset from one base.
-template <typename BaseT, int MODE, int T, int NU, int KPC = 0>
+// FM: filter mode (bf_common.hpp; FilterStage above).  Everything it adds is behind
+// `if constexpr (FM != kBfNoFilter)`: the unfiltered kernels are what they were.
+template <typename BaseT, int MODE, int T, int NU, int KPC = 0, int FM = kBfNoFilter>
 __global__ void __launch_bounds__(256)
-    __attribute__((amdgpu_waves_per_eu(T == 1 ? 3 : T <= 3 ? 2 : 1))) bf_mfma_kernel(const BfMfmaArgs a)
+    __attribute__((amdgpu_waves_per_eu(T == 1 ? 3 : T <= 3 ? 2 : 1)))
+    bf_mfma_kernel(const BfMfmaArgsOf<FM> a)
 {
   extern __shared__ __attribute__((aligned(16))) float lds_f[];
   // the two tile buffers are addressed as lds_f + offset (never through a pointer array: a select
@@ -697,6 +800,10 @@ __global__ void __launch_bounds__(256)
   // first tile is staged before the current group's epilogue), [group parity][tile][row]; the
   // epilogue reads them from here -- a global load there is a round trip of its own per group
   float* bn_grp = thr_lds;  // (the single-chunk kernel keeps its thresholds in these words)
+  // filtered kernels: the verdict area behind them (layout: bf_filter_lds_words, bf_common.hpp)
+  [[maybe_unused]] uint32_t* filt_lds =
+      reinterpret_cast<uint32_t*>(thr_lds + (T == 1 ? 1 : 2) * kBfQueriesPerBlock);
+  FilterStage<FM> fstage;
   for (uint32_t i = tid; i < a.DM; i += 256)
     mean_lds[i] = (a.mean && i < a.D) ? a.mean[i] : 0.f;
 
@@ -759,20 +866,29 @@ __global__ void __launch_bounds__(256)
 #endif
         thr_lds[wave * 32 + lane] = t0v;
       }
+      // (the wave's own 32 query labels, like its query norms)
+      if constexpr (FM == kBfLabels)
+        reinterpret_cast<int32_t*>(filt_lds)[wave * 32 + lane] =
+            qi < a.Nq ? a.filter_table.query_labels[qi] : -1;
     }
   }
+  fstage.open(a, qblock);
   __syncthreads();
   const uint32_t ntiles = (end > begin) ? (end - begin + kBfTileRows - 1) / kBfTileRows : 0;
   if (ntiles) {
     if constexpr (T > 1) {
       stage.load(base, a.D, begin, end, 0, CW, a.bnorm, bn_pad);
+      fstage.load(a, begin, end);
       stage.store_shifted(lds_f, DP, CW, mean_lds, 0);
       if (tid < kBfTileRows)
         bn_grp[tid] = stage.norm();
+      fstage.store_group(filt_lds, 0);
     }
     else {
       stage.load(base, a.D, begin, end, 0, CW, a.bnorm, bn_pad);
+      fstage.load(a, begin, end);
       stage.store_shifted(lds_f, DP, CW, mean_lds, 0);
+      fstage.store_single(lds_f, DP, CW, filt_lds, 0);
     }
   }
   __syncthreads();
@@ -800,9 +916,16 @@ __global__ void __launch_bounds__(256)
       // norm of this lane's tile row, staged next to the tile (an LDS read: a global load here
       // would make the compiler wait for vmcnt(0), i.e. for the prefetch of the next tile)
       const float bn = lds_f[(tt & 1) * tile_floats + j * DP + CW];
+      // (kBfLabels: the row's label from the spare word next to it)
+      [[maybe_unused]] int32_t row_label = 0;
+      if constexpr (FM == kBfLabels)
+        row_label =
+            reinterpret_cast<const int32_t*>(lds_f)[(tt & 1) * tile_floats + j * DP + CW + 1];
       const bool has_next = tt + 1 < ntiles;
-      if (has_next)
+      if (has_next) {
         stage.load(base, a.D, row0 + kBfTileRows, end, 0, CW, a.bnorm, bn_pad);
+        fstage.load(a, row0 + kBfTileRows, end);
+      }
       f32x16 acc = f32x16{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
       const float* bt = lds_f + (tt & 1) * tile_floats + j * DP + h * Dh;
 #pragma unroll
@@ -823,6 +946,23 @@ __global__ void __launch_bounds__(256)
         dd[4 * g + 1] = bf_expand<MODE>(acc[4 * g + 1], qn4.y, bn, jvalid);
         dd[4 * g + 2] = bf_expand<MODE>(acc[4 * g + 2], qn4.z, bn, jvalid);
         dd[4 * g + 3] = bf_expand<MODE>(acc[4 * g + 3], qn4.w, bn, jvalid);
+        // the verdicts of the lane's four query rows of this group, read like qn4 / th4
+        if constexpr (FM == kBfBits) {
+          const uint4 fw4 = *reinterpret_cast<const uint4*>(
+              filt_lds + (tt & 1) * kBfQueriesPerBlock + wave * 32 + 8 * g + 4 * h);
+          dd[4 * g + 0] = ((fw4.x >> j) & 1u) ? dd[4 * g + 0] : inf_f();
+          dd[4 * g + 1] = ((fw4.y >> j) & 1u) ? dd[4 * g + 1] : inf_f();
+          dd[4 * g + 2] = ((fw4.z >> j) & 1u) ? dd[4 * g + 2] : inf_f();
+          dd[4 * g + 3] = ((fw4.w >> j) & 1u) ? dd[4 * g + 3] : inf_f();
+        }
+        if constexpr (FM == kBfLabels) {
+          const int4 ql4 = *reinterpret_cast<const int4*>(
+              reinterpret_cast<const int32_t*>(filt_lds) + wave * 32 + 8 * g + 4 * h);
+          dd[4 * g + 0] = bf_label_denied(ql4.x, row_label) ? inf_f() : dd[4 * g + 0];
+          dd[4 * g + 1] = bf_label_denied(ql4.y, row_label) ? inf_f() : dd[4 * g + 1];
+          dd[4 * g + 2] = bf_label_denied(ql4.z, row_label) ? inf_f() : dd[4 * g + 2];
+          dd[4 * g + 3] = bf_label_denied(ql4.w, row_label) ? inf_f() : dd[4 * g + 3];
+        }
         any |= __ballot(dd[4 * g + 0] < th4.x) | __ballot(dd[4 * g + 1] < th4.y) |
                __ballot(dd[4 * g + 2] < th4.z) | __ballot(dd[4 * g + 3] < th4.w);
       }
@@ -830,9 +970,11 @@ __global__ void __launch_bounds__(256)
       if (any)
         bf_test_and_insert(dd, thr_w, row0, wave_d, wave_id, KP, h);
       GGNN_BF_TICK(1);
-      if (has_next)
+      if (has_next) {
         stage.store_shifted(lds_f + ((tt + 1) & 1) * tile_floats, DP, CW, mean_lds,
                                             0);
+        fstage.store_single(lds_f + ((tt + 1) & 1) * tile_floats, DP, CW, filt_lds, (tt + 1) & 1);
+      }
       GGNN_BF_TICK(2);
       __syncthreads();
       GGNN_BF_TICK(3);
@@ -899,9 +1041,11 @@ __global__ void __launch_bounds__(256)
           else
             has_next = false;
         }
-        if (has_next)
+        if (has_next) {
           stage.load(base, a.D, begin + n_tile * kBfTileRows, end, n_chunk * CW, CW, a.bnorm,
                      bn_pad);
+          fstage.load(a, begin + n_tile * kBfTileRows, end);
+        }
 
         // S += Q_chunk x B_chunk^T for this wave's 32 queries against the 32 tile rows.  During
         // the last tile of a chunk every group of four query operands is reloaded for the NEXT
@@ -920,6 +1064,8 @@ __global__ void __launch_bounds__(256)
                               n_chunk * CW);
           if (n_chunk == 0 && tid < kBfTileRows)
             bn_grp[((((n_tile / T) & 1) * T) + n_tile % T) * kBfTileRows + tid] = stage.norm();
+          if (n_chunk == 0)
+            fstage.store_group(filt_lds, ((n_tile / T) & 1) * T + n_tile % T);
         }
         GGNN_BF_TICK(2);
         __syncthreads();
@@ -941,6 +1087,12 @@ __global__ void __launch_bounds__(256)
       thr2[r] = wave_d2[ql * KP + KP - 1];   // -inf for padding queries (list initialisation)
       qn2[r] = qn_lds[wave * 32 + ql];
     }
+    [[maybe_unused]] int32_t ql2[16];
+    if constexpr (FM == kBfLabels) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r)
+        ql2[r] = reinterpret_cast<const int32_t*>(filt_lds)[wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * h];
+    }
 #pragma unroll
     for (int t = 0; t < T; ++t) {
       const uint32_t tt = g0 + t;
@@ -955,6 +1107,16 @@ __global__ void __launch_bounds__(256)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         dd[r] = bf_expand<MODE>(acc[t][r], qn2[r], bn, jvalid);
+        if constexpr (FM == kBfBits) {
+          const uint32_t fw = filt_lds[(((g0 / T) & 1) * T + t) * kBfQueriesPerBlock + wave * 32 +
+                                       (r & 3) + 8 * (r >> 2) + 4 * h];
+          dd[r] = ((fw >> j) & 1u) ? dd[r] : inf_f();
+        }
+        if constexpr (FM == kBfLabels) {
+          const int32_t row_label = static_cast<int32_t>(
+              filt_lds[kBfQueriesPerBlock + (((g0 / T) & 1) * T + t) * kBfTileRows + j]);
+          dd[r] = bf_label_denied(ql2[r], row_label) ? inf_f() : dd[r];
+        }
         any |= __ballot(dd[r] < thr2[r]);
       }
       if (!any)
@@ -1242,18 +1404,83 @@ __global__ void __launch_bounds__(kWave) bf_rerank_kernel(const BfRerankArgs a)
     a.rescan_list[atomicAdd(a.rescan_count, 1u)] = n;
 }
 
+#ifdef GGNN_BF_FILTER_TU
+// ---- the filtered instantiations of this translation unit (bf_mfma_bits.hip, bf_mfma_labels.hip) --
+template <typename BaseT, int MODE>
+static const void* bf_filtered_kernel_of(int T, int NU, int KPC)
+{
+  constexpr int FM = GGNN_BF_FILTER_TU;
+#define GGNN_BF_K(T_, NU_, KPC_) \
+  reinterpret_cast<const void*>(&bf_mfma_kernel<BaseT, MODE, T_, NU_, KPC_, FM>)
+  if (T == 2)
+    return GGNN_BF_K(2, 16, 0);
+  if (T == 3)
+    return GGNN_BF_K(3, 16, 0);
+  if (T == 4)
+    return GGNN_BF_K(4, 16, 0);
+  // single chunk: the list length is a constant (bf_common.hpp, kBfFilteredSingleChunkKP)
+  static_assert(kBfFilteredSingleChunkKP == 18, "the filtered single-chunk list length");
+  if (KPC == 18)
+    return NU == 8 ? GGNN_BF_K(1, 8, 18) : NU == 12 ? GGNN_BF_K(1, 12, 18) : GGNN_BF_K(1, 16, 18);
+  throw Error(GGNN_UNSUPPORTED, "no filtered tile kernel for this list length");
+#undef GGNN_BF_K
+}
+#if GGNN_BF_FILTER_TU == 1
+const void* bf_mfma_bits_kernel(ggnn_dtype dtype, ggnn_measure measure, int T, int NU, int KPC)
+#else
+const void* bf_mfma_labels_kernel(ggnn_dtype dtype, ggnn_measure measure, int T, int NU, int KPC)
+#endif
+{
+  const bool l2 = measure == GGNN_EUCLIDEAN;
+  switch (dtype) {
+    case GGNN_F32:
+      return l2 ? bf_filtered_kernel_of<float, kL2>(T, NU, KPC)
+                : bf_filtered_kernel_of<float, kCos>(T, NU, KPC);
+    case GGNN_F16:
+      return l2 ? bf_filtered_kernel_of<f16_t, kL2>(T, NU, KPC)
+                : bf_filtered_kernel_of<f16_t, kCos>(T, NU, KPC);
+    case GGNN_BF16:
+      return l2 ? bf_filtered_kernel_of<bf16_t, kL2>(T, NU, KPC)
+                : bf_filtered_kernel_of<bf16_t, kCos>(T, NU, KPC);
+    case GGNN_U8:
+      return l2 ? bf_filtered_kernel_of<uint8_t, kL2>(T, NU, KPC)
+                : bf_filtered_kernel_of<uint8_t, kCos>(T, NU, KPC);
+  }
+  throw Error(GGNN_INVALID_ARGUMENT, "unknown dtype");
+}
+
+}  // namespace ggnn_amd
+#else  // GGNN_BF_FILTER_TU
 // ---- host ---------------------------------------------------------------------------------------
+static int bf_filter_mode(const BfLaunch& a)
+{
+  return !a.filter_bits ? kBfNoFilter : a.filter_table.query_labels ? kBfLabels : kBfBits;
+}
+
+// uint8 + squared L2 with rows of up to 128 bytes: the integer kernels (no filtered form)
+bool bf_mfma_uses_i8(const BfLaunch& a)
+{
+  return a.dtype == GGNN_U8 && a.measure == GGNN_EUCLIDEAN && a.D <= 128 && hook(kHookBfNoI8) == 0;
+}
+
 bool bf_mfma_supported(const BfLaunch& a)
 {
   const uint32_t epc = dtype_elems_per_chunk(a.dtype);
   if (!(a.D % epc == 0 && a.k_query + 8 <= kBfMaxKP && a.Nq >= 256 && a.N_base >= 4096))
     return false;
   // tiles + candidate lists (+ the shift vector of the chunked kernel) must fit into 160 KB of LDS
-  const size_t lists = 2ull * kBfQueriesPerBlock * (a.k_query + 8);
+  const int fm = bf_filter_mode(a);
+  // (a filtered call with k > 10 runs the chunked kernel whatever D is: bf_common.hpp)
+  const bool chunked =
+      fm != kBfNoFilter ? bf_filtered_runs_chunked(a.D, a.k_query) : a.D > 128;
+  const size_t lists =
+      2ull * kBfQueriesPerBlock * (chunked ? a.k_query + 8 : std::max(a.k_query + 8, 18u));
   const size_t tiles = 2ull * kBfTileRows * 132;
-  const size_t shift = a.D > 128 ? (a.D + 127) / 128 * 128 + 3 * kBfQueriesPerBlock
+  const size_t shift = chunked ? (a.D + 127) / 128 * 128 + 3 * kBfQueriesPerBlock
                                  : 128 + 2 * kBfQueriesPerBlock;
-  return (lists + tiles + shift) * sizeof(float) <= 160 * 1024;
+  // (+ the verdict area of a filtered kernel, at the largest accumulator group of the chunked one)
+  const size_t filt = bf_filter_lds_words(fm, chunked ? 4u : 1u);
+  return (lists + tiles + shift + filt) * sizeof(float) <= 160 * 1024;
 }
 
 size_t bf_rescan_tmp_entries(const BfLaunch& a, uint32_t* slices_out);
@@ -1269,16 +1496,24 @@ void launch_bf_query_mfma(const BfLaunch& a, hipStream_t stream)
   // uint8 + squared L2 with rows of up to 128 bytes: integer contraction on the i8 matrix path;
   // lists of up to 24 entries live in registers (bf_i8v2_kernel), longer ones in LDS
   // (bf_mfma_i8_kernel; hook BF_I8_V1 = 1 forces that one: A/B hook)
-  const bool use_i8 = a.dtype == GGNN_U8 && a.measure == GGNN_EUCLIDEAN && a.D <= 128 &&
-                      hook(kHookBfNoI8) == 0;
+  const bool use_i8 = bf_mfma_uses_i8(a);
+  const int fm = bf_filter_mode(a);  // (launch_bf_query sends no filtered call to the i8 kernels)
+  GGNN_REQUIRE(!(fm != kBfNoFilter && use_i8), GGNN_UNSUPPORTED,
+               "the i8 matrix kernels have no filtered form");
   const bool use_i8v2 = use_i8 && a.k_query <= 16 && hook(kHookBfI8V1) == 0;
   // (integer arithmetic needs no certificate margin: the register sets hold exactly K rounded up)
+  // rows longer than one chunk of 128 columns run the chunked kernel -- and so does a filtered
+  // call with k > 10 at any D (bf_common.hpp: the filtered single-chunk kernels exist with the
+  // constant list length 18 only, to which shorter lists are rounded up)
+  const bool chunked =
+      fm != kBfNoFilter ? bf_filtered_runs_chunked(a.D, a.k_query) : a.D > 128;
   const uint32_t KP = use_i8v2 ? (a.k_query <= 4 ? 4u : a.k_query <= 10 ? 10u : 16u)
-                               : a.k_query + 8;
+                      : (fm != kBfNoFilter && !chunked) ? kBfFilteredSingleChunkKP
+                                                        : a.k_query + 8;
   // one chunk of 2*Dh columns when the row fits (D <= 128), otherwise chunks of 128 columns
   // half-row width: 64 when D > 128 (K streams in chunks), otherwise 32 / 48 / 64 so that the
   // single chunk covers the row (columns past D are zero in the tile and in the query operand)
-  const uint32_t Dh = a.D > 128 ? 64 : (a.D <= 64 ? 32 : a.D <= 96 ? 48 : 64);
+  const uint32_t Dh = chunked ? 64 : (a.D <= 64 ? 32 : a.D <= 96 ? 48 : 64);
   const uint32_t DP = (2 * Dh) + (((2 * Dh) % 8 == 0) ? 4 : 8);  // odd number of 16-B slots/row
   const uint32_t queries_per_block = use_i8v2 ? 256u : static_cast<uint32_t>(kBfQueriesPerBlock);
   const uint32_t qblocks = (a.Nq + queries_per_block - 1) / queries_per_block;
@@ -1286,11 +1521,11 @@ void launch_bf_query_mfma(const BfLaunch& a, hipStream_t stream)
   // second round costs more than the lower parallelism (measured: 790 blocks 39.8 ms, 474 blocks
   // 31.5 ms for 10k x 1M x 128)
   // (the single-chunk float kernel runs three workgroups per CU when their LDS fits)
-  const bool single_chunk = !use_i8 && a.D <= 128;
+  const bool single_chunk = !use_i8 && !chunked;
   uint32_t resident = 512;
   if (single_chunk) {
     const size_t lds1 = (2 * kBfTileRows * DP + 2 * kBfQueriesPerBlock * KP + 2 * Dh +
-                         2 * kBfQueriesPerBlock) * sizeof(float);
+                         2 * kBfQueriesPerBlock + bf_filter_lds_words(fm, 1)) * sizeof(float);
     resident = 256u * static_cast<uint32_t>(std::clamp<size_t>(160 * 1024 / lds1, 1, 3));
   }
   uint32_t slices = std::max(1u, std::min(32u, resident / std::max(1u, qblocks)));
@@ -1308,7 +1543,7 @@ void launch_bf_query_mfma(const BfLaunch& a, hipStream_t stream)
   const bool equal_ranges = !use_i8;
   const int64_t tiles_hook = hook(kHookBfTiles);
   const uint32_t unit_tiles =
-      a.D > 128 ? (tiles_hook == 4 ? 4u : tiles_hook == 2 ? 2u : 3u) : 1u;
+      chunked ? (tiles_hook == 4 ? 4u : tiles_hook == 2 ? 2u : 3u) : 1u;
   const uint32_t unit_rows = unit_tiles * kBfTileRows;
   const uint32_t tiles_per_q = (a.N_base + unit_rows - 1) / unit_rows;
   const uint64_t total_tiles = static_cast<uint64_t>(qblocks) * tiles_per_q;
@@ -1346,7 +1581,7 @@ void launch_bf_query_mfma(const BfLaunch& a, hipStream_t stream)
   // exchange area of the i8 register-set kernel (bf_i8.hip "bound exchange")
   const size_t n_gthr = use_i8v2 ? pad4(bf_i8v2_exchange_ints(a.Nq, slices)) + pad4(a.Nq) : 0;
   // chunked float kernel: the query set once more, in operand order (QueryWindow)
-  const uint32_t pack_chunks = (!use_i8 && a.D > 128) ? (a.D + 127) / 128 : 0;
+  const uint32_t pack_chunks = (!use_i8 && chunked) ? (a.D + 127) / 128 : 0;
   const size_t n_qpack = static_cast<size_t>(qblocks) * kBfQueriesPerBlock * pack_chunks * 128;
   const size_t words = n_norms + n_mean + n_partial + 4 + n_list + 2 * n_parts + 2 * n_rescan +
                        pad4(n_qshift) + n_gthr + n_qpack;
@@ -1438,13 +1673,26 @@ void launch_bf_query_mfma(const BfLaunch& a, hipStream_t stream)
   // the shift vector sits in LDS (single chunk: its 2*Dh columns); 128 query norms and 128
   // thresholds (single chunk only) follow
   // (zero past column D up to the end of the last chunk: see TileStage<float>::load)
-  m.DM = a.D > 128 ? (a.D + 127) / 128 * 128 : 2 * Dh;
+  m.DM = chunked ? (a.D + 127) / 128 * 128 : 2 * Dh;
   // (chunked kernel: [2][T <= 4][32] row norms in place of the thresholds)
+  // (filtered kernels: + their verdict area, bf_filter_lds_words)
   const size_t lds = (2 * kBfTileRows * DP + 2 * kBfQueriesPerBlock * KP + m.DM +
-                      (a.D > 128 ? 3 : 2) * kBfQueriesPerBlock) * sizeof(float);
+                      (chunked ? 3 : 2) * kBfQueriesPerBlock +
+                      bf_filter_lds_words(fm, unit_tiles)) * sizeof(float);
   GGNN_REQUIRE(lds <= 160 * 1024, GGNN_UNSUPPORTED, "k too large for the MFMA brute-force path");
   // rows longer than one chunk: base tiles per accumulator group (hook BF_TILES = 2 | 4)
   const int tiles_per_group = static_cast<int>(unit_tiles);
+  BfMfmaFilteredArgs mf{};
+  static_cast<BfMfmaArgs&>(mf) = m;
+  mf.filter_bits = a.filter_bits;
+  mf.filter_bit_offset = a.filter_bit_offset;
+  mf.filter_table = a.filter_table;
+  // the filtered kernel of this launch comes from its own translation unit
+  const int f_nu = static_cast<int>(Dh / 4), f_kpc = chunked ? 0 : static_cast<int>(KP);
+  const void* f_kern = fm == kBfBits ? bf_mfma_bits_kernel(a.dtype, a.measure, tiles_per_group, f_nu, f_kpc)
+                       : fm == kBfLabels
+                           ? bf_mfma_labels_kernel(a.dtype, a.measure, tiles_per_group, f_nu, f_kpc)
+                           : nullptr;
 
   BfRerankArgs rr{};
   rr.base = a.base;
@@ -1473,7 +1721,7 @@ void launch_bf_query_mfma(const BfLaunch& a, hipStream_t stream)
     hipLaunchKernelGGL((row_norms_kernel<T>), dim3(norm_grid(a.Nq)), dim3(256), 0, stream,       \
                        static_cast<const T*>(tile_query), a.Nq, a.D,                              \
                        static_cast<const float*>(nullptr), qnorm, static_cast<uint32_t*>(nullptr)); \
-    const void* kern = (a.D > 128) ? (tiles_per_group == 2                                             \
+    const void* kern = f_kern ? f_kern : chunked ? (tiles_per_group == 2                                             \
                            ? reinterpret_cast<const void*>(&bf_mfma_kernel<T, MODE_, 2, 16>)      \
                            : tiles_per_group == 3                                                 \
                            ? reinterpret_cast<const void*>(&bf_mfma_kernel<T, MODE_, 3, 16>)      \
@@ -1488,7 +1736,7 @@ void launch_bf_query_mfma(const BfLaunch& a, hipStream_t stream)
     if (lds > 64 * 1024)                                                                          \
       GGNN_HIP_CHECK(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize,        \
                                          static_cast<int>(lds)));                                 \
-    void* kargs[] = {&m};                                                                         \
+    void* kargs[] = {f_kern ? static_cast<void*>(&mf) : static_cast<void*>(&m)};                 \
     const dim3 grid = equal_ranges ? dim3(nblocks) : dim3(qblocks, slices);                       \
     GGNN_HIP_CHECK(hipLaunchKernel(kern, grid, dim3(256), kargs, lds, stream));                   \
   } while (0)
@@ -1589,8 +1837,9 @@ void launch_bf_query_mfma(const BfLaunch& a, hipStream_t stream)
 }
 
 }  // namespace ggnn_amd
+#endif  // GGNN_BF_FILTER_TU
 
-#ifdef GGNN_BF_PHASE
+#if defined(GGNN_BF_PHASE) && !defined(GGNN_BF_FILTER_TU)
 extern "C" int ggnn_debug_bf_bound(const float* bound)
 {
   using namespace ggnn_amd;

@@ -9,8 +9,10 @@
 // for large query batches is planned on top of this parity anchor, see DESIGN.md.)
 //
 // FILT = true (ggnn_bf_query_filtered): the exact K nearest among the rows an allowed-id bitset
-// admits -- a denied row's distance becomes +inf before the ballot.  The filtered call always runs
-// on these scan kernels: a filtered matrix-core path (bf_mfma.hip, bf_i8.hip) is out of scope.
+// admits -- a denied row's distance becomes +inf before the ballot.  Large filtered batches run
+// on the filtered tile kernels of bf_mfma.hip (launch_bf_query below says which); these scan
+// kernels answer the rest, and the queries the tile kernels could not certify -- the filter of a
+// re-scanned query is chosen by its real index n = qlist[...], not by its position in the list.
 #include <cstdlib>
 
 #include "hooks.hpp"
@@ -434,6 +436,7 @@ void launch_scatter_labels(int32_t* labels, uint64_t N, const uint32_t* ids, con
 }
 
 bool bf_mfma_supported(const BfLaunch& a);
+bool bf_mfma_uses_i8(const BfLaunch& a);
 void launch_bf_query_mfma(const BfLaunch& a, hipStream_t stream);
 
 // scan of all queries (qlist == nullptr) or of the subset qlist[0, *qcount); slices > 1 needs
@@ -506,17 +509,52 @@ void launch_bf_rescan(const BfLaunch& a, const uint32_t* qlist, const uint32_t* 
   launch_bf_scan(a, slices, rows, qlist, qcount, tmp_ids, tmp_dists, stream);
 }
 
-void launch_bf_query(const BfLaunch& a, hipStream_t stream)
+// the all-ones / all-zero rows of a launch with filter ids that brings none (operator seam): made
+// in stream-ordered scratch for the duration of the launch, on either path
+struct BfFilterConsts {
+  uint32_t* p;
+  hipStream_t stream;
+  ~BfFilterConsts() { scratch_free(p, stream); }
+};
+
+void launch_bf_query(const BfLaunch& a_in, hipStream_t stream)
 {
-  if (a.n_rescanned)
-    GGNN_HIP_CHECK(hipMemsetAsync(a.n_rescanned, 0, sizeof(uint32_t), stream));
-  if (a.Nq == 0)
+  if (a_in.n_rescanned)
+    GGNN_HIP_CHECK(hipMemsetAsync(a_in.n_rescanned, 0, sizeof(uint32_t), stream));
+  if (a_in.matrix_path)
+    *a_in.matrix_path = 0;
+  if (a_in.Nq == 0)
     return;
-  // large batches: Q x B^T on the matrix cores (bf_mfma.hip); hook BF_SCAN = 1 forces the scan
-  // (a filtered call always scans: there is no filtered matrix-core path)
-  const bool force_scan = hook(kHookBfScan) == 1 || a.filter_bits != nullptr;
+  // what a filtered launch must bring, on either path
+  GGNN_REQUIRE(!a_in.filter_table.query_labels || (a_in.filter_bits && !a_in.filter_table.ids),
+               GGNN_INVALID_ARGUMENT,
+               "query labels need the label column and exclude filter ids");
+  GGNN_REQUIRE(!a_in.filter_table.query_labels || a_in.N_base <= kMaxLabeledShardRows,
+               GGNN_UNSUPPORTED, "label filters need at most 2^30 base vectors per scan");
+  const bool table = a_in.filter_bits && a_in.filter_table.ids;
+  GGNN_REQUIRE(!table || (a_in.filter_table.words != 0 && a_in.filter_table.num_filters != 0),
+               GGNN_INVALID_ARGUMENT, "filter ids need a filter table");
+  BfLaunch a = a_in;
+  BfFilterConsts consts{table ? filter_consts_scratch(a.filter_table, stream) : nullptr, stream};
+  if (consts.p)
+    a.filter_table.consts = consts.p;
+
+  // large batches: Q x B^T on the matrix cores (bf_mfma.hip); hook BF_SCAN = 1 forces the scan,
+  // for filtered calls too (the A/B switch).  A filtered call keeps the scan
+  //   - at the shapes of the integer kernels (uint8, squared L2, D <= 128): they have no filtered form
+  //   - under a bitset (per call or table) whose bit offset is not a multiple of 32: a tile's 32
+  //     verdicts of a query are then not one word of its bitset (the engine's offsets are 0)
+  //   (labels: N_base <= kMaxLabeledShardRows holds on both paths, required above)
+  bool force_scan = hook(kHookBfScan) == 1;
+  if (a.filter_bits) {
+    const bool bits = !a.filter_table.query_labels;
+    force_scan = force_scan || bf_mfma_uses_i8(a) || (bits && a.filter_bit_offset % 32 != 0) ||
+                 static_cast<uint64_t>(a.filter_bit_offset) + a.N_base > 0xffffffffull;
+  }
   if (!force_scan && bf_mfma_supported(a)) {
     launch_bf_query_mfma(a, stream);
+    if (a.matrix_path)
+      *a.matrix_path = 1;
     return;
   }
   check_vector_layout(a.base, a.D, a.dtype);
@@ -539,24 +577,7 @@ void launch_bf_query(const BfLaunch& a, hipStream_t stream)
     GGNN_HIP_CHECK(hipMallocAsync(reinterpret_cast<void**>(&tmp_ids), n * sizeof(int32_t), stream));
     GGNN_HIP_CHECK(hipMallocAsync(reinterpret_cast<void**>(&tmp_dists), n * sizeof(float), stream));
   }
-  GGNN_REQUIRE(!a.filter_table.query_labels || (a.filter_bits && !a.filter_table.ids),
-               GGNN_INVALID_ARGUMENT,
-               "query labels need the label column and exclude filter ids");
-  GGNN_REQUIRE(!a.filter_table.query_labels || a.N_base <= kMaxLabeledShardRows, GGNN_UNSUPPORTED,
-               "label filters need at most 2^30 base vectors per scan");
-  if (a.filter_bits && a.filter_table.ids) {
-    GGNN_REQUIRE(a.filter_table.words != 0 && a.filter_table.num_filters != 0,
-                 GGNN_INVALID_ARGUMENT, "filter ids need a filter table");
-    // the all-ones / all-zero rows of a launch that brings none (operator seam)
-    BfLaunch b = a;
-    uint32_t* consts = filter_consts_scratch(a.filter_table, stream);
-    if (consts)
-      b.filter_table.consts = consts;
-    launch_bf_scan(b, slices, rows_per_slice, nullptr, nullptr, tmp_ids, tmp_dists, stream);
-    scratch_free(consts, stream);
-  }
-  else
-    launch_bf_scan(a, slices, rows_per_slice, nullptr, nullptr, tmp_ids, tmp_dists, stream);
+  launch_bf_scan(a, slices, rows_per_slice, nullptr, nullptr, tmp_ids, tmp_dists, stream);
   if (slices > 1) {
     GGNN_HIP_CHECK(hipFreeAsync(tmp_ids, stream));
     GGNN_HIP_CHECK(hipFreeAsync(tmp_dists, stream));

@@ -220,11 +220,14 @@ struct BfLaunch {
   // with the scan kernel instead (0 on the scan path)
   uint32_t* n_rescanned{nullptr};
   // optional allowed-id bitset (device; bit (row + filter_bit_offset)): the exact K nearest among
-  // the allowed rows, on the scan kernels (bf_query.hip)
+  // the allowed rows (bf_query.hip: launch_bf_query says which filtered calls run the tile kernels)
   const uint32_t* filter_bits{nullptr};
   uint32_t filter_bit_offset{0};
   // per-query filters: filter_bits is then a table (see FilterTable)
   FilterTable filter_table{};
+  // optional (HOST): 1 if the launch ran the tile kernels of bf_mfma.hip, 0 if it ran the scan --
+  // decided on the host before anything is enqueued; results are bit-identical either way
+  int* matrix_path{nullptr};
 };
 void launch_bf_query(const BfLaunch& a, hipStream_t stream);
 

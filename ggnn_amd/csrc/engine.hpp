@@ -545,6 +545,7 @@ struct ggnn_handle {
   ggnn_build_work build_work{};  // collect_counters during build(): see ggnn_last_build_work
   std::mutex build_work_mutex;   // one host thread per GPU accounts into it
   uint32_t last_bf_rescanned{0};
+  int last_bf_matrix_path{0};  // the last bf_query ran the tile kernels (bf_mfma.hip) on every shard
   // per-query filters.  The table as ggnn_set_filters copied it, [num_filters x filter_words]
   // words on the host (placed on a GPU when a context exists: place_filter_table)
   std::vector<uint32_t> filter_table_host;

@@ -668,6 +668,15 @@ ggnn_status ggnn_last_bf_query_rescanned(const ggnn_t* h, uint32_t* n_rescanned)
   return GGNN_OK;
 }
 
+ggnn_status ggnn_last_bf_query_matrix_path(const ggnn_t* h, int* out)
+{
+  GGNN_NEED_HANDLE(h);
+  if (!out)
+    return GGNN_INVALID_ARGUMENT;
+  *out = h->last_bf_matrix_path;
+  return GGNN_OK;
+}
+
 ggnn_status ggnn_last_query_counters(const ggnn_t* h, uint64_t* n_dist, uint64_t* n_pop)
 {
   GGNN_NEED_HANDLE(h);
@@ -816,6 +825,24 @@ ggnn_status ggnn_op_bf_query_filtered(const void* base, ggnn_dtype dtype, uint32
   });
 }
 
+ggnn_status ggnn_op_bf_query_filtered_certified(const void* base, ggnn_dtype dtype,
+                                                uint32_t N_base, uint32_t D, const void* query,
+                                                uint32_t Nq, uint32_t k_query,
+                                                ggnn_measure measure, int32_t* ids, float* dists,
+                                                const uint32_t* filter_bits,
+                                                uint32_t filter_bit_offset, uint32_t* n_rescanned,
+                                                int* matrix_path, void* stream)
+{
+  return guarded(nullptr, [&] {
+    GGNN_REQUIRE(filter_bits != nullptr, GGNN_INVALID_ARGUMENT, "the filter bitset is null");
+    BfLaunch b{base, query, dtype, N_base, D, Nq, k_query, measure, ids, dists, n_rescanned};
+    b.filter_bits = filter_bits;
+    b.filter_bit_offset = filter_bit_offset;
+    b.matrix_path = matrix_path;
+    launch_bf_query(b, static_cast<hipStream_t>(stream));
+  });
+}
+
 ggnn_status ggnn_op_query_filtered_by(const void* base, ggnn_dtype dtype, uint32_t N_base,
                                       uint32_t D, const uint8_t* codes, const float* params,
                                       const void* query, uint32_t Nq, const int32_t* graph0,
@@ -860,6 +887,23 @@ ggnn_status ggnn_op_bf_query_filtered_by(const void* base, ggnn_dtype dtype, uin
   });
 }
 
+ggnn_status ggnn_op_bf_query_filtered_by_certified(
+    const void* base, ggnn_dtype dtype, uint32_t N_base, uint32_t D, const void* query, uint32_t Nq,
+    uint32_t k_query, ggnn_measure measure, int32_t* ids, float* dists,
+    const uint32_t* filter_table, uint32_t num_filters, uint64_t n_bits, const int32_t* filter_ids,
+    uint32_t filter_bit_offset, uint32_t* n_rescanned, int* matrix_path, void* stream)
+{
+  return guarded(nullptr, [&] {
+    BfLaunch b{base, query, dtype, N_base, D, Nq, k_query, measure, ids, dists, n_rescanned};
+    b.filter_table =
+        seam_filter_table(filter_table, num_filters, n_bits, filter_ids, filter_bit_offset, N_base);
+    b.filter_bits = filter_table;
+    b.filter_bit_offset = filter_bit_offset;
+    b.matrix_path = matrix_path;
+    launch_bf_query(b, static_cast<hipStream_t>(stream));
+  });
+}
+
 ggnn_status ggnn_op_query_labeled(const void* base, ggnn_dtype dtype, uint32_t N_base, uint32_t D,
                                   const uint8_t* codes, const float* params, const void* query,
                                   uint32_t Nq, const int32_t* graph0, uint32_t KBuild,
@@ -896,6 +940,24 @@ ggnn_status ggnn_op_bf_query_labeled(const void* base, ggnn_dtype dtype, uint32_
     b.filter_table = seam_labels(labels, n_labels, query_labels, filter_bit_offset, N_base);
     b.filter_bits = reinterpret_cast<const uint32_t*>(labels);
     b.filter_bit_offset = filter_bit_offset;
+    launch_bf_query(b, static_cast<hipStream_t>(stream));
+  });
+}
+
+ggnn_status ggnn_op_bf_query_labeled_certified(const void* base, ggnn_dtype dtype,
+                                               uint32_t N_base, uint32_t D, const void* query,
+                                               uint32_t Nq, uint32_t k_query, ggnn_measure measure,
+                                               int32_t* ids, float* dists, const int32_t* labels,
+                                               uint64_t n_labels, const int32_t* query_labels,
+                                               uint32_t filter_bit_offset, uint32_t* n_rescanned,
+                                               int* matrix_path, void* stream)
+{
+  return guarded(nullptr, [&] {
+    BfLaunch b{base, query, dtype, N_base, D, Nq, k_query, measure, ids, dists, n_rescanned};
+    b.filter_table = seam_labels(labels, n_labels, query_labels, filter_bit_offset, N_base);
+    b.filter_bits = reinterpret_cast<const uint32_t*>(labels);
+    b.filter_bit_offset = filter_bit_offset;
+    b.matrix_path = matrix_path;
     launch_bf_query(b, static_cast<hipStream_t>(stream));
   });
 }

@@ -483,6 +483,7 @@ void ggnn_handle::bf_query(const QueryRequest& r, const QueryFilter& filter)
   DeviceCtx& ctx = devs[0];
   ctx.activate();
   bf_ms = 0.f;
+  last_bf_matrix_path = 0;
   if (!Nq)
     return;
   // out-of-core shards with the rows on the host: the exhaustive scan needs the whole base on
@@ -521,6 +522,9 @@ void ggnn_handle::bf_query(const QueryRequest& r, const QueryFilter& filter)
   const DeviceFilter df = resolve_filter(ctx, filter, DeviceCtx::kBlockingLane);
   bl.filter_bits = df.bits;
   bl.filter_table = df.table;
+  // (one launch over the whole base: "every shard" is this launch)
+  last_bf_matrix_path = 0;
+  bl.matrix_path = &last_bf_matrix_path;
   EventTimer timer(ctx.stream, ctx.ev_a, ctx.ev_b);
   launch_bf_query(bl, ctx.stream);
   bf_ms = timer.stop();

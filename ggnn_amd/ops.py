@@ -5,6 +5,8 @@ Mirrors the reference's internal operator interface -- QueryKernels::{query, bru
 (src/ggnn/construction/graph_construction.cu:128-379) -- one function per kernel, all on the
 current torch stream.  torch is only the owner of the device memory here.
 """
+import ctypes as C
+
 import torch
 
 from . import _lib
@@ -185,9 +187,20 @@ def query_filtered(base, query, graph0, start, nn1_stats, k_query, tau_query, fi
     return ids, dists
 
 
-def bf_query_filtered(base, query, k_query, filter_bits, measure=EUCLIDEAN, filter_bit_offset=0):
+def _certified(call, base, *args):
+    """run a ggnn_op_bf_query_*_certified entry point: (rescanned, matrix_path)"""
+    n = torch.zeros(1, dtype=torch.int32, device=base.device)
+    path = C.c_int(0)
+    check(call(*args, _ptr(n), C.byref(path), _stream()))
+    return int(n.item()), int(path.value)
+
+
+def bf_query_filtered(base, query, k_query, filter_bits, measure=EUCLIDEAN, filter_bit_offset=0,
+                      rescanned=False):
     """the exact k nearest among the rows the bitset allows (row i: bit i + filter_bit_offset);
-    slots beyond the number of allowed rows are (-1, +inf)"""
+    slots beyond the number of allowed rows are (-1, +inf).
+    rescanned=True: returns (ids, dists, rescanned, matrix_path) -- how many queries the
+    matrix-core path handed to the scan, and 1 if the launch ran the tile kernels at all (0: scan)"""
     _need(base, name="base"), _need(query, base.dtype, "query")
     _need(filter_bits, torch.int32, "filter_bits")
     if filter_bits.numel() * 32 < filter_bit_offset + base.shape[0]:
@@ -195,6 +208,11 @@ def bf_query_filtered(base, query, k_query, filter_bits, measure=EUCLIDEAN, filt
     Nq = query.shape[0]
     ids = torch.empty((Nq, k_query), dtype=torch.int32, device=base.device)
     dists = torch.empty((Nq, k_query), dtype=torch.float32, device=base.device)
+    if rescanned:
+        return (ids, dists) + _certified(
+            lib().ggnn_op_bf_query_filtered_certified, base, _ptr(base), _dtype_code(base),
+            base.shape[0], base.shape[1], _ptr(query), Nq, k_query, measure, _ptr(ids), _ptr(dists),
+            _ptr(filter_bits), filter_bit_offset)
     check(lib().ggnn_op_bf_query_filtered(_ptr(base), _dtype_code(base), base.shape[0],
                                           base.shape[1], _ptr(query), Nq, k_query, measure,
                                           _ptr(ids), _ptr(dists), _ptr(filter_bits),
@@ -247,13 +265,19 @@ def query_filtered_by(base, query, graph0, start, nn1_stats, k_query, tau_query,
 
 
 def bf_query_filtered_by(base, query, k_query, filter_table, filter_ids, measure=EUCLIDEAN,
-                         filter_bit_offset=0):
+                         filter_bit_offset=0, rescanned=False):
     """`bf_query_filtered` with one filter per query (see query_filtered_by)"""
     _need(base, name="base"), _need(query, base.dtype, "query")
     Nq = query.shape[0]
     _need_filter_table(filter_table, filter_ids, Nq, filter_bit_offset + base.shape[0])
     ids = torch.empty((Nq, k_query), dtype=torch.int32, device=base.device)
     dists = torch.empty((Nq, k_query), dtype=torch.float32, device=base.device)
+    if rescanned:
+        return (ids, dists) + _certified(
+            lib().ggnn_op_bf_query_filtered_by_certified, base, _ptr(base), _dtype_code(base),
+            base.shape[0], base.shape[1], _ptr(query), Nq, k_query, measure, _ptr(ids), _ptr(dists),
+            _ptr(filter_table), filter_table.shape[0], filter_table.shape[1] * 32, _ptr(filter_ids),
+            filter_bit_offset)
     check(lib().ggnn_op_bf_query_filtered_by(
         _ptr(base), _dtype_code(base), base.shape[0], base.shape[1], _ptr(query), Nq, k_query,
         measure, _ptr(ids), _ptr(dists), _ptr(filter_table), filter_table.shape[0],
@@ -302,13 +326,19 @@ def query_labeled(base, query, graph0, start, nn1_stats, k_query, tau_query, lab
     return ids, dists
 
 
-def bf_query_labeled(base, query, k_query, labels, query_labels, measure=EUCLIDEAN, bit_offset=0):
+def bf_query_labeled(base, query, k_query, labels, query_labels, measure=EUCLIDEAN, bit_offset=0,
+                     rescanned=False):
     """`bf_query_filtered` under label filters (see query_labeled)"""
     _need(base, name="base"), _need(query, base.dtype, "query")
     Nq = query.shape[0]
     _need_labels(labels, query_labels, Nq, bit_offset + base.shape[0])
     ids = torch.empty((Nq, k_query), dtype=torch.int32, device=base.device)
     dists = torch.empty((Nq, k_query), dtype=torch.float32, device=base.device)
+    if rescanned:
+        return (ids, dists) + _certified(
+            lib().ggnn_op_bf_query_labeled_certified, base, _ptr(base), _dtype_code(base),
+            base.shape[0], base.shape[1], _ptr(query), Nq, k_query, measure, _ptr(ids), _ptr(dists),
+            _ptr(labels), labels.numel(), _ptr(query_labels), bit_offset)
     check(lib().ggnn_op_bf_query_labeled(
         _ptr(base), _dtype_code(base), base.shape[0], base.shape[1], _ptr(query), Nq, k_query,
         measure, _ptr(ids), _ptr(dists), _ptr(labels), labels.numel(), _ptr(query_labels),

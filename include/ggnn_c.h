@@ -303,6 +303,12 @@ ggnn_status ggnn_last_query_parts(const ggnn_t* h, uint32_t* parts);
 /* queries of the last ggnn_bf_query that were answered by the exhaustive scan because the
  * matrix-core pre-selection could not be certified exact (tracing; results are exact either way) */
 ggnn_status ggnn_last_bf_query_rescanned(const ggnn_t* h, uint32_t* n_rescanned);
+/* *out = 1 if the last ggnn_bf_query* call of the handle (filtered or not) ran the matrix-core
+ * tile kernel on every shard, else 0 (the scan kernels; also before the first call and after a
+ * call without queries).  Results are bit-identical on either path: this getter is how a caller
+ * or a test tells which one ran.  out == NULL: GGNN_INVALID_ARGUMENT.
+ * ggnn_last_bf_query_rescanned covers the filtered calls as well. */
+ggnn_status ggnn_last_bf_query_matrix_path(const ggnn_t* h, int* out);
 ggnn_status ggnn_set_collect_counters(ggnn_t* h, int enable);
 /* rows the last ggnn_query read for those evaluations (needs collect_counters): float rows
  * (4*D bytes each) and, with the pre-screen, 8-bit code rows (prescreen_code_dim(D) bytes each: a power of two up to 64, multiples of 64 above). */
@@ -502,7 +508,12 @@ ggnn_status ggnn_op_query_filtered(const void* base, ggnn_dtype dtype, uint32_t 
                                    float* dists, uint32_t* n_dist, uint32_t* n_pop,
                                    uint32_t* n_rows, const uint32_t* filter_bits,
                                    uint32_t filter_bit_offset, void* stream);
-/* ggnn_op_bf_query among the allowed rows only (scan kernels); unfilled slots are (-1, +inf) */
+/* ggnn_op_bf_query among the allowed rows only; unfilled slots are (-1, +inf).  Large batches
+ * (Nq >= 256, N_base >= 4096, k_query <= 112) run the filtered matrix-core tile kernels, checked
+ * by the same exactness certificate as ggnn_op_bf_query; the scan kernels answer the rest:
+ * smaller calls, uint8 rows under squared L2 with D <= 128 (the integer kernels have no filtered
+ * form), a bitset or filter table whose filter_bit_offset is not a multiple of 32, and every call
+ * under hook BF_SCAN = 1.  Results are bit-identical on either path. */
 ggnn_status ggnn_op_bf_query_filtered(const void* base, ggnn_dtype dtype, uint32_t N_base,
                                       uint32_t D, const void* query, uint32_t Nq,
                                       uint32_t k_query, ggnn_measure measure, int32_t* ids,
@@ -553,6 +564,30 @@ ggnn_status ggnn_op_bf_query_labeled(const void* base, ggnn_dtype dtype, uint32_
                                      const int32_t* labels, uint64_t n_labels,
                                      const int32_t* query_labels, uint32_t filter_bit_offset,
                                      void* stream);
+/* The three filtered brute-force calls above, reporting how they ran (modelled on
+ * ggnn_op_bf_query_certified): *n_rescanned (DEVICE memory, may be NULL) receives the number of
+ * queries the matrix-core pre-selection could not certify and the filtered scan answered instead;
+ * *matrix_path (HOST memory, may be NULL) is set before the call returns to 1 if the launch ran
+ * the tile kernels and to 0 if it ran the scan. */
+ggnn_status ggnn_op_bf_query_filtered_certified(const void* base, ggnn_dtype dtype,
+                                                uint32_t N_base, uint32_t D, const void* query,
+                                                uint32_t Nq, uint32_t k_query,
+                                                ggnn_measure measure, int32_t* ids, float* dists,
+                                                const uint32_t* filter_bits,
+                                                uint32_t filter_bit_offset, uint32_t* n_rescanned,
+                                                int* matrix_path, void* stream);
+ggnn_status ggnn_op_bf_query_filtered_by_certified(
+    const void* base, ggnn_dtype dtype, uint32_t N_base, uint32_t D, const void* query, uint32_t Nq,
+    uint32_t k_query, ggnn_measure measure, int32_t* ids, float* dists,
+    const uint32_t* filter_table, uint32_t num_filters, uint64_t n_bits, const int32_t* filter_ids,
+    uint32_t filter_bit_offset, uint32_t* n_rescanned, int* matrix_path, void* stream);
+ggnn_status ggnn_op_bf_query_labeled_certified(const void* base, ggnn_dtype dtype,
+                                               uint32_t N_base, uint32_t D, const void* query,
+                                               uint32_t Nq, uint32_t k_query, ggnn_measure measure,
+                                               int32_t* ids, float* dists, const int32_t* labels,
+                                               uint64_t n_labels, const int32_t* query_labels,
+                                               uint32_t filter_bit_offset, uint32_t* n_rescanned,
+                                               int* matrix_path, void* stream);
 /* [num_filters x N] byte masks (non-zero: allowed) -> [num_filters x ceil(N / 32)] bitset words,
  * padding bits zero; both in device memory.  A table made from a label column on the GPU needs
  * no host round trip. */

@@ -28,7 +28,15 @@ Label filters (one int32 label per base vector, one per query) against the filte
 same tenants on the same handle and graph; per tenant count T: T disjoint tenants of N / T rows,
 query labels drawn uniformly.  Kernel ms of the mixed batch through `query_labeled` and through a
 T-row table (`query_filtered_by`), alternating, every repeat listed; recall@10 of the labelled
-call against `bf_query_labeled`; resident bytes per GPU of both forms."""
+call against `bf_query_labeled`; resident bytes per GPU of both forms.
+
+    python scripts/filtered_bench.py --bf [--tenants 16] [--big-table 1024]
+
+The filtered brute force alone (no graph is built): on one handle, alternating per repeat, the
+time of each call under hook BF_SCAN = 1 (the scan kernels) and without it (the matrix-core tile
+kernels where the dispatch takes them), every repeat listed, with the path and the rescanned
+count of the matrix run: the unfiltered call, the per-call bitset at 100 / 50 / 10 / 1 % allowed,
+the --tenants-row and --big-table-row filter tables, and the same tenant counts as labels."""
 import argparse
 import json
 import os
@@ -55,6 +63,7 @@ def main():
     ap.add_argument("--big-table", type=int, default=1024)
     ap.add_argument("--labels", action="store_true")
     ap.add_argument("--label-tenants", type=int, nargs="+", default=[16, 1024])
+    ap.add_argument("--bf", action="store_true")
     a = ap.parse_args()
     rs = np.random.default_rng(1)
     centres = rs.normal(size=(256, a.d)).astype(np.float32) * 2
@@ -62,8 +71,11 @@ def main():
     query = centres[rs.integers(0, 256, a.queries)] + rs.normal(size=(a.queries, a.d)).astype(np.float32)
     g = ggnn.GGNN()
     g.set_base(torch.from_numpy(base).cuda())
-    g.build(24, 0.5)
     q = torch.from_numpy(query).cuda()
+    if a.bf:
+        brute_force(a, g, q)
+        return
+    g.build(24, 0.5)
     if a.mixed:
         mixed(a, g, q)
         return
@@ -106,6 +118,41 @@ def main():
                           "n_dist": round(nd, 1), "n_pop": round(npop, 1),
                           "recall": round(float(rec), 4), "bf_filtered_ms": round(bf_ms, 3)}),
               flush=True)
+
+
+def brute_force(a, g, q):
+    """scan against matrix path of the filtered brute force, alternating per repeat"""
+    from ggnn_amd import _lib
+    rs = np.random.default_rng(3)
+
+    def ab(name, call, **extra):
+        scan, matrix = [], []
+        for _ in range(a.reps):
+            with _lib.hooks(BF_SCAN=1):
+                call()
+            scan.append(round(g.last_timing_ms()["bf_query_ms"], 3))
+            call()
+            matrix.append(round(g.last_timing_ms()["bf_query_ms"], 3))
+        print(json.dumps({"bf": name, **extra, "scan_ms": scan, "matrix_ms": matrix,
+                          "matrix_path": g.last_bf_query_matrix_path(),
+                          "rescanned": g.last_bf_query_rescanned()}), flush=True)
+
+    ab("unfiltered", lambda: g.bf_query(q, a.k))
+    for share in (1.0, 0.5, 0.1, 0.01):
+        mask = np.random.default_rng(int(share * 1000)).random(a.n) < share
+        bits = ggnn.pack_filter(mask).cuda()
+        ab("bitset", lambda: g.bf_query_filtered(q, a.k, filter=bits), allowed=share)
+    for T in (a.tenants, a.big_table):
+        tenant = rs.integers(0, T, a.n).astype(np.int32)
+        ids = torch.from_numpy(rs.integers(0, T, a.queries).astype(np.int32)).cuda()
+        g.set_labels(tenant)
+        ab("labels", lambda: g.bf_query_labeled(q, a.k, labels=ids), tenants=T)
+        g.set_labels(None)
+        # (the table row by row: T x N booleans at once would be a gigabyte at T = 1024)
+        words = np.stack([ggnn.pack_filter(tenant == t).numpy() for t in range(T)])
+        g.set_filters(torch.from_numpy(words))
+        ab("table", lambda: g.bf_query_filtered_by(q, a.k, filter_ids=ids), rows=T)
+        g.set_filters(None)
 
 
 def mixed(a, g, q):
