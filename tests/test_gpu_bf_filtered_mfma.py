@@ -13,6 +13,12 @@ The filtered single-chunk kernels exist with the constant list length 18 only (k
 rounded up to it); a filtered call with k > 10 at D <= 128 runs the chunked kernel with its one
 chunk of 128 columns (bf_filtered_runs_chunked, bf_common.hpp): K = 100 here, and K = 30 at
 D = 64 / 100 / 128 in test_longer_lists_run_the_chunked_kernel (columns past D are padding).
+
+Labels run everything the bitset and the table run (section 4b): the chunked kernels at T = 2 / 3 /
+4 tiles per group (the [2][T][32] row labels beside the group norms), several segments per
+workgroup, the re-scan of uncertified queries, a column window at an offset that is no multiple of
+32 (which, unlike a bitset's, stays on the tile kernels) and K = 30 on the one-chunk chunked kernel;
+and the chunked kernels also run with uint8 (both measures) and float16 rows.
 """
 import functools
 
@@ -312,6 +318,147 @@ def test_labels(ops, orc, kind, measure, K):
     assert d[sel].tobytes() == u_d.cpu().numpy()[sel].tobytes()
 
 
+# ---- 4b. labels beyond D = 128, the default tile group and the aligned window -----------------------
+QLABEL_CYCLE = (-1, 0, 1, 2, 3, 4, 7, 0)   # -1: unfiltered; 7: no row carries it; 4: six rows
+
+
+def _label_column(n, seed):
+    """the column of tests/test_gpu_filtered_layout_matrix.py: classes of about 50 / 30 / 15 / 5 %
+    and label 4 on exactly six rows (fewer than K)"""
+    rs = np.random.default_rng(seed)
+    labels = rs.choice(5, n, p=[.5, .3, .15, .04, .01]).astype(np.int32)
+    had = labels == 4
+    forced = rs.choice(np.nonzero(~had)[0], 6, replace=False)
+    labels[had] = 3
+    labels[forced] = 4
+    return labels
+
+
+def _query_labels(nq):
+    """every value within every 8 consecutive queries: mixed within each wave's 32"""
+    return np.resize(np.array(QLABEL_CYCLE, np.int32), nq)
+
+
+def _labels_reference(orc, base, q, K, labels, qlabels, measure):
+    r_ids = np.full((q.shape[0], K), -1, np.int32)
+    r_d = np.full((q.shape[0], K), np.inf, np.float32)
+    for L in np.unique(qlabels):
+        sel = np.nonzero(qlabels == L)[0]
+        allowed = np.ones(base.shape[0], bool) if L == -1 else labels == L
+        r_ids[sel], r_d[sel] = bf_filtered_reference(orc, base, q[sel], K, allowed, measure)
+    fin = np.isfinite(r_d).sum(1)
+    assert (fin[qlabels == 7] == 0).all() and (fin[qlabels == 4] == min(K, 6)).all()
+    assert (fin[(qlabels != 7) & (qlabels != 4)] == K).all()
+    return r_ids, r_d
+
+
+@functools.lru_cache(maxsize=None)
+def _chunked_labels(D):
+    return _label_column(9100, 400 + D), _query_labels(301)
+
+
+@functools.lru_cache(maxsize=None)
+def _chunked_labels_reference(orc, D, measure):
+    base, q, _ = _chunked_data(D)
+    labels, qlabels = _chunked_labels(D)
+    return _labels_reference(orc, base, q, 10, labels, qlabels, measure)
+
+
+@pytest.mark.parametrize("tiles", [2, 3, 4])
+@pytest.mark.parametrize("measure", [0, 1])
+@pytest.mark.parametrize("kind,D", [("f32", 200), ("f32", 960), ("bf16", 200)])
+def test_chunked_kernels_labels(ops, orc, kind, D, measure, tiles):
+    """test_chunked_kernels under labels: the [2][T][32] row labels beside the group norms
+    (bf_filter_lds_words(kBfLabels, T > 1)) at T = 2 / 3 / 4, the padding tiles of the last group
+    included"""
+    from ggnn_amd import _lib
+    base, q, _ = _chunked_data(D)
+    labels, qlabels = _chunked_labels(D)
+    d_base, d_q, d_lab, d_ql = _cast(base, kind), _cast(q, kind), _i32(labels), _i32(qlabels)
+    with _lib.hooks(BF_TILES=tiles):
+        ids, d, resc = both_paths(lambda: ops.bf_query_labeled(d_base, d_q, 10, d_lab, d_ql, measure,
+                                                               rescanned=True))
+    r_ids, r_d = _chunked_labels_reference(orc, D, measure)
+    assert_same(ids, d, r_ids, r_d, (kind, D, measure, tiles, resc))
+
+
+@pytest.mark.parametrize("kind,D,measure", [("u8", 256, 0), ("u8", 256, 1), ("f16", 256, 0)],
+                         ids=["u8-D256-l2", "u8-D256-cos", "f16-D256-l2"])
+def test_chunked_kernels_other_element_types(ops, orc, kind, D, measure):
+    """the element types the chunked filtered kernels never ran with: uint8 beyond the integer
+    kernels' D <= 128 under both measures, float16 beyond one chunk; the 30 % bitset and labels,
+    at the default tiles per group"""
+    base, q, allowed = _chunked_data(D)
+    labels, qlabels = _chunked_labels(D)
+    d_base, d_q = _cast(base, kind), _cast(q, kind)
+    bits, d_lab, d_ql = _bits(allowed), _i32(labels), _i32(qlabels)
+    ids, d, resc = both_paths(lambda: ops.bf_query_filtered(d_base, d_q, 10, bits, measure,
+                                                            rescanned=True))
+    r_ids, r_d = _chunked_reference(orc, D, measure)
+    assert_same(ids, d, r_ids, r_d, (kind, D, measure, "bitset", resc))
+    ids, d, resc = both_paths(lambda: ops.bf_query_labeled(d_base, d_q, 10, d_lab, d_ql, measure,
+                                                           rescanned=True))
+    r_ids, r_d = _chunked_labels_reference(orc, D, measure)
+    assert_same(ids, d, r_ids, r_d, (kind, D, measure, "labels", resc))
+
+
+@pytest.mark.parametrize("tiles", [2, 3, 4])
+def test_chunked_many_segments_per_workgroup_labeled(ops, tiles):
+    """test_chunked_many_segments_per_workgroup_filtered with labels in place of the table: a
+    workgroup that runs several segments in one do/while stages the 128 query labels of each anew.
+    Labels mixed within every 32 queries, -1 and a label no row carries (4) among them; compared
+    with the scan on every query, and every reported row carries its query's label"""
+    from ggnn_amd import _lib
+    N, Nq, D = 4100, 40_000, 132
+    rng = np.random.default_rng(77)
+    base = rng.normal(size=(N, D)).astype(np.float32)
+    q = rng.normal(size=(Nq, D)).astype(np.float32)
+    labels = rng.choice(4, N, p=[0.5, 0.05, 0.449, 0.001]).astype(np.int32)
+    qlabels = rng.integers(-1, 5, Nq).astype(np.int32)
+    for w in range(0, Nq - 31, 32):                        # mixed within every 32 queries
+        assert len(np.unique(qlabels[w:w + 32])) >= 3
+    d_base, d_q, d_lab, d_ql = _cast(base, "f32"), _cast(q, "f32"), _i32(labels), _i32(qlabels)
+    with _lib.hooks(BF_TILES=tiles):
+        ids, d, resc = both_paths(lambda: ops.bf_query_labeled(d_base, d_q, 10, d_lab, d_ql, 0,
+                                                               rescanned=True))
+    for L in range(0, 4):
+        sel = ids[qlabels == L]
+        assert (labels[sel[sel >= 0]] == L).all(), L
+        assert (sel >= 0).sum(1).min() == min(10, int((labels == L).sum())), L
+    assert (ids[qlabels == -1] >= 0).all()
+    assert (ids[qlabels == 4] == -1).all() and np.isinf(d[qlabels == 4]).all()
+
+
+@pytest.mark.parametrize("measure", [0, 1])
+def test_labels_unaligned_window(ops, orc, measure):
+    """the label column as a window at offset 4517 of a longer one: labels are read per row, so an
+    offset that is no multiple of 32 stays on the tile kernels (unlike a bitset) and is exact"""
+    D, K, off = 128, 10, 4517
+    base, q, _ = _bitset_data(D)
+    labels, qlabels = _label_column(NB, 91), _query_labels(NQ)
+    rs = np.random.default_rng(92)
+    wide = np.concatenate([rs.integers(-1, 8, off), labels, rs.integers(-1, 8, 100)]).astype(np.int32)
+    d_base, d_q, d_wide, d_ql = _cast(base, "f32"), _cast(q, "f32"), _i32(wide), _i32(qlabels)
+    ids, d, resc = both_paths(lambda: ops.bf_query_labeled(d_base, d_q, K, d_wide, d_ql, measure,
+                                                           bit_offset=off, rescanned=True))
+    r_ids, r_d = _labels_reference(orc, base, q, K, labels, qlabels, measure)
+    assert_same(ids, d, r_ids, r_d, (measure, off, resc))
+
+
+@pytest.mark.parametrize("D", [64, 100])
+def test_longer_lists_run_the_chunked_kernel_labels(ops, orc, D):
+    """K = 30 at D <= 128 under labels: the chunked kernel on its one chunk of 128 columns, half of
+    them / 28 past the end of the row"""
+    K = 30
+    base, q, _ = _bitset_data(D)
+    labels, qlabels = _label_column(NB, 93 + D), _query_labels(NQ)
+    d_base, d_q, d_lab, d_ql = _cast(base, "f32"), _cast(q, "f32"), _i32(labels), _i32(qlabels)
+    ids, d, resc = both_paths(lambda: ops.bf_query_labeled(d_base, d_q, K, d_lab, d_ql, 0,
+                                                           rescanned=True))
+    r_ids, r_d = _labels_reference(orc, base, q, K, labels, qlabels, 0)
+    assert_same(ids, d, r_ids, r_d, (D, resc))
+
+
 # ---- 5. the certificate under a filter ------------------------------------------------------------
 def _far_tight(N, D, seed):
     """the data of test_bf_mfma_uncertifiable_data_is_rescanned (tests/test_gpu_bf_exact.py)"""
@@ -345,6 +492,18 @@ def test_uncertifiable_data_is_rescanned_under_a_filter(ops):
         assert table[f][ids[fids == f]].all(), f
     assert (ids[fids == 3] == -1).all()
     assert (ids[fids == -1] >= 0).all()
+    # ... and labels mixed within the batch: the re-scan picks the label by the query's real index
+    labels = rs.integers(0, 3, N).astype(np.int32)
+    qlabels = rs.integers(-1, 4, Nq).astype(np.int32)    # 3: no row carries it -> empty
+    d_lab, d_ql = _i32(labels), _i32(qlabels)
+    ids, d, resc = both_paths(lambda: ops.bf_query_labeled(d_base, d_q, K, d_lab, d_ql, 0,
+                                                           rescanned=True))
+    print(f"uncertifiable, mixed labels: {resc} of {Nq} queries rescanned")
+    assert resc > 0
+    for L in range(3):
+        assert (qlabels == L).any() and (labels[ids[qlabels == L]] == L).all(), L
+    assert (ids[qlabels == 3] == -1).all() and np.isinf(d[qlabels == 3]).all()
+    assert (ids[qlabels == -1] >= 0).all()
 
 
 def test_certifiable_data_is_certified_under_a_filter(ops, orc):
