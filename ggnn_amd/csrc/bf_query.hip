@@ -509,14 +509,6 @@ void launch_bf_rescan(const BfLaunch& a, const uint32_t* qlist, const uint32_t* 
   launch_bf_scan(a, slices, rows, qlist, qcount, tmp_ids, tmp_dists, stream);
 }
 
-// the all-ones / all-zero rows of a launch with filter ids that brings none (operator seam): made
-// in stream-ordered scratch for the duration of the launch, on either path
-struct BfFilterConsts {
-  uint32_t* p;
-  hipStream_t stream;
-  ~BfFilterConsts() { scratch_free(p, stream); }
-};
-
 void launch_bf_query(const BfLaunch& a_in, hipStream_t stream)
 {
   if (a_in.n_rescanned)
@@ -535,9 +527,11 @@ void launch_bf_query(const BfLaunch& a_in, hipStream_t stream)
   GGNN_REQUIRE(!table || (a_in.filter_table.words != 0 && a_in.filter_table.num_filters != 0),
                GGNN_INVALID_ARGUMENT, "filter ids need a filter table");
   BfLaunch a = a_in;
-  BfFilterConsts consts{table ? filter_consts_scratch(a.filter_table, stream) : nullptr, stream};
+  // the all-ones / all-zero rows of a launch with filter ids that brings none (operator seam): made
+  // in stream-ordered scratch for the duration of the launch, on either path
+  ScratchGuard consts{table ? filter_consts_scratch(a.filter_table, stream) : nullptr, stream};
   if (consts.p)
-    a.filter_table.consts = consts.p;
+    a.filter_table.consts = static_cast<const uint32_t*>(consts.p);
 
   // large batches: Q x B^T on the matrix cores (bf_mfma.hip); hook BF_SCAN = 1 forces the scan,
   // for filtered calls too (the A/B switch).  A filtered call keeps the scan

@@ -338,6 +338,12 @@ void launch_merge_results_range(uint32_t Nq, uint32_t k, uint32_t num_parts, uin
 // stream-ordered scratch of one launch from a private, bounded pool per device (scratch.cpp)
 void* scratch_alloc(size_t bytes, hipStream_t stream);
 void scratch_free(void* p, hipStream_t stream);
+// frees a launch's scratch (null: nothing) at scope exit, on the launch's stream
+struct ScratchGuard {
+  void* p;
+  hipStream_t stream;
+  ~ScratchGuard() { scratch_free(p, stream); }
+};
 
 // host layout math (graph_config.cpp)
 void graph_config_init(uint32_t N, uint32_t D, uint32_t KBuild, ggnn_graph_config* out);

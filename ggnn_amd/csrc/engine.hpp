@@ -187,7 +187,9 @@ struct Shard {
 
 using namespace ggnn_amd;
 
-// destroying a DeviceCtx switches devices; leave the caller's current device as it was
+// the engine switches devices (hipSetDevice) while it works, and so does destroying a DeviceCtx;
+// callers such as PyTorch keep their own notion of the current device, so every entry point leaves
+// it as it found it
 struct DeviceRestoreGuard {
   int prev{-1};
   DeviceRestoreGuard() { (void)hipGetDevice(&prev); }
