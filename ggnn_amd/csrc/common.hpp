@@ -170,6 +170,9 @@ struct QueryLaunch {
   const uint8_t* ps_codes{nullptr};
   const float* ps_params{nullptr};
   uint32_t ps_Dc{0};
+  // the caller knows that params[5] of this copy is set (lossless on a power-of-two grid, squared
+  // L2): the launch may take the kernels that read exact distances from the codes (traversal.hpp)
+  bool ps_lossless{false};
   uint32_t* n_rows{nullptr};  // optional [Nq x 2]: float rows and code rows read per query
   // optional allowed-id bitset (device; bit (id + filter_bit_offset) of the uint32 words): the
   // search reports allowed ids only (query_filtered.hip)

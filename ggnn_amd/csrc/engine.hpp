@@ -158,6 +158,7 @@ struct Shard {
   // (non-finite values)
   DeviceBuffer ps_codes, ps_params;
   int ps_state{0};
+  bool ps_lossless{false};  // params[5] of the copy: lossless on a power-of-two grid (squared L2)
   ggnn_measure ps_measure{GGNN_EUCLIDEAN};
 
   static size_t pool_bytes(const ggnn_graph_config& c)

@@ -71,6 +71,7 @@ QueryLaunch ggnn_handle::shard_launch(const DeviceCtx& ctx, uint32_t si, const Q
     ql.ps_codes = sh.ps_codes.as<uint8_t>();
     ql.ps_params = sh.ps_params.as<float>();
     ql.ps_Dc = prescreen_code_dim(pad_D);
+    ql.ps_lossless = sh.ps_lossless;
   }
   ql.filter_bits = df.bits;
   ql.filter_bit_offset = sh.global_id * cfg.N;

@@ -213,6 +213,7 @@ bool ggnn_handle::ensure_prescreen(DeviceCtx& ctx, uint32_t si, ggnn_measure mea
       if (ctx.shard_stream[i])
         GGNN_HIP_CHECK(hipStreamSynchronize(ctx.shard_stream[i]));
     sh.ps_state = 0;
+    sh.ps_lossless = false;
   }
   if (sh.ps_state == 0) {
     const uint32_t Dc = prescreen_code_dim(pad_D);
@@ -243,6 +244,7 @@ bool ggnn_handle::ensure_prescreen(DeviceCtx& ctx, uint32_t si, ggnn_measure mea
                                   ctx.stream));
     GGNN_HIP_CHECK(hipStreamSynchronize(ctx.stream));
     sh.ps_state = header[4] != 0.f ? 1 : -1;
+    sh.ps_lossless = sh.ps_state > 0 && header[5] != 0.f;
     sh.ps_measure = measure;
     GGNN_LOG(1, "[GPU: %d] pre-screen copy of part %u (%s): scale %g, max coding error %g%s",
              ctx.device, sh.global_id, measure == GGNN_EUCLIDEAN ? "L2" : "cosine", header[0],

@@ -38,6 +38,7 @@ enum Hook {
   kHookBfI8Refresh,     // BF_I8_REFRESH    stages between bound exchanges of the i8 kernel's slices
   kHookBfI8Seed,        // BF_I8_SEED       rows of the i8 kernel's seeding launch (0 = none)
   kHookMergeCounting,   // MERGE_COUNTING   1 = merge launches without counters use the counting kernel too
+  kHookPsExact,         // PS_EXACT         0 = query kernels always run the float phase, also on a lossless-grid base
   kHookCount
 };
 

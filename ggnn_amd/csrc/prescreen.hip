@@ -7,6 +7,10 @@
 // is first tried as a power of two: integer (or dyadic) data with a range <= 255 s per dimension
 // (SIFT) is then coded without loss (e_max = 0).  Otherwise the rows are coded again with the
 // tightest scale, max range / 255.
+// A squared-L2 copy that is lossless AND whose offsets lie on the grid of s is published as such
+// (params[5], "lossless grid"): every row then IS o + s*c, an integer multiple of s below 2^24 s in
+// every dimension, and the query kernels take exact distances from the codes (traversal.hpp,
+// "Distances from lossless codes").
 // For the cosine measure the rows are coded after normalisation to unit length (a zero row stays
 // zero); e_max then bounds the error against the exactly normalised row.
 #include "traversal.hpp"
@@ -88,15 +92,25 @@ __global__ void __launch_bounds__(kPsThreads)
     params[2] = 0.f;      // e_max, raised by ps_encode_kernel
     params[3] = sqrtf(osq) * (1.f + 1e-6f);
     params[4] = ok ? 1.f : 0.f;
-    params[5] = range;  // for ps_retry_kernel
+    params[5] = range;  // for ps_retry_kernel, which replaces it by the lossless-grid flag
     params[6] = 1.f;    // coding pass wanted
     params[7] = static_cast<float>(measure);
   }
 }
 
 // after the first coding pass: lossy with the power-of-two scale -> ask for a second pass with
-// the tightest scale
-__global__ void ps_retry_kernel(float* params)
+// the tightest scale.  Lossless: no second pass, and params[5] (the range, whose use ends here)
+// becomes the lossless-grid flag of the copy:
+//   * squared L2 (unit-normalised cosine rows are never lossless), scale 2^-40 .. 2^40,
+//   * e_max == 0 after the power-of-two pass: v == o + s*c for every coded value (the residual is
+//     taken in double, where o + s*c is exact under the next condition),
+//   * every offset is k*s with an integer |k| <= 2^23, tested without rounding: k = o * (1/s) is a
+//     scaling by a power of two, |k| <= 2^23 makes k == rint(k) an exact test, and k * s == o
+//     catches a product that underflowed.
+// Then every row value is (k + c) * s with |k + c| < 2^24: all arithmetic on differences of such
+// values is integer arithmetic in float32.  The flag is written by every coding, so coding again
+// for another measure resets it.
+__global__ void ps_retry_kernel(float* params, uint32_t Dc)
 {
   const float range = params[5];
   if (params[4] != 0.f && params[2] > 0.f && range > 0.f) {
@@ -104,10 +118,21 @@ __global__ void ps_retry_kernel(float* params)
     params[0] = s;
     params[1] = 1.f / s;
     params[2] = 0.f;
+    params[5] = 0.f;
     params[6] = 1.f;
   }
-  else
+  else {
+    const float s = params[0], inv_s = params[1];
+    bool grid = params[4] != 0.f && params[2] == 0.f &&
+                params[7] == static_cast<float>(GGNN_EUCLIDEAN) && s >= 0x1p-40f && s <= 0x1p40f;
+    const float* offs = params + kPsHeader;
+    for (uint32_t d = 0; d < Dc; ++d) {
+      const float k = offs[d] * inv_s;
+      grid = grid && fabsf(k) <= 0x1p23f && k == rintf(k) && k * s == offs[d];
+    }
+    params[5] = grid ? 1.f : 0.f;
     params[6] = 0.f;
+  }
 }
 
 // sum of squares of one row in double, lpr lanes per row; every lane of the row gets the total
@@ -272,7 +297,7 @@ void launch_prescreen_encode(const float* base, uint32_t N, uint32_t D, ggnn_mea
                      Dc, B, static_cast<int>(measure), params);
   hipLaunchKernelGGL(ps_encode_kernel, grid, dim3(kPsThreads), 0, stream, base, N, D, Dc, lpr,
                      inv_norm, codes, params);
-  hipLaunchKernelGGL(ps_retry_kernel, dim3(1), dim3(1), 0, stream, params);
+  hipLaunchKernelGGL(ps_retry_kernel, dim3(1), dim3(1), 0, stream, params, Dc);
   hipLaunchKernelGGL(ps_encode_kernel, grid, dim3(kPsThreads), 0, stream, base, N, D, Dc, lpr,
                      inv_norm, codes, params);
   GGNN_HIP_CHECK(hipGetLastError());

@@ -76,6 +76,13 @@ struct QueryLadder {
     // early rows (traversal.hpp): graph rows of <= 24 neighbours, first row read 8 lanes x 16 bytes
     // (hook QUERY_EARLY = 0: the round-1..4 order, A/B and test hook)
     if constexpr (early_rows_layout<LPR, NCH, PSC>()) {
+      // Exact distances from lossless codes (traversal.hpp): when the caller knows the base's flag
+      // the ring-less kernels are taken in their two-phase variant PSX.  Every other launch -- a
+      // fractional base, the operator seam without the flag, hook PS_EXACT = 0 -- runs the kernels
+      // of PSC, the code objects they always were.  (The variants that keep a visited ring in LDS
+      // stay with PSC: at 7 waves per SIMD both phases would put 2-5 registers in scratch there.)
+      using PSX = typename ExactOf<PSC>::type;
+      const bool exact = args.ps_lossless != 0 && !std::is_same<PSX, PSC>::value;
       // the tag set of long rings (513..2016 iterations): early rows only when the search cannot
       // wrap its ring -- then the set is ring-less too (no store per pop: a store in flight turns
       // every wait for the requested rows into vmcnt(0)); otherwise the round-4 order below
@@ -87,9 +94,11 @@ struct QueryLadder {
         const size_t tag_lds = tag_set_lds_bytes(sorted, args.cache - sorted) +
                                DistEngine<BaseT, LPR, NCH, PSC::enabled>::kQueryLdsBytes;
         if (args.tag_bits == 8)
-          go(query_kernel<BaseT, LPR, NCH, 1, MODE, PSC, -8, true, true>, tag_lds);
+          go(exact ? query_kernel<BaseT, LPR, NCH, 1, MODE, PSX, -8, true, true>
+                   : query_kernel<BaseT, LPR, NCH, 1, MODE, PSC, -8, true, true>, tag_lds);
         else
-          go(query_kernel<BaseT, LPR, NCH, 1, MODE, PSC, -9, true, true>, tag_lds);
+          go(exact ? query_kernel<BaseT, LPR, NCH, 1, MODE, PSX, -9, true, true>
+                   : query_kernel<BaseT, LPR, NCH, 1, MODE, PSC, -9, true, true>, tag_lds);
         return;
       }
       if (args.KBuild <= 8 * kEarlySteps && sorted <= 64 && !tagged && hook(kHookQueryEarly) != 0) {
@@ -100,13 +109,15 @@ struct QueryLadder {
         // (SortedList<R, HB, true>; launch_query allocates the overflow lists then)
         const bool ringless = args.ring && args.tag_bits == 0;
         if (hb == 1 && ringless)
-          go(query_kernel<BaseT, LPR, NCH, 1, MODE, PSC, 1, true, true>,
+          go(exact ? query_kernel<BaseT, LPR, NCH, 1, MODE, PSX, 1, true, true>
+                   : query_kernel<BaseT, LPR, NCH, 1, MODE, PSC, 1, true, true>,
              wave_lds_bytes(sorted, 1) + qrow);
         else if (hb == 1)
           go(query_kernel<BaseT, LPR, NCH, 1, MODE, PSC, 1, true>,
              wave_lds_bytes(args.cache, 1) + qrow);
         else if (hb == 2 && ringless)
-          go(query_kernel<BaseT, LPR, NCH, 1, MODE, PSC, 2, true, true>,
+          go(exact ? query_kernel<BaseT, LPR, NCH, 1, MODE, PSX, 2, true, true>
+                   : query_kernel<BaseT, LPR, NCH, 1, MODE, PSC, 2, true, true>,
              wave_lds_bytes(sorted, 2) + qrow);
         else if (hb == 2)
           go(query_kernel<BaseT, LPR, NCH, 1, MODE, PSC, 2, true>,
@@ -222,6 +233,7 @@ void launch_query(const QueryLaunch& a, hipStream_t stream)
     args.ps_codes = a.ps_codes;
     args.ps_params = a.ps_params;
     args.ps_Dc = a.ps_Dc;
+    args.ps_lossless = (a.ps_lossless && a.measure == GGNN_EUCLIDEAN && hook(kHookPsExact) != 0) ? 1u : 0u;
   }
 
   if (a.filter_bits) {

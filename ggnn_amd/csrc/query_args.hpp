@@ -32,6 +32,10 @@ struct QueryArgs {
   // see FilteredQueryArgs)
   const uint32_t* filter_bits;
   uint32_t filter_bit_offset;
+  // HOST side only (in the struct's tail padding: size and every offset are what they were, and
+  // no kernel reads it): the launch may pick the kernels that take exact distances from lossless
+  // pre-screen codes (ExactOf in traversal.hpp; QueryLaunch::ps_lossless and hook PS_EXACT)
+  uint32_t ps_lossless;
 };
 
 // Arguments of the filtered kernels (query_filtered.hip): per-query filters make filter_bits a

@@ -108,12 +108,17 @@ struct FilteredLadder {
       const uint32_t hb = sorted <= 64 ? vis_hash_regs(args.cache - sorted) : 0;
       if (hb != 0 && args.KBuild <= 8 * kEarlySteps && hook(kHookQueryEarly) != 0) {
         const size_t qrow = DistEngine<BaseT, LPR, NCH, PSC::enabled>::kQueryLdsBytes;
+        // (PSX: the two-phase variant for a base known to be lossless, as in QueryLadder)
+        using PSX = typename ExactOf<PSC>::type;
+        const bool exact = args.ps_lossless != 0 && !std::is_same<PSX, PSC>::value;
         if (hb == 1)
-          launch_wave_per_query(filtered_kernel<FILT, BaseT, LPR, NCH, 1, MODE, PSC, 1, true>(), args,
-                                wave_lds_bytes(args.cache, 1) + qrow, stream);
+          launch_wave_per_query(exact ? filtered_kernel<FILT, BaseT, LPR, NCH, 1, MODE, PSX, 1, true>()
+                                      : filtered_kernel<FILT, BaseT, LPR, NCH, 1, MODE, PSC, 1, true>(),
+                                args, wave_lds_bytes(args.cache, 1) + qrow, stream);
         else
-          launch_wave_per_query(filtered_kernel<FILT, BaseT, LPR, NCH, 1, MODE, PSC, 2, true>(), args,
-                                wave_lds_bytes(args.cache, 2) + qrow, stream);
+          launch_wave_per_query(exact ? filtered_kernel<FILT, BaseT, LPR, NCH, 1, MODE, PSX, 2, true>()
+                                      : filtered_kernel<FILT, BaseT, LPR, NCH, 1, MODE, PSC, 2, true>(),
+                                args, wave_lds_bytes(args.cache, 2) + qrow, stream);
         return;
       }
     }

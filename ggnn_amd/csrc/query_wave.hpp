@@ -7,11 +7,13 @@
 
 namespace ggnn_amd {
 
+// (the kernels of PrescreenExact also derive the certificate of exact distances from lossless codes)
 template <class PSC, typename BaseT>
 GGNN_DEV void load_prescreen(PSC& ps, const QueryArgs& a, const BaseT* qrow)
 {
   if constexpr (PSC::enabled)
-    ps.load(a.ps_codes, a.ps_params, a.ps_Dc, reinterpret_cast<const float*>(qrow), a.D);
+    ps.template load<PsExact<PSC>::value>(a.ps_codes, a.ps_params, a.ps_Dc,
+                                          reinterpret_cast<const float*>(qrow), a.D);
 }
 
 // the filter of the wave of query n.  IdFilter: this wave's bitset is the call's, or the row of the

@@ -43,6 +43,9 @@
       lds_raw + (is_tag_set(HB) ? tag_set_lds_ints(a.sorted, static_cast<uint32_t>(-HB))
                                 : wave_lds_ints(GR ? a.sorted : a.cache, HB)));
   PSC ps;
+  // (PrescreenExact: with the certificate of exact distances from lossless codes, traversal.hpp)
+  constexpr bool kExactCodes = PsExact<PSC>::value;
+  static_assert(!kExactCodes || EARLY, "exact distances from codes: early-rows kernels only");
   load_prescreen(ps, a, query + static_cast<size_t>(n) * a.D);
 
   SortedList<R, HB, GR> sl;
@@ -90,6 +93,17 @@
       int cand;
       if (anchor == spec_key)
         cand = in_row ? spec_row : kEmptyKey;
+      else if constexpr (kExactCodes && !FILT::enabled) {
+        // (the row's address as a scalar base + lane offset: the per-lane 64-bit address of the form
+        // below is loop invariant, and the unfiltered two-phase kernels have no register pair left for it --
+        // it went to scratch and its reload put a vmcnt(0) in front of this load)
+        const uint64_t rp = reinterpret_cast<uint64_t>(
+            a.graph0 + static_cast<size_t>(static_cast<uint32_t>(anchor)) * a.KBuild);
+        const int32_t* row = reinterpret_cast<const int32_t*>(
+            (static_cast<uint64_t>(static_cast<uint32_t>(uni(static_cast<int>(rp >> 32)))) << 32) |
+            static_cast<uint32_t>(uni(static_cast<int>(rp))));
+        cand = in_row ? row[lane] : kEmptyKey;
+      }
       else
         cand = in_row ? a.graph0[static_cast<size_t>(static_cast<uint32_t>(anchor)) * a.KBuild + lane]
                       : kEmptyKey;
@@ -120,8 +134,8 @@
         er.issue(ps, cand);
         __builtin_amdgcn_s_setprio(0);
         sl.pop_commit(anchor, lds.known);
-        cnt_dist += fetch_early<MODE>(sl, de, lds, cand, er, ps, cnt_rows, prefetch_head_row,
-                                      nullptr, idf);
+        cnt_dist += fetch_early<MODE, true, kExactCodes>(sl, de, lds, cand, er, ps, cnt_rows,
+                                                  prefetch_head_row, nullptr, idf);
       }
       else {
         EarlyRows<DE> er;

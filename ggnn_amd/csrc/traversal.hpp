@@ -1368,7 +1368,21 @@ GGNN_DEV void compute_distances(const DE& de, const WaveLds& lds, int nsurv,
 // these are covered by the relative margin m = 4(Dc+32)u and the absolute slack
 // e_q(1+m) + 8u(||q|| + ||o||) + e_max used in threshold().
 // ---------------------------------------------------------------------------------------------
-constexpr int kPsHeader = 8;  // params: [0] s  [1] 1/s  [2] e_max  [3] ||o||  [4] valid  [8..] o_d
+//
+// Distances from lossless codes (query kernels, squared L2).  prescreen.hip publishes params[5] = 1
+// for a copy coded WITHOUT loss on a power-of-two grid: every row is x_d = o_d + s*c_d exactly, with
+// o_d = k_d*s, |k_d| <= 2^23.  A query with q_d = o_d + s*cq_d, cq_d an integer in [0, 255], in every
+// dimension -- tested in float32 without rounding: s*cq_d is exact (8 bits times a power of two) and
+// so is the sum, (k_d + cq_d)*s with |k_d + cq_d| < 2^24, hence `o_d + s*cq_d == q_d` compares the
+// real numbers -- lies on the same grid.  Then x_d - q_d = s*(c_d - cq_d) is representable, and so
+// is every partial sum of its squares, s^2 times an integer <= Dc * 255^2 < 2^24 (Dc <= 128: early
+// rows): the float phase (diff = o - q, fmaf(diff, diff, a), group_sum; traversal order, FMA or not)
+// rounds nowhere and returns s^2 * S, S = sum (cq_d - c_d)^2 -- the integer the verdicts already
+// hold.  fetch_early<.., EXACT> takes the distance from there: no threshold, no compaction, no float
+// rows.  The certificate is wave-uniform (Prescreen::s2 != 0); any other base or query (fractional,
+// clamped, off the grid) keeps the float phase.  tests/test_lossless_math.py re-derives all of this.
+constexpr int kPsHeader = 8;  // params: [0] s  [1] 1/s  [2] e_max  [3] ||o||  [4] valid
+                              //         [5] lossless grid  [8..] o_d
 struct NoPrescreen {
   static constexpr bool enabled = false;
 };
@@ -1394,6 +1408,8 @@ struct Prescreen {
   float inv_s, slack, m;
   bool usable;
   bool all_chunks;  // wave-uniform: the code row fills every chunk of every lane
+  float s2;         // wave-uniform: s * s when base and query lie on the lossless grid, else 0
+                    // (load<true> only; ONE scalar register for flag and factor)
 
   GGNN_DEV bool chunk_valid(int c) const
   {
@@ -1409,9 +1425,17 @@ struct Prescreen {
   }
 
   // D: float row length of the query (multiple of 4, <= Dc)
+  // EXACT (the kernels of PrescreenExact): also derive the certificate of "Distances from lossless
+  // codes" above
+  template <bool EXACT = false>
   GGNN_DEV void load(const uint8_t* codes_, const float* params, uint32_t Dc_, const float* qrow,
                      uint32_t D)
   {
+    constexpr bool kCert = EXACT && MODE_ == kL2;
+    [[maybe_unused]] float s_grid = 0.f;
+    [[maybe_unused]] bool on_grid = true;
+    if constexpr (kCert)
+      s_grid = params[0];
     codes = codes_;
     Dc = Dc_;
     g = threadIdx.x % LPR;
@@ -1473,6 +1497,8 @@ struct Prescreen {
           eq = fmaf(diff, diff, eq);
           qs = fmaf(qe[e], qe[e], qs);
           w[j] |= static_cast<uint32_t>(code) << (8 * e);
+          if constexpr (kCert)
+            on_grid &= (oe[e] + s_grid * code == qe[e]);  // exact on a lossless-grid base (see above)
         }
         qq = __builtin_amdgcn_udot4(w[j], w[j], qq, false);
       }
@@ -1486,6 +1512,11 @@ struct Prescreen {
     const float q_norm = (MODE_ == kCos) ? 1.f : sqrtf(group_sum<LPR>(qs));
     const float e_q = params[0] * sqrtf(group_sum<LPR>(eq)) * (1.f + m);
     slack = e_q + 8.f * u * (q_norm + params[3]) + params[2];
+    s2 = 0.f;
+    if constexpr (kCert) {
+      if (params[5] != 0.f && __all(on_grid))
+        s2 = s_grid * s_grid;  // (>= 2^-80: never 0 on a certified base)
+    }
   }
 
   // sum (cq - c)^2 over this lane's chunks of one code row (exact)
@@ -1520,6 +1551,32 @@ struct Prescreen {
   }
 };
 
+// The pre-screen of the kernel VARIANTS that hold both phases (query kernels, early rows, squared
+// L2): the same reader under a name of its own, so that they are code objects of their own next to
+// the kernels of Prescreen<8, 1, kL2>, which stay what they were.  A launch takes them when the
+// caller knows the base's lossless-grid flag (QueryLaunch::ps_lossless); a wave whose query is off
+// the grid falls back to the float phase inside them.
+template <int LPR_, int NCH_, int MODE_ = kL2>
+struct PrescreenExact : Prescreen<LPR_, NCH_, MODE_> {
+};
+template <class PS>
+struct PsExact {
+  static constexpr bool value = false;
+};
+template <int LPR, int NCH, int MODE>
+struct PsExact<PrescreenExact<LPR, NCH, MODE>> {
+  static constexpr bool value = true;
+};
+// the two-phase counterpart of a pre-screen type (itself where there is none)
+template <class PS>
+struct ExactOf {
+  using type = PS;
+};
+template <>
+struct ExactOf<Prescreen<8, 1, kL2>> {
+  using type = PrescreenExact<8, 1, kL2>;
+};
+
 // code-row layout used next to a float-row layout <LPR, NCH> (a code row has a quarter of the
 // 16-byte chunks of the float row)
 template <int LPR, int NCH, int MODE>
@@ -1544,6 +1601,7 @@ template <class PS>
 struct PsLayout {
   static constexpr int lpr = PS::LPR, nch = PS::NCH;
 };
+
 template <>
 struct PsLayout<NoPrescreen> {
   static constexpr int lpr = 0, nch = 0;
@@ -1904,8 +1962,11 @@ GGNN_DEV void replay_lanes(SL& sl, unsigned long long m, const int k_of, const f
 // the VISITED test only and are not used.
 // filt (filtered search): the caller has requested the bit words of `cand` (IdFilter::request)
 // in front of er.issue()
-template <int MODE, bool COUNT = true, class SL, class DE, class PS, class ER, class HOOK,
-          class FILT = NoIdFilter>
+// EXACT (the kernels of PrescreenExact, squared L2; "Distances from lossless codes"): a wave whose
+// certificate holds (ps.s2 != 0) takes the distances from the code sums, as the branch for rows read
+// directly does.
+template <int MODE, bool COUNT = true, bool EXACT = false, class SL, class DE, class PS, class ER,
+          class HOOK, class FILT = NoIdFilter>
 GGNN_DEV int fetch_early(SL& sl, const DE& de, const WaveLds& lds, int cand, const ER& er,
                          const PS& ps, uint2& rows, HOOK&& after_filter,
                          const int32_t* translation = nullptr, FILT&& filt = FILT{})
@@ -1926,43 +1987,84 @@ GGNN_DEV int fetch_early(SL& sl, const DE& de, const WaveLds& lds, int cand, con
   if constexpr (PS::enabled) {
     if (nsurv == 0)
       return 0;
+    // lossless codes (EXACT kernels): the code sum IS the distance, times s^2 -- no threshold, no
+    // compaction, no float rows; the lane of the verdict keeps key and distance for the replay, as
+    // in the branch for rows read directly below.  Wave-uniform; constant false without EXACT.
+    constexpr bool kExact = EXACT && MODE == kL2;
+    if constexpr (kExact) {
+      static_assert(PS::LPR == 8 && PS::NCH == 1, "lossless codes: sums of at most 128 dimensions");
+      static_assert(PS::LPR * PS::NCH * 16 * 255 * 255 < (1 << 24), "s^2 * S must be exact");
+    }
+    bool exact = false;
+    if constexpr (kExact)
+      exact = ps.s2 != 0.f;
     // +inf (list not full yet, pre-screen unusable): nothing is dropped, every survivor is evaluated
-    const float s_thr = ps.threshold(sl.criteria());
+    const float crit = sl.criteria();
+    const float s_thr = exact ? crit : ps.threshold(crit);  // (exact: only "is it finite" is used)
     if (s_thr < inf_f())
       rows.y += nsurv;
     float S[kEarlySteps];
 #pragma unroll
     for (int s = 0; s < kEarlySteps; ++s)
       S[s] = group_sum<8>(ps.partial(er.v[s]));  // (every lane of the group holds the sum)
-    bool pass = alive && !(ER::of_my_step(S[0], S[1], S[2]) >= s_thr);
-    unsigned long long pm = __ballot(pass);   // ascending lanes = ascending candidates
-    const int mykey = ER::of_my_step(er.kk[0], er.kk[1], er.kk[2]);
-    if constexpr (!COUNT) {
-      pm = sl.drop_sorted(pm, mykey);
-      pass = (pm >> lane) & 1ull;
+    const float smine = ER::of_my_step(S[0], S[1], S[2]);
+    // this lane's candidate key.  The two-phase kernels select it here, for both phases (selected
+    // inside each branch it costs them 2-4 registers: scratch); the others after the ballot, where
+    // it always was -- their code is instruction for instruction what it was.
+    int mykey = kEmptyKey;
+    if constexpr (kExact)
+      mykey = ER::of_my_step(er.kk[0], er.kk[1], er.kk[2]);
+    float d_of;
+    int k_of;
+    unsigned long long m;
+    if (exact) {
+      d_of = ps.s2 * smine;
+      k_of = mykey;
+      m = __ballot(alive && d_of < crit);
+      if constexpr (!COUNT)
+        m = sl.drop_sorted(m, mykey);
     }
-    const int neval = __popcll(pm);
-    if (neval == 0)
-      return nsurv;
-    rows.x += neval;
-    constexpr int kSteps = StepsOf<DE::LPR, DE::NCH>::value;
-    constexpr int kExactSteps = (DE::NCH == 3 && DE::ROWS >= 8) ? 1 : (kSteps > 2) ? 2 : kSteps;
-    // keys of the candidates that pass -> LDS in candidate order (one write: the ballot is already
-    // in that order), float rows, distances -> LDS, replay.  (Routing the ~3 keys through scalar
-    // registers to the row groups and keeping the distances in their lanes -- no LDS between the
-    // verdicts and the replay -- was measured: identical results, 10k-query batch unchanged, 100k
-    // batch and build -2 %; not worth a second code path.  DESIGN.md Appendix B.)
-    if (pass)
-      lds.ckeys[__popcll(pm & ((1ull << lane) - 1ull))] = mykey;
-    __syncthreads();
-    compute_distances<MODE, DE, kExactSteps>(de, lds, neval, translation);
-    __syncthreads();
-    const float cd = lane < neval ? lds.cd0[lane] : inf_f();
-    const int ck = lane < neval ? lds.ckeys[lane] : kEmptyKey;
+    else {
+      bool pass = alive && !(smine >= s_thr);
+      unsigned long long pm = __ballot(pass);   // ascending lanes = ascending candidates
+      if constexpr (!kExact)
+        mykey = ER::of_my_step(er.kk[0], er.kk[1], er.kk[2]);
+      if constexpr (!COUNT) {
+        pm = sl.drop_sorted(pm, mykey);
+        pass = (pm >> lane) & 1ull;
+      }
+      const int neval = __popcll(pm);
+      if (neval == 0)
+        return nsurv;
+      rows.x += neval;
+      constexpr int kSteps = StepsOf<DE::LPR, DE::NCH>::value;
+      constexpr int kExactSteps = (DE::NCH == 3 && DE::ROWS >= 8) ? 1 : (kSteps > 2) ? 2 : kSteps;
+      // keys of the candidates that pass -> LDS in candidate order (one write: the ballot is already
+      // in that order), float rows, distances -> LDS, replay.  (Routing the ~3 keys through scalar
+      // registers to the row groups and keeping the distances in their lanes -- no LDS between the
+      // verdicts and the replay -- was measured: identical results, 10k-query batch unchanged, 100k
+      // batch and build -2 %; not worth a second code path.  DESIGN.md Appendix B.)
+      // (EXACT kernels count the lanes below with v_mbcnt: the lane mask of the other form is loop
+      // invariant, two registers the kernel holding both phases does not have -- it went to scratch)
+      int slot;
+      if constexpr (kExact)
+        slot = __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(pm >> 32),
+                                         __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(pm), 0u));
+      else
+        slot = __popcll(pm & ((1ull << lane) - 1ull));
+      if (pass)
+        lds.ckeys[slot] = mykey;
+      __syncthreads();
+      compute_distances<MODE, DE, kExactSteps>(de, lds, neval, translation);
+      __syncthreads();
+      d_of = lane < neval ? lds.cd0[lane] : inf_f();
+      k_of = lane < neval ? lds.ckeys[lane] : kEmptyKey;
+      m = __ballot(d_of < sl.criteria());
+    }
     if constexpr (kFiltered)
-      replay_lanes_filtered(sl, __ballot(cd < sl.criteria()), ck, cd, filt);
+      replay_lanes_filtered(sl, m, k_of, d_of, filt);
     else
-      replay_lanes(sl, __ballot(cd < sl.criteria()), ck, cd);
+      replay_lanes(sl, m, k_of, d_of);
     return nsurv;
   }
   else {

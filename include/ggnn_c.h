@@ -423,7 +423,14 @@ void ggnn_set_log_level(int level);
  *                             kernel that tests a candidate against the sorted part of the cache
  *                             only once it has passed the pre-screen; 1 = they run the counting
  *                             kernel, which scans the sorted part for every candidate first (same
- *                             graph; A/B and test hook) */
+ *                             graph; A/B and test hook)
+ *   PS_EXACT            1     early-rows query kernels on a float32 base whose pre-screen copy is
+ *                             lossless on a power-of-two grid (integer or dyadic data, squared L2)
+ *                             take a candidate's distance from its codes when the query lies on
+ *                             the grid too, and read no float row (kernel variants of their own,
+ *                             launched by the engine, which knows the copy's flag; the operator
+ *                             seam always runs the float rows); 0 = always the float rows (same
+ *                             results; A/B and test hook) */
 ggnn_status ggnn_set_hook(const char* name, int64_t value);
 /* back to environment / default */
 ggnn_status ggnn_reset_hook(const char* name);
