@@ -26,7 +26,8 @@ pytestmark = pytest.mark.skipif(
 
 @pytest.fixture(scope="module")
 def kernels(tmp_path_factory):
-    """{demangled kernel name: {metadata key: int}} over every gfx950 code object in the library."""
+    """{demangled kernel name: {metadata key: int}} over every gfx950 code object in the library
+    (also the fixture of tests/test_lossless_coverage.py)."""
     d = tmp_path_factory.mktemp("co")
     lib = shutil.copy(LIB, d)   # llvm-objdump writes the extracted bundles next to its input
     subprocess.run([os.path.join(LLVM, "llvm-objdump"), "--offloading", lib], cwd=d, check=True,
@@ -68,6 +69,16 @@ DEFAULT_KERNELS = [
     # long searches on the ring-less tag set
     ("query_kernel<float, 16, 2, 1, 0, Prescreen<8, 1, 0>, -8, true, true>", 72),
     ("query_kernel<float, 16, 2, 1, 0, Prescreen<8, 1, 0>, -9, true, true>", 72),
+    # the same on a base whose pre-screen copy is lossless (integer or dyadic data through the engine
+    # handle): distances from the codes, PrescreenExact; both layouts with every set, HB 1, 2, -8, -9
+    ("query_kernel<float, 16, 2, 1, 0, PrescreenExact<8, 1, 0>, 1, true, true>", 72),
+    ("query_kernel<float, 16, 2, 1, 0, PrescreenExact<8, 1, 0>, 2, true, true>", 72),
+    ("query_kernel<float, 8, 3, 1, 0, PrescreenExact<8, 1, 0>, 1, true, true>", 72),
+    ("query_kernel<float, 8, 3, 1, 0, PrescreenExact<8, 1, 0>, 2, true, true>", 72),
+    ("query_kernel<float, 16, 2, 1, 0, PrescreenExact<8, 1, 0>, -8, true, true>", 72),
+    ("query_kernel<float, 16, 2, 1, 0, PrescreenExact<8, 1, 0>, -9, true, true>", 72),
+    ("query_kernel<float, 8, 3, 1, 0, PrescreenExact<8, 1, 0>, -8, true, true>", 72),
+    ("query_kernel<float, 8, 3, 1, 0, PrescreenExact<8, 1, 0>, -9, true, true>", 72),
     # uint8 rows read directly
     ("query_kernel<unsigned char, 8, 1, 1, 0, NoPrescreen, 1, true, true>", 64),
     ("query_kernel<unsigned char, 8, 1, 1, 0, NoPrescreen, 2, true, true>", 64),
@@ -137,16 +148,35 @@ def test_labeled_kernels_keep_their_registers(kernels, name, vgprs, scratch):
     assert k["vgpr_count"] <= vgprs, k
 
 
+# The filtered and labelled headline and shard kernels on a lossless base (PrescreenExact: both
+# phases in one kernel).  The file's bound for filtered kernels, 80 registers; the build gives 78 /
+# 78 / 72 / 72 under a bitset and 79 / 79 / 72 / 72 under labels, private segment 0 in all eight.
+@pytest.mark.parametrize("name", [n.replace("Prescreen<", "PrescreenExact<") % kernel
+                                  for kernel in ("query_filtered_kernel", "query_labeled_kernel")
+                                  for n in FILTERED_KERNELS])
+def test_exact_filtered_and_labeled_kernels_have_no_scratch(kernels, name):
+    assert name in kernels, f"{name} is not in the library (renamed template parameters?)"
+    k = kernels[name]
+    assert k["private_segment_fixed_size"] == 0, k
+    assert k["vgpr_spill_count"] == 0, k
+    assert k["vgpr_count"] <= 80, k
+
+
 def test_every_early_rows_query_kernel_of_an_l2_base_is_scratch_free(kernels):
     """All `EARLY = true` squared-L2 query variants (whatever ring home / bucket count the launcher
     picks): no private segment.  (Cosine variants carry a second accumulator and may spill a few
-    registers: not a BASELINE shape, listed by scripts/kernel_resources.py.)"""
-    seen = 0
+    registers: not a BASELINE shape, listed by scripts/kernel_resources.py.)  Also every filtered
+    and labelled kernel that takes its distances from lossless codes, on all four layouts."""
+    seen = exact = 0
     for name, k in kernels.items():
         m = re.match(r"query_kernel<(float|unsigned char), \d+, \d+, 1, 0, .*, true, (true|false)>$",
                      name)
-        if not m or not name.endswith("true, true>"):
-            continue
-        seen += 1
-        assert k["private_segment_fixed_size"] == 0, (name, k)
+        if m and name.endswith("true, true>"):
+            seen += 1
+            assert k["private_segment_fixed_size"] == 0, (name, k)
+        elif re.match(r"query_(filtered|labeled)_kernel<float, \d+, \d+, 1, 0, PrescreenExact<8, 1, 0>, "
+                      r"[12], true>$", name):
+            exact += 1
+            assert k["private_segment_fixed_size"] == 0, (name, k)
     assert seen >= 8
+    assert exact >= 12
