@@ -47,6 +47,26 @@ uint32_t merge_sorted_size(uint32_t KBuild)
 #define GGNN_MERGE_WAVES_EARLY 6   // see GGNN_QUERY_WAVES_EARLY (query.hip)
 #endif
 
+// SortedList<.., SEL> of a merge kernel: the push with selects and the one-block replay
+// (traversal.hpp), except where that form costs the kernel registers it does not have -- seven of the
+// counting kernels (COUNT: launches with work counters, i.e. tests and profiling), which it takes
+// 4-8 bytes deeper into scratch memory; they keep the nested `if`
+template <typename BaseT, int LPR, int NCH, int R, int MODE, class PSC, int HB, bool EARLY, bool COUNT>
+constexpr bool merge_select_push()
+{
+  if (R != 1 || !COUNT)
+    return true;
+  // (one register at the step from 64 to 65)
+  if (std::is_same_v<BaseT, float> && PSC::enabled && LPR == 8 && NCH == 1 && MODE == kCos && HB == 0 &&
+      !EARLY)
+    return false;
+  if (std::is_same_v<BaseT, float> && PSC::enabled && HB == 1)
+    return !((LPR == 16 && NCH == 2 && MODE == kL2 && EARLY) || (LPR == 8 && NCH == 3 && !EARLY));
+  if (std::is_same_v<BaseT, uint8_t> && !PSC::enabled && HB == 0)
+    return !(NCH == 2 && (LPR == 8 || LPR == 16) && !EARLY);
+  return true;
+}
+
 // EARLY (R = 1, KBuild <= 24): the pop order of traversal.hpp "Early rows", as in the query kernel
 // COUNT = false (launches without work counters: every production build): the membership test
 // against the sorted part runs behind the verdicts, for the candidates that are still in the race
@@ -89,7 +109,7 @@ __global__ void __launch_bounds__(kWave)
             a.D);
   uint2 rows_read = make_uint2(0u, 0u);
 
-  SortedList<R, HB> sl;
+  SortedList<R, HB, false, merge_select_push<BaseT, LPR, NCH, R, MODE, PSC, HB, EARLY, COUNT>()> sl;
   sl.init(K + 1, a.sorted, kMergeCache, xi, lds.known, static_cast<int>(a.vis_slots));
   uint32_t cnt_dist = 0, cnt_pop = 0;
 

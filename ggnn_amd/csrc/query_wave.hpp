@@ -39,6 +39,42 @@ GGNN_DEV void request_filter_words(FILT& idf, const int cand)
     idf.request(cand);
 }
 
+// SortedList<.., SEL> of a query kernel: the push with selects and the one-block replay
+// (traversal.hpp), except where that form costs the kernel registers it does not have.  Eight
+// unfiltered kernels of two-chunk layouts keep the nested `if`: six early-rows kernels with the
+// visited ring in LDS (GR = false: hook QUERY_GLOBAL_RING = 0, or a search that can wrap its ring),
+// which would go 8-28 bytes into scratch memory, four of them from none, and the two cosine uint8
+// tag-set kernels without pre-screen, which spill already and would spill 4 bytes more.
+template <typename BaseT, int LPR, int NCH, int R, int MODE, class PSC, int HB, bool EARLY, bool GR,
+          class FILT>
+constexpr bool query_select_push()
+{
+  if (R != 1)
+    return true;
+  // (and where it costs one register at an occupancy step, 64 -> 65 or 80 -> 81: the ring-less
+  // early-rows kernels of rows read directly with two bucket registers, the bfloat16 8 x 3 kernel
+  // without a hashed set, and the bitset kernels of 16-bit 16 x 4 cosine rows)
+  if (!PSC::enabled && !FILT::enabled && LPR == 8 && NCH == 1 && HB == 2 && EARLY && GR)
+    return false;
+  if (std::is_same_v<BaseT, bf16_t> && !PSC::enabled && !FILT::enabled && LPR == 8 && NCH == 3 &&
+      MODE == kL2 && HB == 0 && !EARLY)
+    return false;
+  if (std::is_same_v<FILT, IdFilter> && sizeof(BaseT) == 2 && !PSC::enabled && LPR == 16 && NCH == 4 &&
+      MODE == kCos && HB == 0)
+    return false;
+  if (FILT::enabled || NCH != 2)
+    return true;
+  if (std::is_same_v<BaseT, float> && PSC::enabled && EARLY && !GR) {
+    if (LPR == 16)
+      return HB != 2;
+    if (LPR == 8)
+      return MODE == kL2 ? !(HB == 1 || HB == 2) : !(HB == 0 || HB == 1);
+  }
+  if (std::is_same_v<BaseT, uint8_t> && !PSC::enabled && !EARLY && !GR && LPR == 8 && MODE == kCos)
+    return !is_tag_set(HB);
+  return true;
+}
+
 // ---- host side: what the launchers of query.hip and query_filtered.hip share ----
 
 // layouts whose first row read is 8 lanes x one 16-byte chunk: Prescreen<8,1> next to any float

@@ -48,7 +48,7 @@
   static_assert(!kExactCodes || EARLY, "exact distances from codes: early-rows kernels only");
   load_prescreen(ps, a, query + static_cast<size_t>(n) * a.D);
 
-  SortedList<R, HB, GR> sl;
+  SortedList<R, HB, GR, query_select_push<BaseT, LPR, NCH, R, MODE, PSC, HB, EARLY, GR, FILT>()> sl;
   if constexpr (GR && !is_tag_set(HB))
     sl.init_global_ring(a.KQuery, a.sorted, a.cache, xi, lds.known, static_cast<int>(a.vis_slots),
                         a.ring + static_cast<size_t>(n) * (a.cache - a.sorted));
@@ -99,7 +99,10 @@
         // it went to scratch and its reload put a vmcnt(0) in front of this load)
         const uint64_t rp = reinterpret_cast<uint64_t>(
             a.graph0 + static_cast<size_t>(static_cast<uint32_t>(anchor)) * a.KBuild);
-        const int32_t* row = reinterpret_cast<const int32_t*>(
+        // (a pointer made from an integer is a generic one -- a flat load, which also counts as an
+        // LDS access and is waited for with lgkmcnt(0): the address space is stated)
+        using GlobalRow = const __attribute__((address_space(1))) int32_t*;
+        const GlobalRow row = reinterpret_cast<GlobalRow>(
             (static_cast<uint64_t>(static_cast<uint32_t>(uni(static_cast<int>(rp >> 32)))) << 32) |
             static_cast<uint32_t>(uni(static_cast<int>(rp))));
         cand = in_row ? row[lane] : kEmptyKey;

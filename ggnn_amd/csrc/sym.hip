@@ -127,17 +127,18 @@ struct SymEngine : DistEngine<BaseT, LPR, NCH> {
 };
 
 // fetch of the sym cache, simple_knn_sym_cache.cuh:405-436
-template <int MODE, int R, class SE>
-GGNN_DEV void sym_distances(SortedList<R>& sl, const SE& se, const WaveLds& lds, const int nsurv,
-                            const int32_t* translation, float criteria_half);
+template <int MODE, int R, class SE, bool SEL>
+GGNN_DEV void sym_distances(SortedList<R, 0, false, SEL>& sl, const SE& se, const WaveLds& lds,
+                            const int nsurv, const int32_t* translation, float criteria_half);
 
 // ps: exact pre-screen on the distance to the query point (traversal.hpp): a candidate whose lower
 // bound already reaches criteria_sym() = s_dists[0] + xi at the start of the fetch fails the
 // first half of the acceptance test (simple_knn_sym_cache.cuh:431) whatever its distance to the
 // half point is -- the criteria only tightens during a fetch -- so its float row is not read.
-template <int MODE, int R, class SE, class PS>
-GGNN_DEV void sym_fetch(SortedList<R>& sl, const SE& se, const WaveLds& lds, int cand,
-                        const int32_t* translation, float criteria_half, const PS& ps, uint4& work)
+template <int MODE, int R, class SE, class PS, bool SEL>
+GGNN_DEV void sym_fetch(SortedList<R, 0, false, SEL>& sl, const SE& se, const WaveLds& lds,
+                        int cand, const int32_t* translation, float criteria_half, const PS& ps,
+                        uint4& work)
 {
   const int lane = threadIdx.x;
   cand = lower_half_to_both(cand);
@@ -166,9 +167,9 @@ GGNN_DEV void sym_fetch(SortedList<R>& sl, const SE& se, const WaveLds& lds, int
   sym_distances<MODE, R>(sl, se, lds, nsurv_eval, translation, criteria_half);
 }
 
-template <int MODE, int R, class SE>
-GGNN_DEV void sym_distances(SortedList<R>& sl, const SE& se, const WaveLds& lds, const int nsurv,
-                            const int32_t* translation, float criteria_half)
+template <int MODE, int R, class SE, bool SEL>
+GGNN_DEV void sym_distances(SortedList<R, 0, false, SEL>& sl, const SE& se, const WaveLds& lds,
+                            const int nsurv, const int32_t* translation, float criteria_half)
 {
   constexpr int STEPS = StepsOf<SE::LPR, SE::NCH>::value;
   constexpr int ROWS = SE::ROWS;
@@ -225,6 +226,17 @@ GGNN_DEV void sym_distances(SortedList<R>& sl, const SE& se, const WaveLds& lds,
   }
 }
 
+// SortedList<.., SEL> of a sym kernel: the push with selects (traversal.hpp), except where that form
+// costs the kernel registers it does not have -- two cosine kernels of the widest layout, which
+// spill already and would spill 8-12 bytes more; they keep the nested `if`
+template <typename BaseT, int LPR, int NCH, int R, int MODE>
+constexpr bool sym_select_push()
+{
+  if (LPR == 64 && NCH == 16 && MODE == kCos)
+    return !((std::is_same_v<BaseT, uint8_t> && R == 1) || (std::is_same_v<BaseT, bf16_t> && R == 2));
+  return true;
+}
+
 template <typename BaseT, int LPR, int NCH, int R, int MODE, class PSC>
 // one-chunk layouts fit 7 waves per SIMD without spilling (79 -> 71 registers for uint8 rows)
 __global__ void __launch_bounds__(kWave)
@@ -258,7 +270,7 @@ __global__ void __launch_bounds__(kWave)
             reinterpret_cast<const float*>(base + static_cast<size_t>(static_cast<uint32_t>(m)) * a.D),
             a.D);
 
-  SortedList<R> sl;
+  SortedList<R, 0, false, sym_select_push<BaseT, LPR, NCH, R, MODE>()> sl;
   sl.init(KF, a.sorted, kSymCache, xi, lds.known);
   uint4 work = make_uint4(0u, 0u, 0u, 0u);
 

@@ -12,7 +12,10 @@
 // Distances are computed for all surviving candidates of a fetch at once (LPR lanes per base
 // row, 64/LPR rows per wave-wide 16-byte load instruction, i.e. fully coalesced 16 B/lane
 // gathers), then the accept/push sequence is replayed in candidate order, which is what the
-// reference does one candidate at a time (simple_knn_cache.cuh:268-286).
+// reference does one candidate at a time (simple_knn_cache.cuh:268-286).  The replay is the part of
+// a pop that no memory request hides, so it is written without exec-mask regions: a push is selects
+// (push_step), and for one-register lists the criteria and duplicate tests are part of its masks
+// (push_if, replay_push) -- one basic block per candidate.
 #pragma once
 #include <cstdlib>
 #include <type_traits>
@@ -271,7 +274,10 @@ inline size_t tag_set_lds_bytes(uint32_t sorted, uint32_t vis)
 // the compiler can no longer wait for "all but the newest n" loads -- loads and stores retire out
 // of order with respect to each other -- so every wait for the requested code rows became
 // vmcnt(0) and also waited for the speculative graph row issued after them.)
-template <int R, int HB = 0, bool GR = false>
+// SEL: push() written with selects, and for R == 1 the one-block replay (push_if).  false keeps the
+// nested `if` and the branches in front of it, for the kernels (named where they are defined) whose
+// register allocation the select form pushes into scratch memory.
+template <int R, int HB = 0, bool GR = false, bool SEL = true>
 struct SortedList {
   static_assert(!GR || HB != 0, "ring-less: only with a hashed set or a tag set");
   static constexpr int kHashRegs = HB;
@@ -587,7 +593,15 @@ struct SortedList {
     const bool first = (i == 0) || (i == BEST);
     const bool active = (dist[r] >= d) && (i < SORTED) && !(denied && i < BEST);
     const bool prev_active = !first && (pd >= d);
-    if (active) {
+    if constexpr (SEL) {
+      // two selects per value instead of a nested `if`: the nested form compiles to three nested
+      // exec-mask regions (ten basic blocks and 16 phi copies per pushed candidate)
+      const bool take_new = active && (first || !prev_active);
+      const bool take_prev = active && !take_new && i != qlane && pk != kEmptyKey;
+      key[r] = take_new ? k : take_prev ? pk : key[r];
+      dist[r] = take_new ? d : take_prev ? pd : dist[r];
+    }
+    else if (active) {
       if (first || !prev_active) {
         key[r] = k;
         dist[r] = d;
@@ -598,6 +612,49 @@ struct SortedList {
       }
     }
     return active;
+  }
+
+  // One-register lists: the replay of a fetch pushes through push_if(), one basic block per
+  // candidate (longer lists keep the wave-uniform tests as branches in front of push())
+  static constexpr bool kReplayOneBlock = (R == 1) && SEL;
+
+  // push(k, d, denied) if `go` (wave-uniform), for R == 1: no branch, no exec-mask region.  Every
+  // lane-dependent condition of push_step() is a ballot, and what a lane needs to know about its
+  // lower neighbour -- "is it active", "is it empty" -- is that ballot shifted by one, so the
+  // conditions combine in scalar registers, off the vector pipe:
+  //   ge        lanes whose distance is >= d                      (the reference's `active`, Q2)
+  //   active  = ge & [0, SORTED) & not [0, BEST) if denied, or nothing at all if the push is off
+  //             (!go, or k is in the list already: the early returns of push())
+  //   new     = active & (first | ~(ge << 1))                     the insertion points
+  //   prev    = active & ~new & ~qlane & (nonempty << 1)          lanes taking their lower neighbour
+  // and come back to the lanes as the masks of four selects.  A push that is off leaves the list
+  // untouched, as the early returns do.
+  GGNN_DEV void push_if(const int k, const float d, const bool go, const bool denied = false)
+  {
+    static_assert(R == 1 && SEL, "push_if: one list register per lane");
+    using u64 = unsigned long long;
+    const u64 ge = __ballot(dist[0] >= d);
+    const u64 dup = __ballot(key[0] == k);
+    const u64 nonempty = __ballot(key[0] != kEmptyKey);
+    const u64 below_best = (2ull << (BEST - 1)) - 1ull;  // [0, BEST), 1 <= BEST <= 64
+    const u64 in_sorted = ~0ull >> (kWave - SORTED);     // [0, SORTED), 1 <= SORTED <= 64
+    const u64 first = 1ull | (below_best + 1ull);        // lanes 0 and BEST
+    const u64 q1 = head_in ? 1ull << (BEST + (P - head_in)) : 0ull;  // Q1: nothing shifts into it
+    u64 active = ge & in_sorted;
+    if (denied)
+      active &= ~below_best;
+    if (!go || dup)
+      active = 0ull;
+    const u64 take_new = active & (first | ~(ge << 1));
+    const u64 take_prev = active & ~take_new & ~q1 & (nonempty << 1);
+    // (lane 0 never takes its neighbour: the shift may leave anything there, which saves the copy
+    // that keeps the boundary lane's own value)
+    const int pk = __builtin_amdgcn_update_dpp(0, key[0], 0x138, 0xf, 0xf, true);
+    const float pd = dpp_f<0x138>(dist[0]);
+    const bool tn = __builtin_amdgcn_inverse_ballot_w64(take_new);
+    const bool tp = __builtin_amdgcn_inverse_ballot_w64(take_prev);
+    key[0] = tn ? k : tp ? pk : key[0];
+    dist[0] = tn ? d : tp ? pd : dist[0];
   }
 
   // KBestList::add_unique, k_best_list.cuh:77-109 (stable insert after equal distances, no
@@ -931,6 +988,7 @@ struct SortedList {
 // chunk width).  Slow path: every push walks the sorted region through LDS.
 // ---------------------------------------------------------------------------------------------
 struct LdsList {
+  static constexpr bool kReplayOneBlock = false;  // (every push walks LDS: see replay_push())
   int* key;     // [CACHE] physical layout: best | priority-queue ring | visited ring
   float* dist;  // [SORTED]
   int BEST, SORTED, CACHE;
@@ -1522,7 +1580,7 @@ struct Prescreen {
   // sum (cq - c)^2 over this lane's chunks of one code row (exact)
   GGNN_DEV float partial(const uint4 (&v)[NCH]) const
   {
-    uint32_t ab = 0, bb = 0;
+    uint32_t ab = 0, bb = qq;  // (|cq|^2 is the accumulator's start: no add of its own)
 #pragma unroll
     for (int c = 0; c < NCH; ++c) {
       ab = __builtin_amdgcn_udot4(v[c].x, qc[c].x, ab, false);
@@ -1534,7 +1592,7 @@ struct Prescreen {
       bb = __builtin_amdgcn_udot4(v[c].z, v[c].z, bb, false);
       bb = __builtin_amdgcn_udot4(v[c].w, v[c].w, bb, false);
     }
-    return static_cast<float>((qq + bb) - 2u * ab);
+    return static_cast<float>(bb - 2u * ab);
   }
 
   // a candidate with group-summed S >= threshold(crit) has a float distance >= crit
@@ -1770,6 +1828,23 @@ struct LabelFilter {
   }
 };
 
+// One candidate of a replay (simple_knn_cache.cuh:283-285): pushed if it still beats the criteria,
+// which the pushes before it may have tightened.  One-register lists take the test, and the
+// duplicate test of push(), into the masks of push_if(): the loop around this is then ONE basic block
+// per candidate.  Longer lists (and the list in LDS) keep the wave-uniform branch in front of push().
+// (The criteria test as a scalar early-out in front of the one-block body, so that a candidate that
+// fails the tightened criteria skips the body, was built and measured against this form: a tie --
+// ten alternating headline runs each, 0.810-0.826 ms both, DESIGN.md 4.7 -- so the form without the
+// branch stays.)
+template <class SL>
+GGNN_DEV void replay_push(SL& sl, const int k, const float d, const bool denied = false)
+{
+  if constexpr (SL::kReplayOneBlock)
+    sl.push_if(k, d, d < sl.criteria(), denied);
+  else if (d < sl.criteria())
+    sl.push(k, d, denied);
+}
+
 // the replay of a fetch (simple_knn_cache.cuh:268-286) under a filter: as replay_lanes() below,
 // a denied candidate is pushed with the flag
 template <class SL, class IDF>
@@ -1782,7 +1857,9 @@ GGNN_DEV void replay_lanes_filtered(SL& sl, unsigned long long m, const int k_of
     m &= m - 1;
     const float d = rdlanef(d_of, j);
     const int k = rdlane(k_of, j);
-    if (d < sl.criteria())
+    if constexpr (SL::kReplayOneBlock)
+      replay_push(sl, k, d, filt.denied(dl, k));  // (no skip of the compare for dl == 0: a branch)
+    else if (d < sl.criteria())
       sl.push(k, d, dl != 0ull && filt.denied(dl, k));
   }
 }
@@ -1847,8 +1924,7 @@ GGNN_DEV int fetch(SL& sl, const DE& de, const WaveLds& lds, int cand,
     m &= m - 1;
     const float d = rdlanef(cd, j);
     const int k = rdlane(ck, j);
-    if (d < sl.criteria())
-      sl.push(k, d);
+    replay_push(sl, k, d);
   }
   GGNN_TICK(8);  // accept / push replay
   return nsurv;
@@ -1920,6 +1996,9 @@ struct EarlyRows {
         else
           v[s][0] = typename RD::Chunk{};
       }
+      // (keeps the two paths apart: the optimiser otherwise sinks the third load of both into one
+      // exec-mask region behind the branch, and the path above pays that region and its zero-fill)
+      asm volatile("");
     }
   }
   // the value of step (lane & 7) in lanes whose (lane & 7) < 3 (their candidate's lane).  The three
@@ -1949,8 +2028,7 @@ GGNN_DEV void replay_lanes(SL& sl, unsigned long long m, const int k_of, const f
     m &= m - 1;
     const float d = rdlanef(d_of, j);
     const int k = rdlane(k_of, j);
-    if (d < sl.criteria())
-      sl.push(k, d);
+    replay_push(sl, k, d);
   }
 }
 
