@@ -17,6 +17,7 @@ if os.environ.get("GGNN_TEST_HOOKS") == "1" and os.environ.get("GGNN_AMD_LIB"):
 OK, INVALID_ARGUMENT, INVALID_STATE, OUT_OF_RANGE, OUT_OF_MEMORY, DEVICE_ERROR, UNSUPPORTED, \
     IO_ERROR = range(8)
 F32, U8, F16, BF16 = 0, 1, 2, 3
+I8 = 5   # (4 is reserved and refused)
 CPU, GPU = 0, 1
 
 

@@ -5,7 +5,7 @@ nanobind module (src/ggnn/python/nanobind.cu:131-301), implemented over the C-AB
     g = ggnn.GGNN(); g.set_base(base); g.build(24, 0.5)
     indices, dists = g.query(query, 10, 0.64, 400)
 
-Inputs may be numpy arrays or torch tensors (CPU or CUDA), C-contiguous 2-D float32/uint8/
+Inputs may be numpy arrays or torch tensors (CPU or CUDA), C-contiguous 2-D float32/uint8/int8/
 float16/bfloat16 (bfloat16 through torch only: numpy has no such type);
 results are torch tensors like the reference's (nb::pytorch ndarrays), int32 ids and float32
 SQUARED L2 (or |1-cos|) distances.
@@ -32,7 +32,8 @@ def set_log_level(level: int) -> None:
     lib().ggnn_set_log_level(int(level))
 
 
-_NP_OF = {torch.float32: np.float32, torch.uint8: np.uint8, torch.int32: np.int32}
+_NP_OF = {torch.float32: np.float32, torch.uint8: np.uint8, torch.int8: np.int8,
+          torch.int32: np.int32}
 
 
 def _as_tensor(data, dtype=None, what="data"):
@@ -60,13 +61,14 @@ def _loc(t):
 
 
 _DTYPE_CODES = {torch.float32: _lib.F32, torch.uint8: _lib.U8, torch.float16: _lib.F16,
-                torch.bfloat16: _lib.BF16}
+                torch.bfloat16: _lib.BF16, torch.int8: _lib.I8}
 
 
 def _dtype_code(t):
     code = _DTYPE_CODES.get(t.dtype)
     if code is None:
-        raise TypeError("unsupported datatype (float32, uint8, float16 and bfloat16 are supported)")
+        raise TypeError("unsupported datatype (int8, float32, uint8, float16 and bfloat16 are "
+                        "supported)")
     return code
 
 
@@ -271,6 +273,13 @@ class FloatDataset(_Dataset):
 
 class UCharDataset(_Dataset):
     _torch_dtype = torch.uint8
+
+
+class CharDataset(_Dataset):
+    """Signed 8-bit rows (torch.int8).  This project's extension: the reference has no such
+    dataset.  `store` / `load` use the bvecs record layout of `UCharDataset` (per vector a uint32
+    dimension, then D bytes) with the bytes read as signed."""
+    _torch_dtype = torch.int8
 
 
 class IntDataset(_Dataset):

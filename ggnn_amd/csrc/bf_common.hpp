@@ -1,5 +1,5 @@
 // Shared between bf_mfma.hip (f32 / LDS-list kernels, host side) and bf_i8.hip (the register-set
-// uint8 kernel, compiled with the VGPR form of the MFMA instructions).
+// uint8 / int8 kernel, compiled with the VGPR form of the MFMA instructions).
 #pragma once
 #include "traversal.hpp"
 
@@ -83,8 +83,9 @@ constexpr uint32_t kBfI8RowStride = 144;
 // bf_i8.hip: launches bf_i8v2_kernel for KP in {4, 10, 16} (a seeding launch over the first
 // seed_rows rows of the base first, when m.seed is set and there are several slices); m.gthr must
 // point to bf_i8v2_exchange_ints(Nq, slices) words initialised to 0x7fffffff (or be null: no exchange)
-void launch_bf_i8v2(const BfMfmaArgs& m, uint32_t qblocks, uint32_t slices, uint32_t seed_rows,
-                    hipStream_t stream);
+// is_signed: int8 rows (the SIGNED kernels), else uint8
+void launch_bf_i8v2(const BfMfmaArgs& m, bool is_signed, uint32_t qblocks, uint32_t slices,
+                    uint32_t seed_rows, hipStream_t stream);
 size_t bf_i8v2_lds_bytes();
 size_t bf_i8v2_exchange_ints(uint32_t Nq, uint32_t slices);
 uint32_t bf_i8v2_default_rank_mask(uint32_t KP, uint32_t slices);

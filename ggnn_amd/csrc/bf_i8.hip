@@ -153,10 +153,13 @@ GGNN_DEV int i8v2_qrow(int r, int h)
 // B-operand set -- 222 registers, two waves per SIMD, 3.92 ms.  The 4- and 10-entry kernels fit two
 // waves anyway and are slower on the diet (k = 10: 3.24 vs 3.06 ms, also when forced to three
 // waves per SIMD, which costs 14 spilled registers): they keep the offsets in registers.
-template <int NM, int KPT, bool LEAN>
+// SIGNED: int8 rows -- the bytes are the signed operands already (no flip), a.bnorm / a.qnorm are
+// the norms of the rows themselves; everything else is shared
+template <int NM, int KPT, bool LEAN, bool SIGNED = false>
 __global__ void __launch_bounds__(256)
     __attribute__((amdgpu_waves_per_eu(2))) bf_i8v2_kernel(const BfMfmaArgs a)
 {
+  constexpr uint32_t kFlip = SIGNED ? 0u : 0x80808080u;
   extern __shared__ __attribute__((aligned(16))) float lds_f[];
   uint8_t* lds_b = reinterpret_cast<uint8_t*>(lds_f);
   constexpr uint32_t SR = kI8v2StageRows;
@@ -232,8 +235,8 @@ __global__ void __launch_bounds__(256)
       aq[s2][m] = i32x4{0, 0, 0, 0};
       if (qv && col < a.D) {
         const uint4 v = *reinterpret_cast<const uint4*>(qrow + col);
-        aq[s2][m] = i32x4{static_cast<int>(v.x ^ 0x80808080u), static_cast<int>(v.y ^ 0x80808080u),
-                          static_cast<int>(v.z ^ 0x80808080u), static_cast<int>(v.w ^ 0x80808080u)};
+        aq[s2][m] = i32x4{static_cast<int>(v.x ^ kFlip), static_cast<int>(v.y ^ kFlip),
+                          static_cast<int>(v.z ^ kFlip), static_cast<int>(v.w ^ kFlip)};
       }
     }
   }
@@ -378,8 +381,7 @@ __global__ void __launch_bounds__(256)
     for (int e = 0; e < PPT; ++e) {
       const uint32_t p = tid + 256 * e, srow = p >> 3, scol = 16 * (p & 7);
       *reinterpret_cast<uint4*>(t + srow * kBfI8RowStride + scol) =
-          make_uint4(v[e].x ^ 0x80808080u, v[e].y ^ 0x80808080u, v[e].z ^ 0x80808080u,
-                     v[e].w ^ 0x80808080u);
+          make_uint4(v[e].x ^ kFlip, v[e].y ^ kFlip, v[e].z ^ kFlip, v[e].w ^ kFlip);
     }
     if (tid < (int)SR)  // rows past the end never pass the accumulator test
       bns[buf * SR + tid] = (row0 + tid < end) ? bn : 0x3fffffff;
@@ -656,19 +658,21 @@ size_t bf_i8v2_exchange_ints(uint32_t Nq, uint32_t slices)
   return static_cast<size_t>(Nq) * kI8MaxRanks * 16 * ((slices + 15) / 16);
 }
 
-void launch_bf_i8v2(const BfMfmaArgs& m, uint32_t qblocks, uint32_t slices, uint32_t seed_rows,
-                    hipStream_t stream)
+void launch_bf_i8v2(const BfMfmaArgs& m, bool is_signed, uint32_t qblocks, uint32_t slices,
+                    uint32_t seed_rows, hipStream_t stream)
 {
   const size_t lds2 = bf_i8v2_lds_bytes();
   const uint32_t nm = (m.D + 31) / 32;
   const uint32_t KP = m.KP;
   GGNN_REQUIRE(KP == 4 || KP == 10 || KP == 16, GGNN_INVALID_ARGUMENT, "unsupported list length");
-#define GGNN_I8V2(NM_)                                                                        \
-  (KP == 4    ? reinterpret_cast<const void*>(&bf_i8v2_kernel<NM_, 4, false>)                 \
-   : KP == 10 ? reinterpret_cast<const void*>(&bf_i8v2_kernel<NM_, 10, false>)                \
-              : reinterpret_cast<const void*>(&bf_i8v2_kernel<NM_, 16, true>))
-  const void* kern =
-      nm == 1 ? GGNN_I8V2(1) : nm == 2 ? GGNN_I8V2(2) : nm == 3 ? GGNN_I8V2(3) : GGNN_I8V2(4);
+#define GGNN_I8V2(NM_, S_)                                                                    \
+  (KP == 4    ? reinterpret_cast<const void*>(&bf_i8v2_kernel<NM_, 4, false, S_>)             \
+   : KP == 10 ? reinterpret_cast<const void*>(&bf_i8v2_kernel<NM_, 10, false, S_>)            \
+              : reinterpret_cast<const void*>(&bf_i8v2_kernel<NM_, 16, true, S_>))
+#define GGNN_I8V2_NM(S_) \
+  (nm == 1 ? GGNN_I8V2(1, S_) : nm == 2 ? GGNN_I8V2(2, S_) : nm == 3 ? GGNN_I8V2(3, S_) : GGNN_I8V2(4, S_))
+  const void* kern = is_signed ? GGNN_I8V2_NM(true) : GGNN_I8V2_NM(false);
+#undef GGNN_I8V2_NM
 #undef GGNN_I8V2
   GGNN_HIP_CHECK(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize,
                                      static_cast<int>(lds2)));

@@ -273,15 +273,15 @@ struct TileStage<float> {
   }
 };
 
-// u8: CW/16 chunks of 16 bytes per row, 32 rows -> at most 256 chunks, one per thread
-// (unconditional clamped loads as above)
-template <>
-struct TileStage<uint8_t> {
+// uint8 / int8: CW/16 chunks of 16 bytes per row, 32 rows -> at most 256 chunks, one per thread
+// (unconditional clamped loads as above); int8 bytes are sign-extended where they are widened
+template <typename T8>
+struct TileStage8 {
   uint4 r;
   float bn;
   uint32_t rows;
   float bn_pad;
-  GGNN_DEV void load(const uint8_t* base, uint32_t D, uint32_t row0, uint32_t end, uint32_t col0,
+  GGNN_DEV void load(const T8* base, uint32_t D, uint32_t row0, uint32_t end, uint32_t col0,
                      uint32_t CW, const float* bnorm, float bn_pad_)
   {
     const uint32_t last = end - 1;
@@ -305,15 +305,19 @@ struct TileStage<uint8_t> {
 #pragma unroll
       for (int w = 0; w < 4; ++w) {
         float4 f;
-        f.x = ChunkOf<uint8_t>::get(r, 4 * w + 0);
-        f.y = ChunkOf<uint8_t>::get(r, 4 * w + 1);
-        f.z = ChunkOf<uint8_t>::get(r, 4 * w + 2);
-        f.w = ChunkOf<uint8_t>::get(r, 4 * w + 3);
+        f.x = ChunkOf<T8>::get(r, 4 * w + 0);
+        f.y = ChunkOf<T8>::get(r, 4 * w + 1);
+        f.z = ChunkOf<T8>::get(r, 4 * w + 2);
+        f.w = ChunkOf<T8>::get(r, 4 * w + 3);
         *reinterpret_cast<float4*>(dst + 4 * w) = f;
       }
     }
   }
 };
+template <>
+struct TileStage<uint8_t> : TileStage8<uint8_t> {};
+template <>
+struct TileStage<int8_t> : TileStage8<int8_t> {};
 
 // float16 / bfloat16: CW/8 chunks of 16 bytes per row, 32 rows -> at most 512 chunks, two per
 // thread (unconditional clamped loads as above); widened exactly to float32 in the tile, no shift
@@ -404,8 +408,9 @@ GGNN_DEV float4 load_query_piece(const uint8_t* qrow, bool qvalid, uint32_t D, u
   return make_float4(static_cast<float>(w & 0xffu), static_cast<float>((w >> 8) & 0xffu),
                      static_cast<float>((w >> 16) & 0xffu), static_cast<float>(w >> 24));
 }
-GGNN_DEV void load_query_chunk(float (&aq)[64], const uint8_t* qrow, bool qvalid, uint32_t D,
-                               uint32_t Dh, uint32_t col_h)
+template <typename T8>
+GGNN_DEV void load_query_chunk8(float (&aq)[64], const T8* qrow, bool qvalid, uint32_t D,
+                                uint32_t Dh, uint32_t col_h)
 {
 #pragma unroll
   for (int t = 0; t < 4; ++t) {
@@ -414,8 +419,19 @@ GGNN_DEV void load_query_chunk(float (&aq)[64], const uint8_t* qrow, bool qvalid
       v = *reinterpret_cast<const uint4*>(qrow + col_h + 16 * t);
 #pragma unroll
     for (int e = 0; e < 16; ++e)
-      aq[16 * t + e] = ChunkOf<uint8_t>::get(v, e);
+      aq[16 * t + e] = ChunkOf<T8>::get(v, e);
   }
+}
+GGNN_DEV void load_query_chunk(float (&aq)[64], const uint8_t* qrow, bool qvalid, uint32_t D,
+                               uint32_t Dh, uint32_t col_h)
+{
+  load_query_chunk8(aq, qrow, qvalid, D, Dh, col_h);
+}
+// int8 query chunk: the same with sign extension
+GGNN_DEV void load_query_chunk(float (&aq)[64], const int8_t* qrow, bool qvalid, uint32_t D,
+                               uint32_t Dh, uint32_t col_h)
+{
+  load_query_chunk8(aq, qrow, qvalid, D, Dh, col_h);
 }
 // float16 / bfloat16 query chunk: eight chunks of 8 elements, widened exactly
 template <typename T16>
@@ -609,6 +625,11 @@ __global__ void __launch_bounds__(256) pack_query_kernel(const BaseT* query, uin
         const uint32_t b = *reinterpret_cast<const uint32_t*>(query + q * D + col);
         v = make_float4(static_cast<float>(b & 0xffu), static_cast<float>((b >> 8) & 0xffu),
                         static_cast<float>((b >> 16) & 0xffu), static_cast<float>(b >> 24));
+      }
+      else if constexpr (std::is_same<BaseT, int8_t>::value) {
+        const uint4 c = make_uint4(*reinterpret_cast<const uint32_t*>(query + q * D + col), 0u, 0u, 0u);
+        v = make_float4(ChunkOf<BaseT>::get(c, 0), ChunkOf<BaseT>::get(c, 1),
+                        ChunkOf<BaseT>::get(c, 2), ChunkOf<BaseT>::get(c, 3));
       }
       else {
         const uint2 b = *reinterpret_cast<const uint2*>(query + q * D + col);
@@ -1157,9 +1178,11 @@ __global__ void __launch_bounds__(256)
 
 constexpr int kBfI8Tiles = 4;  // 32-row tiles per staged block (one barrier per 128 base rows)
 
-template <int NM>  // MFMAs per tile = ceil(D / 32), D <= 128
+// SIGNED: int8 rows are those operands as they come (no flip, norms of x itself)
+template <int NM, bool SIGNED = false>  // MFMAs per tile = ceil(D / 32), D <= 128
 __global__ void __launch_bounds__(256) bf_mfma_i8_kernel(const BfMfmaArgs a)
 {
+  constexpr uint32_t kFlip = SIGNED ? 0u : 0x80808080u;
   extern __shared__ __attribute__((aligned(16))) float lds_f[];
   uint8_t* lds_b = reinterpret_cast<uint8_t*>(lds_f);
   constexpr int TT = kBfI8Tiles;
@@ -1192,8 +1215,8 @@ __global__ void __launch_bounds__(256) bf_mfma_i8_kernel(const BfMfmaArgs a)
     aq[m] = i32x4{0, 0, 0, 0};
     if (qvalid && col < a.D) {
       const uint4 v = *reinterpret_cast<const uint4*>(qrow + col);
-      aq[m] = i32x4{static_cast<int>(v.x ^ 0x80808080u), static_cast<int>(v.y ^ 0x80808080u),
-                    static_cast<int>(v.z ^ 0x80808080u), static_cast<int>(v.w ^ 0x80808080u)};
+      aq[m] = i32x4{static_cast<int>(v.x ^ kFlip), static_cast<int>(v.y ^ kFlip),
+                    static_cast<int>(v.z ^ kFlip), static_cast<int>(v.w ^ kFlip)};
     }
   }
   float qn[16], thr[16];
@@ -1216,8 +1239,7 @@ __global__ void __launch_bounds__(256) bf_mfma_i8_kernel(const BfMfmaArgs a)
       if (row0 + srow < end && scol < a.D) {
         const uint4 v = *reinterpret_cast<const uint4*>(
             base + static_cast<size_t>(row0 + srow) * a.D + scol);
-        sv[e] = make_uint4(v.x ^ 0x80808080u, v.y ^ 0x80808080u, v.z ^ 0x80808080u,
-                           v.w ^ 0x80808080u);
+        sv[e] = make_uint4(v.x ^ kFlip, v.y ^ kFlip, v.z ^ kFlip, v.w ^ kFlip);
       }
     }
     sbn = inf_f();
@@ -1445,6 +1467,8 @@ const void* bf_mfma_labels_kernel(ggnn_dtype dtype, ggnn_measure measure, int T,
     case GGNN_U8:
       return l2 ? bf_filtered_kernel_of<uint8_t, kL2>(T, NU, KPC)
                 : bf_filtered_kernel_of<uint8_t, kCos>(T, NU, KPC);
+    case GGNN_I8:  // none: launch_bf_query keeps a filtered call on int8 rows on the scan
+      break;
   }
   throw Error(GGNN_INVALID_ARGUMENT, "unknown dtype");
 }
@@ -1457,10 +1481,11 @@ static int bf_filter_mode(const BfLaunch& a)
   return !a.filter_bits ? kBfNoFilter : a.filter_table.query_labels ? kBfLabels : kBfBits;
 }
 
-// uint8 + squared L2 with rows of up to 128 bytes: the integer kernels (no filtered form)
+// uint8 / int8 + squared L2 with rows of up to 128 bytes: the integer kernels (no filtered form)
 bool bf_mfma_uses_i8(const BfLaunch& a)
 {
-  return a.dtype == GGNN_U8 && a.measure == GGNN_EUCLIDEAN && a.D <= 128 && hook(kHookBfNoI8) == 0;
+  return (a.dtype == GGNN_U8 || a.dtype == GGNN_I8) && a.measure == GGNN_EUCLIDEAN && a.D <= 128 &&
+         hook(kHookBfNoI8) == 0;
 }
 
 bool bf_mfma_supported(const BfLaunch& a)
@@ -1643,6 +1668,10 @@ void launch_bf_query_mfma(const BfLaunch& a, hipStream_t stream)
       hipLaunchKernelGGL((pack_query_kernel<bf16_t>), grid, dim3(256), 0, stream,
                          static_cast<const bf16_t*>(tile_query), a.Nq, a.D, pack_chunks, n4,
                          reinterpret_cast<float4*>(q_packed));
+    else if (a.dtype == GGNN_I8)
+      hipLaunchKernelGGL((pack_query_kernel<int8_t>), grid, dim3(256), 0, stream,
+                         static_cast<const int8_t*>(tile_query), a.Nq, a.D, pack_chunks, n4,
+                         reinterpret_cast<float4*>(q_packed));
     else
       hipLaunchKernelGGL((pack_query_kernel<uint8_t>), grid, dim3(256), 0, stream,
                          static_cast<const uint8_t*>(tile_query), a.Nq, a.D, pack_chunks, n4,
@@ -1740,7 +1769,19 @@ void launch_bf_query_mfma(const BfLaunch& a, hipStream_t stream)
     const dim3 grid = equal_ranges ? dim3(nblocks) : dim3(qblocks, slices);                       \
     GGNN_HIP_CHECK(hipLaunchKernel(kern, grid, dim3(256), kargs, lds, stream));                   \
   } while (0)
-  if (use_i8) {
+  const bool i8_signed = a.dtype == GGNN_I8;
+  if (use_i8 && i8_signed) {
+    // int8: the norms of the rows themselves (integers <= 128 * 128^2 < 2^24: exact in float32)
+    hipLaunchKernelGGL((row_norms_kernel<int8_t>),
+                       dim3(norm_grid(a.N_base)), dim3(256), 0, stream,
+                       static_cast<const int8_t*>(a.base), a.N_base, a.D,
+                       static_cast<const float*>(nullptr), bnorm, static_cast<uint32_t*>(nullptr));
+    hipLaunchKernelGGL((row_norms_kernel<int8_t>),
+                       dim3(norm_grid(a.Nq)), dim3(256), 0, stream,
+                       static_cast<const int8_t*>(a.query), a.Nq, a.D,
+                       static_cast<const float*>(nullptr), qnorm, static_cast<uint32_t*>(nullptr));
+  }
+  else if (use_i8) {
     hipLaunchKernelGGL((row_norms_kernel<uint8_t, true>),
                        dim3(norm_grid(a.N_base)), dim3(256), 0, stream,
                        static_cast<const uint8_t*>(a.base), a.N_base, a.D,
@@ -1772,17 +1813,20 @@ void launch_bf_query_mfma(const BfLaunch& a, hipStream_t stream)
     m.seed = reinterpret_cast<int32_t*>(gthr) + pad4(bf_i8v2_exchange_ints(a.Nq, slices));
     const uint32_t seed_rows = static_cast<uint32_t>(
         std::clamp<int64_t>(hook(kHookBfI8Seed), 0, static_cast<int64_t>(a.N_base)));
-    launch_bf_i8v2(m, qblocks, slices, seed_rows, stream);
+    launch_bf_i8v2(m, i8_signed, qblocks, slices, seed_rows, stream);
   }
   else if (use_i8) {
     // (+ 128 words: bf_insert_hits reads up to 126 words past the last list unconditionally)
     const size_t lds8 = 2 * kBfI8Tiles * kBfTileRows * kBfI8RowStride +
                         2 * kBfQueriesPerBlock * KP * sizeof(float) + 128 * sizeof(float);
     const uint32_t nm = (a.D + 31) / 32;
-    const void* kern = nm == 1   ? reinterpret_cast<const void*>(&bf_mfma_i8_kernel<1>)
-                       : nm == 2 ? reinterpret_cast<const void*>(&bf_mfma_i8_kernel<2>)
-                       : nm == 3 ? reinterpret_cast<const void*>(&bf_mfma_i8_kernel<3>)
-                                 : reinterpret_cast<const void*>(&bf_mfma_i8_kernel<4>);
+#define GGNN_BF_I8(S_)                                                               \
+  (nm == 1   ? reinterpret_cast<const void*>(&bf_mfma_i8_kernel<1, S_>)                 \
+   : nm == 2 ? reinterpret_cast<const void*>(&bf_mfma_i8_kernel<2, S_>)                 \
+   : nm == 3 ? reinterpret_cast<const void*>(&bf_mfma_i8_kernel<3, S_>)                 \
+             : reinterpret_cast<const void*>(&bf_mfma_i8_kernel<4, S_>))
+    const void* kern = i8_signed ? GGNN_BF_I8(true) : GGNN_BF_I8(false);
+#undef GGNN_BF_I8
     if (lds8 > 64 * 1024)
       GGNN_HIP_CHECK(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize,
                                          static_cast<int>(lds8)));
@@ -1806,6 +1850,12 @@ void launch_bf_query_mfma(const BfLaunch& a, hipStream_t stream)
       GGNN_BF_MFMA(bf16_t, kL2);
     else
       GGNN_BF_MFMA(bf16_t, kCos);
+  }
+  else if (a.dtype == GGNN_I8) {
+    if (a.measure == GGNN_EUCLIDEAN)
+      GGNN_BF_MFMA(int8_t, kL2);
+    else
+      GGNN_BF_MFMA(int8_t, kCos);
   }
   else {
     if (a.measure == GGNN_EUCLIDEAN)

@@ -535,14 +535,17 @@ void launch_bf_query(const BfLaunch& a_in, hipStream_t stream)
 
   // large batches: Q x B^T on the matrix cores (bf_mfma.hip); hook BF_SCAN = 1 forces the scan,
   // for filtered calls too (the A/B switch).  A filtered call keeps the scan
-  //   - at the shapes of the integer kernels (uint8, squared L2, D <= 128): they have no filtered form
+  //   - at the shapes of the integer kernels (uint8 / int8, squared L2, D <= 128): they have no
+  //     filtered form
+  //   - on int8 rows at every shape: the filtered tile kernels are not instantiated for the type
   //   - under a bitset (per call or table) whose bit offset is not a multiple of 32: a tile's 32
   //     verdicts of a query are then not one word of its bitset (the engine's offsets are 0)
   //   (labels: N_base <= kMaxLabeledShardRows holds on both paths, required above)
   bool force_scan = hook(kHookBfScan) == 1;
   if (a.filter_bits) {
     const bool bits = !a.filter_table.query_labels;
-    force_scan = force_scan || bf_mfma_uses_i8(a) || (bits && a.filter_bit_offset % 32 != 0) ||
+    force_scan = force_scan || bf_mfma_uses_i8(a) || a.dtype == GGNN_I8 ||
+                 (bits && a.filter_bit_offset % 32 != 0) ||
                  static_cast<uint64_t>(a.filter_bit_offset) + a.N_base > 0xffffffffull;
   }
   if (!force_scan && bf_mfma_supported(a)) {

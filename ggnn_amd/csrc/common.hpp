@@ -41,7 +41,8 @@ inline size_t dtype_size(ggnn_dtype t)
 {
   switch (t) {
     case GGNN_F32: return 4;
-    case GGNN_U8: return 1;
+    case GGNN_U8:
+    case GGNN_I8: return 1;
     case GGNN_F16:
     case GGNN_BF16: return 2;
   }

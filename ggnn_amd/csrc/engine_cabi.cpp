@@ -290,7 +290,8 @@ ggnn_status ggnn_set_base(ggnn_t* h, const void* data, uint64_t N, uint32_t D, g
     // ggnn.cu:146-152
     GGNN_REQUIRE(!h->prepared, GGNN_INVALID_STATE,
                  "The base cannot be changed once the GPU instances are setup.");
-    GGNN_REQUIRE(dtype == GGNN_F32 || dtype == GGNN_U8 || dtype == GGNN_F16 || dtype == GGNN_BF16,
+    GGNN_REQUIRE(dtype == GGNN_F32 || dtype == GGNN_U8 || dtype == GGNN_F16 || dtype == GGNN_BF16 ||
+                     dtype == GGNN_I8,
                  GGNN_INVALID_ARGUMENT, "unsupported datatype for base");
     // ggnn.cu:466-487: the element type is fixed by the first set_base
     GGNN_REQUIRE(!h->base_set || h->base_dtype == dtype, GGNN_INVALID_ARGUMENT,
@@ -692,7 +693,8 @@ ggnn_status ggnn_op_dist_layout(uint32_t D, ggnn_dtype dtype, uint32_t* lanes_pe
                                 uint32_t* chunks_per_lane)
 {
   return guarded(nullptr, [&] {
-    GGNN_REQUIRE(dtype == GGNN_F32 || dtype == GGNN_U8 || dtype == GGNN_F16 || dtype == GGNN_BF16,
+    GGNN_REQUIRE(dtype == GGNN_F32 || dtype == GGNN_U8 || dtype == GGNN_F16 || dtype == GGNN_BF16 ||
+                     dtype == GGNN_I8,
                  GGNN_INVALID_ARGUMENT, "unknown dtype");
     GGNN_REQUIRE(lanes_per_row && chunks_per_lane, GGNN_INVALID_ARGUMENT, "null output pointer");
     const DistConfig dc = pick_dist_config(D, dtype);

@@ -35,7 +35,7 @@ struct MergeArgs {
 constexpr uint32_t kMergeCache = 256;      // merge_layer.cuh:44
 constexpr uint32_t kMergeIterations = 200; // merge_layer.cuh:43
 
-#ifndef GGNN_ROWS_16_TU
+#ifndef GGNN_ROWS_EXTRA_TU
 uint32_t merge_sorted_size(uint32_t KBuild)
 {
   // merge_layer.cuh:68-69 (CACHE_SIZE = 256 < 512)
@@ -62,7 +62,7 @@ constexpr bool merge_select_push()
     return false;
   if (std::is_same_v<BaseT, float> && PSC::enabled && HB == 1)
     return !((LPR == 16 && NCH == 2 && MODE == kL2 && EARLY) || (LPR == 8 && NCH == 3 && !EARLY));
-  if (std::is_same_v<BaseT, uint8_t> && !PSC::enabled && HB == 0)
+  if (is_byte_row<BaseT> && !PSC::enabled && HB == 0)
     return !(NCH == 2 && (LPR == 8 || LPR == 16) && !EARLY);
   return true;
 }
@@ -307,9 +307,12 @@ static void launch_merge_cfg(const MergeArgs& args, bool use_ps, ggnn_measure me
     launch_merge_r<BaseT, LPR, NCH, kCos, NoPrescreen>(args, stream);
 }
 
-#ifndef GGNN_ROWS_16_TU
+#ifndef GGNN_ROWS_EXTRA_TU
 // float16 / bfloat16 rows (no pre-screen): merge_16.hip
 void launch_merge_16(const MergeArgs& args, ggnn_measure measure, ggnn_dtype dtype,
+                     hipStream_t stream);
+// int8 rows (no pre-screen): merge_i8.hip
+void launch_merge_i8(const MergeArgs& args, ggnn_measure measure, ggnn_dtype dtype,
                      hipStream_t stream);
 
 void launch_merge(const MergeLaunch& a, hipStream_t stream)
@@ -360,6 +363,9 @@ void launch_merge(const MergeLaunch& a, hipStream_t stream)
   if (dtype_is_16bit(a.dtype)) {
     launch_merge_16(args, a.measure, a.dtype, stream);
   }
+  else if (a.dtype == GGNN_I8) {
+    launch_merge_i8(args, a.measure, a.dtype, stream);
+  }
   else {
 #define GGNN_LAUNCH_MERGE(T, LPR, NCH) launch_merge_cfg<T, LPR, NCH>(args, use_ps, a.measure, stream)
     GGNN_DISPATCH_DIST_32_8(a.dtype, c.D, GGNN_LAUNCH_MERGE);
@@ -368,7 +374,7 @@ void launch_merge(const MergeLaunch& a, hipStream_t stream)
   GGNN_HIP_CHECK(hipGetLastError());
 }
 
-#else  // GGNN_ROWS_16_TU
+#elif defined(GGNN_ROWS_16_TU)
 
 void launch_merge_16(const MergeArgs& args, ggnn_measure measure, ggnn_dtype dtype,
                      hipStream_t stream)
@@ -378,6 +384,16 @@ void launch_merge_16(const MergeArgs& args, ggnn_measure measure, ggnn_dtype dty
 #undef GGNN_LAUNCH_MERGE
 }
 
-#endif  // GGNN_ROWS_16_TU
+#else  // GGNN_ROWS_I8_TU
+
+void launch_merge_i8(const MergeArgs& args, ggnn_measure measure, ggnn_dtype dtype,
+                     hipStream_t stream)
+{
+#define GGNN_LAUNCH_MERGE(T, LPR, NCH) launch_merge_cfg<T, LPR, NCH>(args, false, measure, stream)
+  GGNN_DISPATCH_DIST_I8(dtype, args.D, GGNN_LAUNCH_MERGE);
+#undef GGNN_LAUNCH_MERGE
+}
+
+#endif  // GGNN_ROWS_EXTRA_TU
 
 }  // namespace ggnn_amd

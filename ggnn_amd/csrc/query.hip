@@ -39,7 +39,7 @@ __global__ void __launch_bounds__(kWave) query_kernel_lds(const QueryArgs a)
 #include "query_wave_lds_body.inc"
 }
 
-#ifndef GGNN_ROWS_16_TU
+#ifndef GGNN_ROWS_EXTRA_TU
 void query_sizing(uint32_t D, uint32_t k_query, uint32_t max_iterations, uint32_t* cache_size,
                   uint32_t* sorted_size)
 {
@@ -153,9 +153,12 @@ struct QueryLadder {
   }
 };
 
-#ifndef GGNN_ROWS_16_TU
+#ifndef GGNN_ROWS_EXTRA_TU
 // float16 / bfloat16 rows (no pre-screen): query_16.hip
 void launch_query_16(const QueryArgs& args, ggnn_measure measure, ggnn_dtype dtype,
+                     hipStream_t stream);
+// int8 rows (no pre-screen): query_i8.hip
+void launch_query_i8(const QueryArgs& args, ggnn_measure measure, ggnn_dtype dtype,
                      hipStream_t stream);
 
 void launch_query(const QueryLaunch& a, hipStream_t stream)
@@ -248,6 +251,9 @@ void launch_query(const QueryLaunch& a, hipStream_t stream)
   else if (dtype_is_16bit(a.dtype)) {
     launch_query_16(args, a.measure, a.dtype, stream);
   }
+  else if (a.dtype == GGNN_I8) {
+    launch_query_i8(args, a.measure, a.dtype, stream);
+  }
   else {
 #define GGNN_LAUNCH_QUERY(T, LPR, NCH) \
   launch_query_cfg<QueryLadder, T, LPR, NCH>(args, use_ps, a.measure, stream)
@@ -271,7 +277,7 @@ extern "C" int ggnn_debug_phase_cycles(unsigned long long* out16, int reset)
 }
 #endif
 
-#else  // GGNN_ROWS_16_TU
+#elif defined(GGNN_ROWS_16_TU)
 
 void launch_query_16(const QueryArgs& args, ggnn_measure measure, ggnn_dtype dtype,
                      hipStream_t stream)
@@ -282,6 +288,17 @@ void launch_query_16(const QueryArgs& args, ggnn_measure measure, ggnn_dtype dty
 #undef GGNN_LAUNCH_QUERY
 }
 
-#endif  // GGNN_ROWS_16_TU
+#else  // GGNN_ROWS_I8_TU
+
+void launch_query_i8(const QueryArgs& args, ggnn_measure measure, ggnn_dtype dtype,
+                     hipStream_t stream)
+{
+#define GGNN_LAUNCH_QUERY(T, LPR, NCH) \
+  launch_query_cfg<QueryLadder, T, LPR, NCH>(args, false, measure, stream)
+  GGNN_DISPATCH_DIST_I8(dtype, args.D, GGNN_LAUNCH_QUERY);
+#undef GGNN_LAUNCH_QUERY
+}
+
+#endif  // GGNN_ROWS_EXTRA_TU
 
 }  // namespace ggnn_amd

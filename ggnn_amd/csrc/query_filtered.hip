@@ -151,6 +151,18 @@ void launch_query_filtered_16(const FilteredQueryArgs& args, ggnn_measure measur
 }
 template void launch_query_filtered_16<TuFilter>(const FilteredQueryArgs&, ggnn_measure, ggnn_dtype,
                                                  hipStream_t);
+#elif defined(GGNN_ROWS_I8_TU)
+template <class FILT>
+void launch_query_filtered_i8(const FilteredQueryArgs& args, ggnn_measure measure, ggnn_dtype dtype,
+                              hipStream_t stream)
+{
+#define GGNN_LAUNCH_QF(T, LPR, NCH) \
+  launch_query_cfg<FilteredLadder<FILT>, T, LPR, NCH>(args, false, measure, stream)
+  GGNN_DISPATCH_DIST_I8(dtype, args.D, GGNN_LAUNCH_QF);
+#undef GGNN_LAUNCH_QF
+}
+template void launch_query_filtered_i8<TuFilter>(const FilteredQueryArgs&, ggnn_measure, ggnn_dtype,
+                                                 hipStream_t);
 #else
 #ifndef GGNN_LABELS_TU
 // the all-ones / all-zero rows of a launch with filter ids that brings none (operator seam; the
@@ -191,6 +203,10 @@ void launch_query_filtered(const QueryArgs& base, const FilterTable& table, bool
     args.filter_table.consts = static_cast<const uint32_t*>(consts.p);
   if (dtype_is_16bit(dtype)) {
     launch_query_filtered_16<FILT>(args, measure, dtype, stream);
+    return;
+  }
+  if (dtype == GGNN_I8) {
+    launch_query_filtered_i8<FILT>(args, measure, dtype, stream);
     return;
   }
 #define GGNN_LAUNCH_QF(T, LPR, NCH) \

@@ -70,7 +70,7 @@ constexpr bool query_select_push()
     if (LPR == 8)
       return MODE == kL2 ? !(HB == 1 || HB == 2) : !(HB == 0 || HB == 1);
   }
-  if (std::is_same_v<BaseT, uint8_t> && !PSC::enabled && !EARLY && !GR && LPR == 8 && MODE == kCos)
+  if (is_byte_row<BaseT> && !PSC::enabled && !EARLY && !GR && LPR == 8 && MODE == kCos)
     return !is_tag_set(HB);
   return true;
 }
@@ -165,6 +165,10 @@ void launch_query_filtered(const QueryArgs& base, const FilterTable& table, bool
                            ggnn_measure measure, ggnn_dtype dtype, hipStream_t stream);
 template <class FILT>
 void launch_query_filtered_16(const FilteredQueryArgs& args, ggnn_measure measure, ggnn_dtype dtype,
+                              hipStream_t stream);
+// (and query_filtered_i8 / query_labeled_i8 for int8 rows)
+template <class FILT>
+void launch_query_filtered_i8(const FilteredQueryArgs& args, ggnn_measure measure, ggnn_dtype dtype,
                               hipStream_t stream);
 
 }  // namespace ggnn_amd

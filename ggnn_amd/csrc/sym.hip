@@ -31,7 +31,7 @@ struct SymArgs {
 constexpr uint32_t kSymCache = 128;          // sym_query_layer.cuh:43
 constexpr uint32_t kSymPathIterations = 20;  // sym_query_layer.cuh:42
 
-#ifndef GGNN_ROWS_16_TU
+#ifndef GGNN_ROWS_EXTRA_TU
 uint32_t sym_sorted_size(uint32_t KBuild)
 {
   // sym_query_layer.cuh:63-64
@@ -232,6 +232,7 @@ GGNN_DEV void sym_distances(SortedList<R, 0, false, SEL>& sl, const SE& se, cons
 template <typename BaseT, int LPR, int NCH, int R, int MODE>
 constexpr bool sym_select_push()
 {
+  // (int8 rows never reach this layout: no kernel of it exists for them)
   if (LPR == 64 && NCH == 16 && MODE == kCos)
     return !((std::is_same_v<BaseT, uint8_t> && R == 1) || (std::is_same_v<BaseT, bf16_t> && R == 2));
   return true;
@@ -387,7 +388,7 @@ static void launch_sym_cfg(const SymArgs& args, bool use_ps, ggnn_measure measur
     launch_sym_r<BaseT, LPR, NCH, kCos, NoPrescreen>(args, stream);
 }
 
-#ifndef GGNN_ROWS_16_TU
+#ifndef GGNN_ROWS_EXTRA_TU
 // deterministic mode, second step: the requests of launch_sym in ascending order (point, then its
 // local neighbour), each at the first of its candidates whose slot counter is below KF -- the
 // schedule of one point per launch, without the in-pass reads.  A request whose point already
@@ -446,6 +447,8 @@ void launch_sym_assign(uint32_t KBuild, uint32_t N_layer, const int32_t* request
 
 // float16 / bfloat16 rows (no pre-screen): sym_16.hip
 void launch_sym_16(const SymArgs& args, ggnn_measure measure, ggnn_dtype dtype, hipStream_t stream);
+// int8 rows (no pre-screen): sym_i8.hip
+void launch_sym_i8(const SymArgs& args, ggnn_measure measure, ggnn_dtype dtype, hipStream_t stream);
 
 void launch_sym(const SymLaunch& a, hipStream_t stream)
 {
@@ -482,6 +485,9 @@ void launch_sym(const SymLaunch& a, hipStream_t stream)
   if (dtype_is_16bit(a.dtype)) {
     launch_sym_16(args, a.measure, a.dtype, stream);
   }
+  else if (a.dtype == GGNN_I8) {
+    launch_sym_i8(args, a.measure, a.dtype, stream);
+  }
   else {
 #define GGNN_LAUNCH_SYM(T, LPR, NCH) launch_sym_cfg<T, LPR, NCH>(args, use_ps, a.measure, stream)
     GGNN_DISPATCH_DIST_32_8(a.dtype, a.D, GGNN_LAUNCH_SYM);
@@ -490,7 +496,7 @@ void launch_sym(const SymLaunch& a, hipStream_t stream)
   GGNN_HIP_CHECK(hipGetLastError());
 }
 
-#else  // GGNN_ROWS_16_TU
+#elif defined(GGNN_ROWS_16_TU)
 
 void launch_sym_16(const SymArgs& args, ggnn_measure measure, ggnn_dtype dtype, hipStream_t stream)
 {
@@ -499,6 +505,15 @@ void launch_sym_16(const SymArgs& args, ggnn_measure measure, ggnn_dtype dtype, 
 #undef GGNN_LAUNCH_SYM
 }
 
-#endif  // GGNN_ROWS_16_TU
+#else  // GGNN_ROWS_I8_TU
+
+void launch_sym_i8(const SymArgs& args, ggnn_measure measure, ggnn_dtype dtype, hipStream_t stream)
+{
+#define GGNN_LAUNCH_SYM(T, LPR, NCH) launch_sym_cfg<T, LPR, NCH>(args, false, measure, stream)
+  GGNN_DISPATCH_DIST_I8(dtype, args.D, GGNN_LAUNCH_SYM);
+#undef GGNN_LAUNCH_SYM
+}
+
+#endif  // GGNN_ROWS_EXTRA_TU
 
 }  // namespace ggnn_amd

@@ -1153,6 +1153,39 @@ struct ChunkOf<uint8_t> {
   }
 };
 
+// signed bytes (GGNN_I8): the chunk of uint8 rows, get() sign-extends (one v_cvt_f32_i32 with an
+// SDWA sext(byte) operand)
+template <>
+struct ChunkOf<int8_t> {
+  using type = uint4;
+  static constexpr int EPC = 16;
+  static GGNN_DEV float get(const uint4& v, int e)
+  {
+    const uint32_t w = (e >> 2) == 0 ? v.x : (e >> 2) == 1 ? v.y : (e >> 2) == 2 ? v.z : v.w;
+    return static_cast<float>(static_cast<int32_t>(w << (24 - 8 * (e & 3))) >> 24);
+  }
+  static GGNN_DEV uint4 zero()
+  {
+    return make_uint4(0u, 0u, 0u, 0u);
+  }
+};
+// 8-bit rows, unsigned or signed: packed integer arithmetic in DistEngine, no pre-screen copy, and
+// the register carve-outs of the kernels that read 16 elements per chunk
+template <typename BaseT>
+inline constexpr bool is_byte_row = std::is_same<BaseT, uint8_t>::value || std::is_same<BaseT, int8_t>::value;
+// sum of the four byte products of two words on top of acc: v_dot4_u32_u8 for uint8 rows,
+// v_dot4c_i32_i8 for int8 rows (the sum modulo 2^32 as uint32_t: a sum of squares is its own value,
+// a signed dot product its two's complement)
+template <typename BaseT>
+GGNN_DEV uint32_t byte_dot4(uint32_t a, uint32_t b, uint32_t acc)
+{
+  if constexpr (std::is_same<BaseT, int8_t>::value)
+    return static_cast<uint32_t>(__builtin_amdgcn_sdot4(static_cast<int>(a), static_cast<int>(b),
+                                                        static_cast<int>(acc), false));
+  else
+    return __builtin_amdgcn_udot4(a, b, acc, false);
+}
+
 // 16-bit rows (GGNN_F16 / GGNN_BF16): element types of their own, 2 bytes of storage each; a
 // chunk is 8 elements in one uint4.  get() widens one element to float32 exactly where it is
 // used (no chunk is widened up front: 8 floats per chunk would double the registers of the rows
@@ -1218,7 +1251,7 @@ struct DistEngine {
   Chunk q[QL ? 1 : NCH];
   Chunk* q_lds;    // QL only
   float q_norm;    // cosine: |q|^2
-  uint32_t qq_u8;  // uint8 rows: sum of squares of this lane's query elements
+  uint32_t qq_u8;  // 8-bit rows: sum of squares of this lane's query elements
 
   GGNN_DEV Chunk qchunk(int c) const
   {
@@ -1267,11 +1300,11 @@ struct DistEngine {
           nrm = fmaf(v, v, nrm);
         }
       }
-      if constexpr (std::is_same<BaseT, uint8_t>::value) {
-        qq_u8 = __builtin_amdgcn_udot4(qc.x, qc.x, qq_u8, false);
-        qq_u8 = __builtin_amdgcn_udot4(qc.y, qc.y, qq_u8, false);
-        qq_u8 = __builtin_amdgcn_udot4(qc.z, qc.z, qq_u8, false);
-        qq_u8 = __builtin_amdgcn_udot4(qc.w, qc.w, qq_u8, false);
+      if constexpr (is_byte_row<BaseT>) {
+        qq_u8 = byte_dot4<BaseT>(qc.x, qc.x, qq_u8);
+        qq_u8 = byte_dot4<BaseT>(qc.y, qc.y, qq_u8);
+        qq_u8 = byte_dot4<BaseT>(qc.z, qc.z, qq_u8);
+        qq_u8 = byte_dot4<BaseT>(qc.w, qc.w, qq_u8);
       }
     }
     q_norm = 0.f;
@@ -1285,28 +1318,33 @@ struct DistEngine {
   template <int MODE>
   GGNN_DEV void partial(const Chunk (&v)[NCH], float& a, float& b) const
   {
-    if constexpr (std::is_same<BaseT, uint8_t>::value) {
-      // packed integer arithmetic (v_dot4_u32_u8), exact: sum (o-q)^2 = sum o^2 + sum q^2 - 2 sum oq.
-      // Equals the reference's float accumulation whenever that is exact (D <= 258).
+    if constexpr (is_byte_row<BaseT>) {
+      // packed integer arithmetic (v_dot4_u32_u8 / v_dot4c_i32_i8), exact: sum (o-q)^2 = sum o^2 +
+      // sum q^2 - 2 sum oq.  Equals the reference's float accumulation whenever that is exact
+      // (D <= 258).  int8 rows: ab is the signed dot product modulo 2^32, so the squared L2 sum below
+      // is the same uint32_t as for the rows x ^ 0x80 read as uint8
       uint32_t ab = 0, bb = 0;
 #pragma unroll
       for (int c = 0; c < NCH; ++c) {
         const Chunk qc = qchunk(c);
-        ab = __builtin_amdgcn_udot4(v[c].x, qc.x, ab, false);
-        ab = __builtin_amdgcn_udot4(v[c].y, qc.y, ab, false);
-        ab = __builtin_amdgcn_udot4(v[c].z, qc.z, ab, false);
-        ab = __builtin_amdgcn_udot4(v[c].w, qc.w, ab, false);
-        bb = __builtin_amdgcn_udot4(v[c].x, v[c].x, bb, false);
-        bb = __builtin_amdgcn_udot4(v[c].y, v[c].y, bb, false);
-        bb = __builtin_amdgcn_udot4(v[c].z, v[c].z, bb, false);
-        bb = __builtin_amdgcn_udot4(v[c].w, v[c].w, bb, false);
+        ab = byte_dot4<BaseT>(v[c].x, qc.x, ab);
+        ab = byte_dot4<BaseT>(v[c].y, qc.y, ab);
+        ab = byte_dot4<BaseT>(v[c].z, qc.z, ab);
+        ab = byte_dot4<BaseT>(v[c].w, qc.w, ab);
+        bb = byte_dot4<BaseT>(v[c].x, v[c].x, bb);
+        bb = byte_dot4<BaseT>(v[c].y, v[c].y, bb);
+        bb = byte_dot4<BaseT>(v[c].z, v[c].z, bb);
+        bb = byte_dot4<BaseT>(v[c].w, v[c].w, bb);
       }
       if (MODE == kL2) {
         a = static_cast<float>((qq_u8 + bb) - 2u * ab);
         b = 0.f;
       }
       else {
-        a = static_cast<float>(ab);
+        if constexpr (std::is_same<BaseT, int8_t>::value)
+          a = static_cast<float>(static_cast<int32_t>(ab));
+        else
+          a = static_cast<float>(ab);
         b = static_cast<float>(bb);
       }
       return;
@@ -2220,6 +2258,20 @@ inline DistConfig pick_dist_config(uint32_t D, ggnn_dtype dtype)
     else { F(T, 64, 16); }                                                        \
   } while (0)
 
+// int8 rows: the six layouts that rows of at most 4096 bytes reach ({64, 16} starts at 4097 bytes,
+// so no kernel of it is instantiated for the type)
+#define GGNN_DISPATCH_LAYOUT_I8(_dc, F)                                            \
+  do {                                                                            \
+    if ((_dc).lpr == 8 && (_dc).nch == 1) { F(int8_t, 8, 1); }                    \
+    else if ((_dc).lpr == 8 && (_dc).nch == 2) { F(int8_t, 8, 2); }               \
+    else if ((_dc).lpr == 8 && (_dc).nch == 3) { F(int8_t, 8, 3); }               \
+    else if ((_dc).lpr == 16 && (_dc).nch == 2) { F(int8_t, 16, 2); }             \
+    else if ((_dc).lpr == 16 && (_dc).nch == 4) { F(int8_t, 16, 4); }             \
+    else if ((_dc).lpr == 64 && (_dc).nch == 4) { F(int8_t, 64, 4); }             \
+    else                                                                          \
+      throw ::ggnn_amd::Error(GGNN_INVALID_ARGUMENT, "D must be in [1, 4096]");   \
+  } while (0)
+
 // dispatch a functor templated on <BaseT, LPR, NCH>
 #define GGNN_DISPATCH_DIST(dtype, D, F)                                           \
   do {                                                                            \
@@ -2230,6 +2282,8 @@ inline DistConfig pick_dist_config(uint32_t D, ggnn_dtype dtype)
       GGNN_DISPATCH_LAYOUT(::ggnn_amd::f16_t, _dc, F);                            \
     else if ((dtype) == GGNN_BF16)                                                \
       GGNN_DISPATCH_LAYOUT(::ggnn_amd::bf16_t, _dc, F);                           \
+    else if ((dtype) == GGNN_I8)                                                  \
+      GGNN_DISPATCH_LAYOUT_I8(_dc, F);                                            \
     else                                                                          \
       GGNN_DISPATCH_LAYOUT(uint8_t, _dc, F);                                      \
   } while (0)
@@ -2252,6 +2306,17 @@ inline DistConfig pick_dist_config(uint32_t D, ggnn_dtype dtype)
     else                                                                          \
       GGNN_DISPATCH_LAYOUT(::ggnn_amd::bf16_t, _dc, F);                           \
   } while (0)
+// int8 rows: units of their own as well (query_i8.hip, merge_i8.hip, sym_i8.hip, ...)
+#define GGNN_DISPATCH_DIST_I8(dtype, D, F)                                        \
+  do {                                                                            \
+    const ::ggnn_amd::DistConfig _dc = ::ggnn_amd::pick_dist_config((D), (dtype)); \
+    GGNN_DISPATCH_LAYOUT_I8(_dc, F);                                              \
+  } while (0)
+// a unit that holds the kernels of further element types only (GGNN_ROWS_16_TU, GGNN_ROWS_I8_TU):
+// the host code of the float32 / uint8 unit is left out of it
+#if defined(GGNN_ROWS_16_TU) || defined(GGNN_ROWS_I8_TU)
+#define GGNN_ROWS_EXTRA_TU
+#endif
 
 inline void check_vector_layout(const void* base, uint32_t D, ggnn_dtype dtype)
 {
@@ -2259,7 +2324,7 @@ inline void check_vector_layout(const void* base, uint32_t D, ggnn_dtype dtype)
   GGNN_REQUIRE(D >= 1 && D <= 4096, GGNN_INVALID_ARGUMENT, "D must be in [1, 4096]");
   GGNN_REQUIRE(D % epc == 0, GGNN_UNSUPPORTED,
                "this build needs D to be a multiple of 16 bytes per row "
-               "(4 for float32, 8 for float16 / bfloat16, 16 for uint8)");
+               "(4 for float32, 8 for float16 / bfloat16, 16 for uint8 / int8)");
   GGNN_REQUIRE((reinterpret_cast<uintptr_t>(base) & 15u) == 0, GGNN_INVALID_ARGUMENT,
                "base/query pointers must be 16-byte aligned");
 }

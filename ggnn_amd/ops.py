@@ -16,13 +16,13 @@ EUCLIDEAN, COSINE = 0, 1
 
 
 _DTYPE_CODES = {torch.float32: _lib.F32, torch.uint8: _lib.U8, torch.float16: _lib.F16,
-                torch.bfloat16: _lib.BF16}
+                torch.bfloat16: _lib.BF16, torch.int8: _lib.I8}
 
 
 def _dtype_code(t):
     code = _DTYPE_CODES.get(t.dtype)
     if code is None:
-        raise TypeError("base/query must be float32, uint8, float16 or bfloat16")
+        raise TypeError("base/query must be int8, float32, uint8, float16 or bfloat16")
     return code
 
 
@@ -72,7 +72,7 @@ def query_sizing(D, k_query, max_iterations):
 
 def dist_layout(D, dtype):
     """(lanes per row, 16-byte chunks per lane) of the distance kernels for rows of D elements of
-    `dtype` (torch.float32 / torch.uint8 / torch.float16 / torch.bfloat16)"""
+    `dtype` (torch.float32 / torch.uint8 / torch.int8 / torch.float16 / torch.bfloat16)"""
     import ctypes as C
     code = _DTYPE_CODES[dtype]
     lpr, nch = C.c_uint32(), C.c_uint32()

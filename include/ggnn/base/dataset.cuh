@@ -23,7 +23,8 @@
 
 namespace ggnn {
 
-enum class DataType : uint16_t { UNKNOWN, BYTE, UINT8, INT32, UINT32, FLOAT };
+// (INT8: this project's extension, signed 8-bit rows; behind the reference's enumerators)
+enum class DataType : uint16_t { UNKNOWN, BYTE, UINT8, INT32, UINT32, FLOAT, INT8 };
 enum class DataLocation : uint16_t {
   UNKNOWN, GPU, MANAGED, CPU_PINNED, CPU_MALLOC, FOREIGN_GPU, FOREIGN_CPU
 };
@@ -32,12 +33,15 @@ namespace detail {
 template <typename T> struct TypeTag;
 template <> struct TypeTag<std::byte> { static constexpr DataType value = DataType::BYTE; };
 template <> struct TypeTag<uint8_t> { static constexpr DataType value = DataType::UINT8; };
+template <> struct TypeTag<int8_t> { static constexpr DataType value = DataType::INT8; };
 template <> struct TypeTag<int32_t> { static constexpr DataType value = DataType::INT32; };
 template <> struct TypeTag<uint32_t> { static constexpr DataType value = DataType::UINT32; };
 template <> struct TypeTag<float> { static constexpr DataType value = DataType::FLOAT; };
 inline size_t size_of(DataType t)
 {
-  return (t == DataType::BYTE || t == DataType::UINT8) ? 1 : (t == DataType::UNKNOWN ? 0 : 4);
+  return (t == DataType::BYTE || t == DataType::UINT8 || t == DataType::INT8)
+             ? 1
+             : (t == DataType::UNKNOWN ? 0 : 4);
 }
 inline void hip_check(hipError_t e, const char* what)
 {

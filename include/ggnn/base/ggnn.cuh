@@ -203,7 +203,9 @@ class GGNN {
       return GGNN_F32;
     if (d.type == DataType::UINT8)
       return GGNN_U8;
-    throw std::runtime_error("unsupported datatype (float and uint8_t are supported)");
+    if (d.type == DataType::INT8)
+      return GGNN_I8;
+    throw std::runtime_error("unsupported datatype (float, uint8_t and int8_t are supported)");
   }
   static ggnn_location loc_of(const GenericDataset& d)
   {

@@ -47,8 +47,18 @@ typedef enum { GGNN_EUCLIDEAN = 0, GGNN_COSINE = 1 } ggnn_measure;
  * operations of the float32 path (no intermediate is rounded to 16 bits), so a 16-bit base gives
  * the results of a float32 base holding the widened values.  Distances returned stay float32.
  * Rows are padded to 16 bytes as for the other types (8 elements).  No pre-screen: see
- * ggnn_set_prescreen. */
-typedef enum { GGNN_F32 = 0, GGNN_U8 = 1, GGNN_F16 = 2, GGNN_BF16 = 3 } ggnn_dtype;
+ * ggnn_set_prescreen.
+ * GGNN_I8 (signed 8-bit, D bytes per row) has no reference counterpart either.  Base and query
+ * have the same type.  Squared L2: the exact integer sum (o - q)^2, formed in 32-bit integer
+ * arithmetic and converted once to float32 -- bit for bit the value of the GGNN_U8 path on the rows
+ * x ^ 0x80 (2 * 255^2 * 4096 < 2^32: nothing wraps).  Cosine: the signed dot product and the row's
+ * sum of squares are exact integers where the GGNN_U8 path forms integers, the query's sum of
+ * squares is a float fmaf chain over the sign-extended elements, then |1 - dot / sqrt(|q|^2 |o|^2)|
+ * as for every type; a zero row or a zero query gives 1.  Rows are padded with zeros to 16 bytes
+ * (16 elements) by the handle; the ggnn_op_* entry points require D % 16 == 0.  No pre-screen
+ * (8-bit rows are the compact copy already): ggnn_set_prescreen is accepted and has no effect.
+ * Code 4 is reserved and refused (GGNN_INVALID_ARGUMENT). */
+typedef enum { GGNN_F32 = 0, GGNN_U8 = 1, GGNN_F16 = 2, GGNN_BF16 = 3, GGNN_I8 = 5 } ggnn_dtype;
 /* include/ggnn/base/data.cuh (MemoryLocation) reduced to what the boundary needs */
 typedef enum { GGNN_CPU = 0, GGNN_GPU = 1 } ggnn_location;
 

@@ -1,6 +1,8 @@
-"""float32 / float16 / bfloat16 bases of the same data: speed, bytes and recall (1M x 128).
-    python scripts/dtype_probe.py [kinds] [n]
+"""float32 / float16 / bfloat16 / uint8 / int8 bases of the same data: speed, bytes and recall
+(1M x 128).
+    python scripts/dtype_probe.py [kinds] [n] [variants]
     python scripts/dtype_probe.py lowrank16,lowrankf16 1000000
+    python scripts/dtype_probe.py lowrank16 1000000 uint8,int8,uint8,int8   (alternating A/B)
 
 Every base is built from the same float32 rows (bench.synthetic) converted to each type; float32
 runs with the pre-screen on (default) and off.  lowrank16 holds integers in [0, 255], exact in all
@@ -8,7 +10,10 @@ three types (speed alone differs); lowrankf16 is fractional, so the 16-bit bases
 recall cost of the rounding).  Ground truth: each base's own bf_query.  Per variant, at the bench
 operating point and at the cheapest point of POINTS that reaches recall@10 0.99: queries/s and
 query-kernel ms on 10k-query batches, rows read per query x row bytes, HBM bytes per base row,
-build time and bf_query ms.  One JSON line per (kind, variant, point)."""
+build time and bf_query ms.  One JSON line per (kind, variant, point).
+uint8 / int8 (integer kinds only, i.e. lowrank16): the uint8 base holds the integers themselves, the
+int8 base the same rows `^ 0x80` (x - 128), so both do identical work; they are not part of the
+default variants (name them in the third argument, repeated for alternating runs)."""
 import json
 import os
 import sys
@@ -30,7 +35,18 @@ POINTS = ((0.85, 150), (0.85, 175), (0.9, 200), (0.95, 225), (1.0, 250), (1.0, 3
           (1.2, 600))
 VARIANTS = (("f32", torch.float32, True), ("f32-nops", torch.float32, False),
             ("f16", torch.float16, False), ("bf16", torch.bfloat16, False))
+BYTE_VARIANTS = {"uint8": ("uint8", torch.uint8, False), "int8": ("int8", torch.int8, False)}
+if len(sys.argv) > 3:
+    by_name = {**{v[0]: v for v in VARIANTS}, **BYTE_VARIANTS}
+    VARIANTS = tuple(by_name[v] for v in sys.argv[3].split(","))
 dev = torch.device("cuda", 0)
+
+
+def rows_as(x32, dt):
+    """the float32 rows in element type dt; int8: the uint8 rows biased by 128"""
+    if dt == torch.int8:
+        return (x32.to(torch.uint8) ^ 0x80).view(torch.int8).contiguous()
+    return x32.to(dt).contiguous()
 
 
 def timed_point(eng, q, gt, tau, iters, steps=3):
@@ -58,7 +74,7 @@ for kind in kinds:
     base32 = synthetic(kind, n, D, 1234, dev)
     q32 = synthetic(kind, NQ, D, 4321, dev)
     for name, dt, ps in VARIANTS:
-        base, q = base32.to(dt).contiguous(), q32.to(dt).contiguous()
+        base, q = rows_as(base32, dt), rows_as(q32, dt)
         es = base.element_size()
         eng = ggnn.GGNN()
         eng.set_base_reference(base)
