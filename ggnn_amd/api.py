@@ -176,6 +176,42 @@ def _labels(labels, n, what="labels", per="base vector"):
     return labels.contiguous()
 
 
+MAX_LABEL_SET = 8  # GGNN_MAX_LABEL_SET
+
+
+def _label_sets(label_sets, Nq):
+    """the `label_sets` argument as a contiguous [Nq, 1..8] int32 tensor (CPU or CUDA): a 2-D int32 /
+    int64 array or tensor is taken as it is (int64 must fit int32); anything else is read as one
+    sequence of 1..8 labels per query and padded to the longest row by repeating each row's first
+    entry"""
+    if isinstance(label_sets, np.ndarray):
+        label_sets = torch.from_numpy(np.ascontiguousarray(label_sets))
+    if not isinstance(label_sets, torch.Tensor):
+        rows = [[int(v) for v in (r.tolist() if hasattr(r, "tolist") else r)] for r in label_sets]
+        for n, r in enumerate(rows):
+            if not 1 <= len(r) <= MAX_LABEL_SET:
+                raise ValueError(f"the label set of query {n} has {len(r)} entries: 1 to "
+                                 f"{MAX_LABEL_SET} are allowed")
+        width = max((len(r) for r in rows), default=1)
+        label_sets = torch.tensor([r + r[:1] * (width - len(r)) for r in rows],
+                                  dtype=torch.int64).reshape(len(rows), width)
+    if label_sets.dim() != 2:
+        raise TypeError("label_sets must be 2-dimensional, or a sequence of per-query sequences")
+    if label_sets.dtype not in (torch.int32, torch.int64):
+        raise TypeError("label_sets must be int32 (or int64 with values that fit int32)")
+    if label_sets.shape[0] != Nq:
+        raise ValueError(f"label_sets needs one row per query ({Nq})")
+    if not 1 <= label_sets.shape[1] <= MAX_LABEL_SET:
+        raise ValueError(f"a label set has 1 to {MAX_LABEL_SET} entries, not "
+                         f"{label_sets.shape[1]}")
+    if label_sets.dtype == torch.int64:
+        if label_sets.numel() and (int(label_sets.min()) < _INT32_MIN or
+                                   int(label_sets.max()) > _INT32_MAX):
+            raise ValueError("label_sets has values outside the int32 range")
+        label_sets = label_sets.to(torch.int32)
+    return label_sets.contiguous()
+
+
 def _filter_words(filter, N):
     """the `filter` argument of query_filtered / bf_query_filtered as a contiguous int32 tensor of
     ceil(N / 32) words (CPU or CUDA): a boolean mask of length N is packed on the host, an
@@ -308,11 +344,12 @@ class QueryTicket:
     """Result of `GGNN.query_async`: `ids, dists = ticket` works as before; `query` keeps the
     input alive (and `filter_ids` the filter ids, or the query labels, of a batch that has some);
     `done` is set by `synchronize()`."""
-    __slots__ = ("query", "ids", "dists", "slot", "done", "filter_ids")
+    __slots__ = ("query", "ids", "dists", "slot", "done", "filter_ids", "label_sets")
 
-    def __init__(self, query, ids, dists, slot, filter_ids=None):
+    def __init__(self, query, ids, dists, slot, filter_ids=None, label_sets=None):
         self.query, self.ids, self.dists, self.slot, self.done = query, ids, dists, slot, False
         self.filter_ids = filter_ids
+        self.label_sets = label_sets
 
     def __iter__(self):
         return iter((self.ids, self.dists))
@@ -557,6 +594,45 @@ class GGNN:
         return self._blocking(lib().ggnn_bf_query_labeled, t, (int(k_gt), int(measure)),
                               self._where(ql))
 
+    def _labeled_in_tail(self, ls, fi):
+        """the filter arguments of the *_labeled_in calls: the sets, then the ids (or null)"""
+        ids = self._where(fi) if fi is not None else (None, _lib.CPU, 0)
+        return (ls.data_ptr(), ls.shape[1], *_loc(ls), *ids)
+
+    def query_labeled_in(self, query, k_query, tau_query, max_iterations=400,
+                         measure=DistanceMeasure.Euclidean, label_sets=None, filter_ids=None):
+        """Extension: `query` under label SETS (`set_labels`), combined with a filter id per query
+        (`set_filters`).  `label_sets`: for every query the labels it accepts -- a 2-D int32 / int64
+        array or tensor [Nq, 1..8], CPU or GPU, or a sequence of per-query sequences of 1 to 8
+        labels (padded by repeating a row's first entry; an empty or longer row is a ValueError).
+        Query n is given base vectors whose label equals one of its entries (an entry -1 accepts
+        every label) AND that row `filter_ids[n]` of the filter table allows (`filter_ids` as in
+        `query_filtered_by`; `None`: no bitset) -- bit for bit `query_filtered` with the mask
+        `isin(base_labels, label_sets[n]) & table[filter_ids[n]]`.  `label_sets=None` is no label
+        restriction (`query_filtered_by`); both `None` is `query`."""
+        if label_sets is None:
+            return self.query_filtered_by(query, k_query, tau_query, max_iterations, measure,
+                                          filter_ids=filter_ids)
+        t = _as_tensor(query, what="query")
+        ls = _label_sets(label_sets, t.shape[0])
+        fi = None if filter_ids is None else _filter_ids(filter_ids, t.shape[0])
+        return self._blocking(lib().ggnn_query_labeled_in, t,
+                              self._search(k_query, tau_query, max_iterations, measure),
+                              self._labeled_in_tail(ls, fi), self._shards)
+
+    def bf_query_labeled_in(self, query, k_gt=100, measure=DistanceMeasure.Euclidean,
+                            label_sets=None, filter_ids=None):
+        """Extension: the exact `k_gt` nearest among the base vectors `label_sets` and `filter_ids`
+        admit (see `query_labeled_in`); slots beyond their number are (-1, +inf).  Always the scan
+        kernels.  `label_sets=None` is `bf_query_filtered_by`; both `None` is `bf_query`."""
+        if label_sets is None:
+            return self.bf_query_filtered_by(query, k_gt, measure, filter_ids=filter_ids)
+        t = _as_tensor(query, what="query")
+        ls = _label_sets(label_sets, t.shape[0])
+        fi = None if filter_ids is None else _filter_ids(filter_ids, t.shape[0])
+        return self._blocking(lib().ggnn_bf_query_labeled_in, t, (int(k_gt), int(measure)),
+                              self._labeled_in_tail(ls, fi))
+
     def query_filtered(self, query, k_query, tau_query, max_iterations=400,
                        measure=DistanceMeasure.Euclidean, filter=None):
         """Extension: `query` among the base vectors `filter` allows -- a boolean mask of length N
@@ -641,22 +717,37 @@ class GGNN:
         return self._query_async(query, k_query, tau_query, max_iterations, measure, slot, None,
                                  labels)
 
+    def query_async_labeled_in(self, query, k_query, tau_query, max_iterations=400,
+                               measure=DistanceMeasure.Euclidean, slot=0, label_sets=None,
+                               filter_ids=None):
+        """Extension: `query_async` under label sets and filter ids (`query_labeled_in`), both with
+        the memory and lifetime rules of the `filter_ids` of `query_async` (kept alive on the
+        ticket: `ticket.filter_ids`, `ticket.label_sets`).  `label_sets=None` is `query_async`."""
+        return self._query_async(query, k_query, tau_query, max_iterations, measure, slot,
+                                 filter_ids, None, label_sets)
+
     def _query_async(self, query, k_query, tau_query, max_iterations, measure, slot, filter_ids,
-                     labels):
+                     labels, label_sets=None):
         t = _as_tensor(query, what="query")
         fi = None if filter_ids is None else _filter_ids(filter_ids, t.shape[0])
         if labels is not None:
             fi = _labels(labels, t.shape[0], per="query")
+        ls = None if label_sets is None else _label_sets(label_sets, t.shape[0])
+
+        def follow(x, pinned):
+            # sets and ids follow the query's memory rule: its GPU, or page-locked host memory
+            if x is None:
+                return None
+            x = x.to(t.device) if t.is_cuda else (x.cpu() if x.is_cuda else x)
+            if pinned and not x.is_cuda and not x.is_pinned():
+                x = x.pin_memory()
+            return x
         if self._num_gpus > 1 or _lib.get_hook("EXCHANGE") == 1:
             # several GPUs (or the forced RCCL path of the tests): merged [Nq, k] results; host-side tensors are page-locked so that the
             # engine's copies stay asynchronous
             if not t.is_cuda and not t.is_pinned():
                 t = t.pin_memory()
-            if fi is not None:
-                # the ids follow the query's memory rule: its GPU, or page-locked host memory
-                fi = fi.to(t.device) if t.is_cuda else (fi.cpu() if fi.is_cuda else fi)
-                if not fi.is_cuda and not fi.is_pinned():
-                    fi = fi.pin_memory()
+            fi, ls = follow(fi, True), follow(ls, True)
             dev = t.device.index if t.is_cuda else -1
             if t.is_cuda:
                 ids, dists = self._out(t.shape[0], int(k_query), True, t.device)
@@ -668,10 +759,18 @@ class GGNN:
             if not t.is_cuda:
                 raise RuntimeError("query_async needs the query on the GPU")
             loc, dev = _loc(t)
-            if fi is not None:
-                fi = fi.to(t.device)
+            fi, ls = follow(fi, False), follow(ls, False)
             ids, dists = self._out(t.shape[0], int(k_query) * self._shards, True, t.device)
-        if fi is not None:
+        if ls is not None:
+            for x in (ls, fi):
+                if x is not None and x.is_cuda:
+                    torch.cuda.current_stream(x.device).synchronize()
+            self._check(lib().ggnn_query_async_labeled_in(
+                self._h, t.data_ptr(), t.shape[0], t.shape[1], _dtype_code(t), dev, int(k_query),
+                float(tau_query), int(max_iterations), int(measure), ids.data_ptr(),
+                dists.data_ptr(), int(slot), ls.data_ptr(), ls.shape[1],
+                None if fi is None else fi.data_ptr()))
+        elif fi is not None:
             if fi.is_cuda:
                 torch.cuda.current_stream(fi.device).synchronize()
             call = (lib().ggnn_query_async_labeled if labels is not None
@@ -685,7 +784,7 @@ class GGNN:
                                                _dtype_code(t), dev, int(k_query), float(tau_query),
                                                int(max_iterations), int(measure), ids.data_ptr(),
                                                dists.data_ptr(), int(slot)))
-        ticket = QueryTicket(t, ids, dists, int(slot), fi)
+        ticket = QueryTicket(t, ids, dists, int(slot), fi, ls)
         held = self._inflight.setdefault(int(slot) % _ASYNC_SLOTS, [])
         if len(held) >= _MAX_TICKETS_PER_SLOT:
             # a serving loop that waits some other way (its own events, torch.cuda.synchronize)

@@ -437,6 +437,7 @@ void launch_scatter_labels(int32_t* labels, uint64_t N, const uint32_t* ids, con
 
 bool bf_mfma_supported(const BfLaunch& a);
 bool bf_mfma_uses_i8(const BfLaunch& a);
+void launch_bf_query_labelset(const BfLaunch& a, hipStream_t stream);  // bf_query_labelset.hip
 void launch_bf_query_mfma(const BfLaunch& a, hipStream_t stream);
 
 // scan of all queries (qlist == nullptr) or of the subset qlist[0, *qcount); slices > 1 needs
@@ -478,7 +479,8 @@ static void launch_bf_scan(const BfLaunch& a, uint32_t slices, uint32_t rows_per
                                 a.dists, qlist, qcount, stream);
 }
 
-static void slice_rows(uint32_t N_base, uint32_t& slices, uint32_t& rows_per_slice)
+// (shared with bf_query_labelset.hip)
+void bf_slice_rows(uint32_t N_base, uint32_t& slices, uint32_t& rows_per_slice)
 {
   const uint32_t row_quant = 64;  // multiple of ROWS*STEPS for every configuration
   slices = std::max(1u, std::min(slices, 64u));
@@ -496,7 +498,7 @@ size_t bf_rescan_tmp_entries(const BfLaunch& a, uint32_t* slices_out)
   uint32_t slices = std::min(32u, std::max(1u, 32768u / std::max(1u, a.Nq)));
   slices = std::min(slices, std::max(1u, a.N_base / 4096u));
   uint32_t rows = 0;
-  slice_rows(a.N_base, slices, rows);
+  bf_slice_rows(a.N_base, slices, rows);
   *slices_out = slices;
   return slices > 1 ? static_cast<size_t>(slices) * a.Nq * a.k_query : 0;
 }
@@ -505,7 +507,7 @@ void launch_bf_rescan(const BfLaunch& a, const uint32_t* qlist, const uint32_t* 
 {
   uint32_t slices = 0, rows = 0;
   (void)bf_rescan_tmp_entries(a, &slices);
-  slice_rows(a.N_base, slices, rows);
+  bf_slice_rows(a.N_base, slices, rows);
   launch_bf_scan(a, slices, rows, qlist, qcount, tmp_ids, tmp_dists, stream);
 }
 
@@ -517,6 +519,11 @@ void launch_bf_query(const BfLaunch& a_in, hipStream_t stream)
     *a_in.matrix_path = 0;
   if (a_in.Nq == 0)
     return;
+  // label sets: scan kernels of their own, no matrix-core form
+  if (a_in.label_sets.labels) {
+    launch_bf_query_labelset(a_in, stream);
+    return;
+  }
   // what a filtered launch must bring, on either path
   GGNN_REQUIRE(!a_in.filter_table.query_labels || (a_in.filter_bits && !a_in.filter_table.ids),
                GGNN_INVALID_ARGUMENT,
@@ -565,7 +572,7 @@ void launch_bf_query(const BfLaunch& a_in, hipStream_t stream)
   if (a.Nq < target_waves)
     slices = std::min((target_waves + a.Nq - 1) / a.Nq, std::max(1u, a.N_base / 4096u));
   uint32_t rows_per_slice = 0;
-  slice_rows(a.N_base, slices, rows_per_slice);
+  bf_slice_rows(a.N_base, slices, rows_per_slice);
 
   int32_t* tmp_ids = nullptr;
   float* tmp_dists = nullptr;

@@ -144,6 +144,18 @@ struct FilterTable {
   uint32_t num_filters{0};
   const int32_t* query_labels{nullptr};  // [Nq] (device) or null
 };
+// Label sets (with a label column): query n carries width <= 8 labels, sets[n * width + j], and a
+// base vector may be given to it iff its label equals one of them; an entry -1 admits every label,
+// entries may repeat.  A launch with labels != nullptr is a label-set launch: filter_bits is then the
+// filter table or null, filter_table.ids the filter id per query or null (both null: labels only),
+// and a vector must ALSO have its bit set in the query's row -- id -1 admits every vector, an id
+// outside [0, num_filters) none.  filter_table.consts and query_labels are not used; filter_bit_offset
+// is the shard's first global id in the column and in the table alike.
+struct LabelSetSpec {
+  const int32_t* labels{nullptr};  // [>= offset + N_base] (device)
+  const int32_t* sets{nullptr};    // [Nq x width] (device)
+  uint32_t width{0};               // 1 .. 8 (GGNN_MAX_LABEL_SET)
+};
 // the two constant rows for a launch that was given none (null if ids is null); free with
 // scratch_free(p, stream) after the launch
 uint32_t* filter_consts_scratch(const FilterTable& t, hipStream_t stream);
@@ -181,6 +193,8 @@ struct QueryLaunch {
   uint32_t filter_bit_offset{0};
   // per-query filters: filter_bits is then a table (see FilterTable)
   FilterTable filter_table{};
+  // label-set filters (labels != nullptr: see LabelSetSpec)
+  LabelSetSpec label_sets{};
 };
 void launch_query(const QueryLaunch& a, hipStream_t stream);
 
@@ -232,6 +246,8 @@ struct BfLaunch {
   // optional (HOST): 1 if the launch ran the tile kernels of bf_mfma.hip, 0 if it ran the scan --
   // decided on the host before anything is enqueued; results are bit-identical either way
   int* matrix_path{nullptr};
+  // label-set filters (labels != nullptr: see LabelSetSpec); always the scan
+  LabelSetSpec label_sets{};
 };
 void launch_bf_query(const BfLaunch& a, hipStream_t stream);
 

@@ -471,11 +471,17 @@ struct QueryRequest {
 // Nq).  The three constructors validate against the handle; a search is filtered iff it is handed
 // one of these, never by anything the handle remembers.
 struct QueryFilter {
-  enum Kind { None, Bitset, TableIds, Labels } kind{None};
+  enum Kind { None, Bitset, TableIds, Labels, LabelSets } kind{None};
   const void* ptr{nullptr};
   uint64_t count{0};
   ggnn_location loc{GGNN_CPU};
   int gpu{0};
+  // LabelSets: ptr is the [Nq x width] label sets (count = Nq * width) and ids the filter id per
+  // query ([Nq], or null: labels only), each with its own location
+  uint32_t width{0};
+  const int32_t* ids{nullptr};
+  ggnn_location ids_loc{GGNN_CPU};
+  int ids_gpu{0};
   static QueryFilter bitset(const ggnn_handle& h, const uint32_t* bits, uint64_t n_bits,
                             ggnn_location loc, int gpu);
   // read_host_ids: ids in host memory are range-checked here (the blocking calls; the asynchronous
@@ -484,14 +490,19 @@ struct QueryFilter {
                                ggnn_location loc, int gpu, bool read_host_ids = true);
   static QueryFilter labels(const ggnn_handle& h, const int32_t* query_labels, uint64_t Nq,
                             ggnn_location loc, int gpu);
+  static QueryFilter label_sets(const ggnn_handle& h, const int32_t* sets, uint32_t width,
+                                uint64_t Nq, ggnn_location loc, int gpu, const int32_t* ids,
+                                ggnn_location ids_loc, int ids_gpu, bool read_host_ids = true);
 };
 
 // A QueryFilter on one GPU, as a launch takes it (filter_bits / filter_table of QueryLaunch and
 // BfLaunch): bits is the bitset, the resident table (table.ids set) or the resident label column
-// (table.query_labels set); all null: unfiltered.
+// (table.query_labels set); all null: unfiltered.  Label sets: set.labels is the resident label column
+// and bits / table.ids the resident table and the filter ids, or null.
 struct DeviceFilter {
   const uint32_t* bits{nullptr};
   FilterTable table{};
+  LabelSetSpec set{};
   // ... of the queries from `first` on (a half-batch; a bitset is shared by all queries)
   DeviceFilter from(uint32_t first) const
   {
@@ -500,6 +511,8 @@ struct DeviceFilter {
       d.table.ids += first;
     if (d.table.query_labels)
       d.table.query_labels += first;
+    if (d.set.sets)
+      d.set.sets += static_cast<size_t>(first) * d.set.width;
     return d;
   }
 };
@@ -659,6 +672,7 @@ struct ggnn_handle {
   // the lane's stream (blocking lane: ctx.filter_stage / filter_ids_stage, a slot's lane: its
   // f_stage); the resident table or label column is placed if it is missing or stale
   DeviceFilter resolve_filter(DeviceCtx& ctx, const QueryFilter& f, int lane);
+  DeviceFilter resolve_label_sets(DeviceCtx& ctx, const QueryFilter& f, int lane);
 
   // the search of local shard si for nq queries of request r, without work counters
   QueryLaunch shard_launch(const DeviceCtx& ctx, uint32_t si, const QueryRequest& r,

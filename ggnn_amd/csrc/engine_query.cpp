@@ -76,6 +76,7 @@ QueryLaunch ggnn_handle::shard_launch(const DeviceCtx& ctx, uint32_t si, const Q
   ql.filter_bits = df.bits;
   ql.filter_bit_offset = sh.global_id * cfg.N;
   ql.filter_table = df.table;
+  ql.label_sets = df.set;
   return ql;
 }
 
@@ -523,6 +524,7 @@ void ggnn_handle::bf_query(const QueryRequest& r, const QueryFilter& filter)
   const DeviceFilter df = resolve_filter(ctx, filter, DeviceCtx::kBlockingLane);
   bl.filter_bits = df.bits;
   bl.filter_table = df.table;
+  bl.label_sets = df.set;
   // (one launch over the whole base: "every shard" is this launch)
   last_bf_matrix_path = 0;
   bl.matrix_path = &last_bf_matrix_path;
@@ -579,11 +581,81 @@ QueryFilter QueryFilter::labels(const ggnn_handle& h, const int32_t* query_label
   return {Labels, query_labels, Nq, loc, gpu};
 }
 
+QueryFilter QueryFilter::label_sets(const ggnn_handle& h, const int32_t* sets, uint32_t width,
+                                    uint64_t Nq, ggnn_location loc, int gpu, const int32_t* ids,
+                                    ggnn_location ids_loc, int ids_gpu, bool read_host_ids)
+{
+  GGNN_REQUIRE(width >= 1 && width <= GGNN_MAX_LABEL_SET, GGNN_INVALID_ARGUMENT,
+               "set_width " + std::to_string(width) + " is outside [1, " +
+                   std::to_string(GGNN_MAX_LABEL_SET) + "]");
+  GGNN_REQUIRE(sets != nullptr, GGNN_INVALID_ARGUMENT, "the label set array is null");
+  GGNN_REQUIRE(!h.labels_host.empty(), GGNN_INVALID_STATE,
+               "There are no labels the label sets could refer to (ggnn_set_labels).");
+  QueryFilter f{LabelSets, sets, Nq * width, loc, gpu};
+  f.width = width;
+  if (ids) {
+    // (the rules of the filter ids of ggnn_query_filtered_by)
+    const QueryFilter t = table_ids(h, ids, Nq, ids_loc, ids_gpu, read_host_ids);
+    f.ids = ids;
+    f.ids_loc = t.loc;
+    f.ids_gpu = t.gpu;
+  }
+  GGNN_REQUIRE(h.base_dtype != GGNN_I8, GGNN_UNSUPPORTED,
+               "label sets are not built for int8 bases");
+  return f;
+}
+
+// label sets: the resident column and (with filter ids) the resident table; the sets and the ids
+// are used in place on their own GPU, else staged behind one another in the lane's id stage
+DeviceFilter ggnn_handle::resolve_label_sets(DeviceCtx& ctx, const QueryFilter& f, int lane)
+{
+  DeviceFilter d;
+  d.set.labels = place_labels(ctx);
+  d.set.width = f.width;
+  if (f.ids) {
+    d.bits = place_filter_table(ctx);
+    d.table.words = filter_words;
+    d.table.num_filters = num_filters;
+  }
+  const bool blocking = lane == DeviceCtx::kBlockingLane;
+  const auto in_place = [&](const void* p, ggnn_location loc, int gpu) {
+    return loc == GGNN_GPU && gpu == ctx.device && (reinterpret_cast<uintptr_t>(p) & 3u) == 0;
+  };
+  const size_t set_bytes = static_cast<size_t>(f.count) * 4;
+  const size_t id_bytes = f.ids ? static_cast<size_t>(f.count / f.width) * 4 : 0;
+  const bool stage_sets = !in_place(f.ptr, f.loc, f.gpu);
+  const bool stage_ids = f.ids && !in_place(f.ids, f.ids_loc, f.ids_gpu);
+  DeviceBuffer& stage = blocking ? ctx.filter_ids_stage : ctx.xb[lane].f_stage;
+  const size_t bytes = (stage_sets ? set_bytes : 0) + (stage_ids ? id_bytes : 0);
+  if (bytes) {
+    if (blocking)
+      DeviceCtx::grow(stage, bytes);
+    else
+      grow_lane(ctx, lane, stage, bytes);
+  }
+  uint8_t* at = static_cast<uint8_t*>(stage.p);
+  const auto here = [&](const void* p, bool staged, size_t n, ggnn_location loc) {
+    if (!staged)
+      return p;
+    GGNN_HIP_CHECK(hipMemcpyAsync(at, p, n, loc == GGNN_GPU ? hipMemcpyDefault : hipMemcpyHostToDevice,
+                                  ctx.lane_stream(lane)));
+    const void* r = at;
+    at += n;
+    return r;
+  };
+  d.set.sets = static_cast<const int32_t*>(here(f.ptr, stage_sets, set_bytes, f.loc));
+  if (f.ids)
+    d.table.ids = static_cast<const int32_t*>(here(f.ids, stage_ids, id_bytes, f.ids_loc));
+  return d;
+}
+
 DeviceFilter ggnn_handle::resolve_filter(DeviceCtx& ctx, const QueryFilter& f, int lane)
 {
   DeviceFilter d;
   if (f.kind == QueryFilter::None)
     return d;
+  if (f.kind == QueryFilter::LabelSets)
+    return resolve_label_sets(ctx, f, lane);
   // what is resident: the filter table, or the label column (the kernels read it through
   // filter_bits, common.hpp: the only place that casts it)
   if (f.kind == QueryFilter::TableIds) {
@@ -617,6 +689,7 @@ DeviceFilter ggnn_handle::resolve_filter(DeviceCtx& ctx, const QueryFilter& f, i
     case QueryFilter::Bitset: d.bits = static_cast<const uint32_t*>(here); break;
     case QueryFilter::TableIds: d.table.ids = static_cast<const int32_t*>(here); break;
     case QueryFilter::Labels: d.table.query_labels = static_cast<const int32_t*>(here); break;
+    case QueryFilter::LabelSets:
     case QueryFilter::None: break;
   }
   return d;

@@ -210,7 +210,7 @@ void launch_query(const QueryLaunch& a, hipStream_t stream)
                            a.KBuild <= 8 * kEarlySteps && hook(kHookQueryEarly) != 0 &&
                            hook(kHookQueryGlobalRing) != 0 && early_shape && set_shape;
   // (the filtered kernels keep their ring in LDS: no scratch)
-  if (!a.filter_bits &&
+  if (!a.filter_bits && !a.label_sets.labels &&
       (global_ring || (args.sorted <= 64 && set_shape && tag_set_usable(vis, a.N_base) &&
                        hook(kHookVisTagSet) != 0))) {
     args.tag_bits = global_ring ? 0 : tag_set_bucket_bits(vis);
@@ -239,7 +239,13 @@ void launch_query(const QueryLaunch& a, hipStream_t stream)
     args.ps_lossless = (a.ps_lossless && a.measure == GGNN_EUCLIDEAN && hook(kHookPsExact) != 0) ? 1u : 0u;
   }
 
-  if (a.filter_bits) {
+  if (a.label_sets.labels) {
+    // any of a set of labels per query, with an optional filter id (query_labelset.hip)
+    args.filter_bits = a.filter_bits;
+    args.filter_bit_offset = a.filter_bit_offset;
+    launch_query_labelset(args, a.filter_table, a.label_sets, use_ps, a.measure, a.dtype, stream);
+  }
+  else if (a.filter_bits) {
     args.filter_bits = a.filter_bits;
     args.filter_bit_offset = a.filter_bit_offset;
     // restricted to an allowed-id bitset (query_filtered.hip) or to a label (query_labeled.hip)

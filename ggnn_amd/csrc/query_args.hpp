@@ -45,4 +45,10 @@ struct FilteredQueryArgs : QueryArgs {
   FilterTable filter_table;
 };
 
+// Arguments of the label-set kernels (query_labelset.hip): the label column and the queries' sets
+// beside the optional filter table.  Derived once more, so that FilteredQueryArgs stays what it is.
+struct LabelSetQueryArgs : FilteredQueryArgs {
+  LabelSetSpec set;
+};
+
 }  // namespace ggnn_amd

@@ -23,6 +23,12 @@
 // (TuFilter: LabelFilter under GGNN_LABELS_TU -- query_labeled.hip, query_labeled_16.hip -- else
 // IdFilter), so the bitset kernels are not touched by the label ones and the build compiles both
 // in parallel.
+//
+// Label sets (any of up to 8 labels per query, with an optional filter id: LabelSetFilter): once more
+// the same wave program in kernel templates of its own (query_labelset_kernel*), instantiated under
+// GGNN_LABELSET_TU -- query_labelset.hip, query_labelset_16.hip.  Their argument block is
+// LabelSetQueryArgs; there is no int8 unit and no PrescreenExact variant (a lossless base takes the
+// ordinary pre-screened kernel: the same results by construction).
 #include <algorithm>
 
 #include "query_wave.hpp"
@@ -77,12 +83,46 @@ __global__ void __launch_bounds__(kWave) query_labeled_kernel_lds(const Filtered
 #include "query_wave_lds_body.inc"
 }
 
+// Label sets.  One more register per lane is live from the request to the replay (the bitset word
+// next to the label), and the eight wanted labels are scalar: the occupancy is the largest at which
+// the early-rows squared-L2 kernels of float32 / uint8 rows have no private segment.
+// At 7 waves (72 registers) the pre-screened early-rows kernels with two bucket registers go 12 / 28
+// bytes into scratch memory on one- and three-chunk float rows as well, not only on two-chunk ones as
+// under IdFilter: every pre-screened early-rows kernel gets 80 registers (6 waves).
+template <class PSC, bool EARLY>
+constexpr int labelset_waves()
+{
+  return (EARLY && PSC::enabled) ? 6 : 7;
+}
+
+template <typename BaseT, int LPR, int NCH, int R, int MODE, class PSC, int HB = 0, bool EARLY = false>
+__global__ void __launch_bounds__(kWave) __attribute__((
+    amdgpu_waves_per_eu((R == 1 && NCH <= 3) ? labelset_waves<PSC, EARLY>() : 1)))
+query_labelset_kernel(const LabelSetQueryArgs a)
+{
+  static_assert(HB >= 0, "the filtered kernels keep their visited ring in LDS");
+  static_assert(!PsExact<PSC>::value, "label sets: no kernels of exact distances from codes");
+  using FILT = LabelSetFilter;
+  constexpr bool GR = false;
+#include "query_wave_body.inc"
+}
+
+// the LDS-resident list (SORTED > 2048, or > 512 with the pre-screen)
+template <typename BaseT, int LPR, int NCH, int MODE, class PSC>
+__global__ void __launch_bounds__(kWave) query_labelset_kernel_lds(const LabelSetQueryArgs a)
+{
+  using FILT = LabelSetFilter;
+#include "query_wave_lds_body.inc"
+}
+
 // the kernel templates of a filter class
 template <class FILT, typename BaseT, int LPR, int NCH, int R, int MODE, class PSC, int HB = 0,
           bool EARLY = false>
 constexpr auto filtered_kernel()
 {
-  if constexpr (std::is_same<FILT, LabelFilter>::value)
+  if constexpr (std::is_same<FILT, LabelSetFilter>::value)
+    return &query_labelset_kernel<BaseT, LPR, NCH, R, MODE, PSC, HB, EARLY>;
+  else if constexpr (std::is_same<FILT, LabelFilter>::value)
     return &query_labeled_kernel<BaseT, LPR, NCH, R, MODE, PSC, HB, EARLY>;
   else
     return &query_filtered_kernel<BaseT, LPR, NCH, R, MODE, PSC, HB, EARLY>;
@@ -90,7 +130,9 @@ constexpr auto filtered_kernel()
 template <class FILT, typename BaseT, int LPR, int NCH, int MODE, class PSC>
 constexpr auto filtered_kernel_lds()
 {
-  if constexpr (std::is_same<FILT, LabelFilter>::value)
+  if constexpr (std::is_same<FILT, LabelSetFilter>::value)
+    return &query_labelset_kernel_lds<BaseT, LPR, NCH, MODE, PSC>;
+  else if constexpr (std::is_same<FILT, LabelFilter>::value)
     return &query_labeled_kernel_lds<BaseT, LPR, NCH, MODE, PSC>;
   else
     return &query_filtered_kernel_lds<BaseT, LPR, NCH, MODE, PSC>;
@@ -99,8 +141,9 @@ constexpr auto filtered_kernel_lds()
 // the kernel of one row layout, measure and pre-screen (launch_query_cfg, query_wave.hpp)
 template <class FILT>
 struct FilteredLadder {
-  template <typename BaseT, int LPR, int NCH, int MODE, class PSC>
-  static void launch(const FilteredQueryArgs& args, hipStream_t stream)
+  // (ARGS: FilteredQueryArgs, or LabelSetQueryArgs under LabelSetFilter)
+  template <typename BaseT, int LPR, int NCH, int MODE, class PSC, class ARGS>
+  static void launch(const ARGS& args, hipStream_t stream)
   {
     const uint32_t sorted = args.sorted;
     if constexpr (early_rows_layout<LPR, NCH, PSC>()) {
@@ -109,7 +152,9 @@ struct FilteredLadder {
       if (hb != 0 && args.KBuild <= 8 * kEarlySteps && hook(kHookQueryEarly) != 0) {
         const size_t qrow = DistEngine<BaseT, LPR, NCH, PSC::enabled>::kQueryLdsBytes;
         // (PSX: the two-phase variant for a base known to be lossless, as in QueryLadder)
-        using PSX = typename ExactOf<PSC>::type;
+        // (label sets have no such variant: PSX = PSC and `exact` is false)
+        using PSX = std::conditional_t<std::is_same<FILT, LabelSetFilter>::value, PSC,
+                                       typename ExactOf<PSC>::type>;
         const bool exact = args.ps_lossless != 0 && !std::is_same<PSX, PSC>::value;
         if (hb == 1)
           launch_wave_per_query(exact ? filtered_kernel<FILT, BaseT, LPR, NCH, 1, MODE, PSX, 1, true>()
@@ -139,7 +184,48 @@ using TuFilter = LabelFilter;
 using TuFilter = IdFilter;
 #endif
 
+#ifdef GGNN_LABELSET_TU
 #ifdef GGNN_ROWS_16_TU
+void launch_query_labelset_16(const LabelSetQueryArgs& args, ggnn_measure measure, ggnn_dtype dtype,
+                              hipStream_t stream)
+{
+#define GGNN_LAUNCH_QF(T, LPR, NCH) \
+  launch_query_cfg<FilteredLadder<LabelSetFilter>, T, LPR, NCH>(args, false, measure, stream)
+  GGNN_DISPATCH_DIST_16(dtype, args.D, GGNN_LAUNCH_QF);
+#undef GGNN_LAUNCH_QF
+}
+#else
+// base: filled by launch_query (query.hip); table: the filter table in base.filter_bits (or null)
+// and the filter id per query (or null); set: the label column and the queries' label sets
+void launch_query_labelset(const QueryArgs& base, const FilterTable& table, const LabelSetSpec& set,
+                           bool use_ps, ggnn_measure measure, ggnn_dtype dtype, hipStream_t stream)
+{
+  GGNN_REQUIRE(set.labels != nullptr && set.sets != nullptr, GGNN_INVALID_ARGUMENT,
+               "the label column or the label sets are missing");
+  GGNN_REQUIRE(set.width >= 1 && set.width <= kMaxLabelSet, GGNN_INVALID_ARGUMENT,
+               "a label set has 1 to 8 entries");
+  GGNN_REQUIRE(!table.query_labels, GGNN_INVALID_ARGUMENT,
+               "label sets exclude the one-label form");
+  GGNN_REQUIRE(!table.ids || !table.num_filters || (base.filter_bits && table.words),
+               GGNN_INVALID_ARGUMENT, "filter ids into a table need the table");
+  GGNN_REQUIRE(dtype != GGNN_I8, GGNN_UNSUPPORTED, "label sets are not built for int8 rows");
+  GGNN_REQUIRE(base.N_base <= kMaxLabeledShardRows, GGNN_UNSUPPORTED,
+               "label filters need shards of at most 2^30 base vectors");
+  LabelSetQueryArgs args{};
+  static_cast<QueryArgs&>(args) = base;
+  args.filter_table = table;
+  args.set = set;
+  if (dtype_is_16bit(dtype)) {
+    launch_query_labelset_16(args, measure, dtype, stream);
+    return;
+  }
+#define GGNN_LAUNCH_QF(T, LPR, NCH) \
+  launch_query_cfg<FilteredLadder<LabelSetFilter>, T, LPR, NCH>(args, use_ps, measure, stream)
+  GGNN_DISPATCH_DIST_32_8(dtype, args.D, GGNN_LAUNCH_QF);
+#undef GGNN_LAUNCH_QF
+}
+#endif
+#elif defined(GGNN_ROWS_16_TU)
 template <class FILT>
 void launch_query_filtered_16(const FilteredQueryArgs& args, ggnn_measure measure, ggnn_dtype dtype,
                               hipStream_t stream)

@@ -21,7 +21,9 @@ GGNN_DEV void load_prescreen(PSC& ps, const QueryArgs& a, const BaseT* qrow)
 template <class FILT, class ARGS>
 GGNN_DEV FILT wave_filter(const ARGS& a, const uint32_t n)
 {
-  if constexpr (std::is_same<FILT, LabelFilter>::value)
+  if constexpr (std::is_same<FILT, LabelSetFilter>::value)
+    return LabelSetFilter(a.filter_bits, a.filter_bit_offset, a.filter_table, a.set, n);
+  else if constexpr (std::is_same<FILT, LabelFilter>::value)
     return LabelFilter(a.filter_bits, a.filter_bit_offset, a.filter_table, n);
   else if constexpr (FILT::enabled)
     return IdFilter{wave_filter_bits(a.filter_bits, a.filter_table, n), a.filter_bit_offset, kEmptyKey,
@@ -169,6 +171,12 @@ void launch_query_filtered_16(const FilteredQueryArgs& args, ggnn_measure measur
 // (and query_filtered_i8 / query_labeled_i8 for int8 rows)
 template <class FILT>
 void launch_query_filtered_i8(const FilteredQueryArgs& args, ggnn_measure measure, ggnn_dtype dtype,
+                              hipStream_t stream);
+// Label sets (LabelSetFilter): query_labelset for float32 / uint8 rows and query_labelset_16 for
+// float16 / bfloat16 ones; there are no int8 kernels (GGNN_UNSUPPORTED)
+void launch_query_labelset(const QueryArgs& base, const FilterTable& table, const LabelSetSpec& set,
+                           bool use_ps, ggnn_measure measure, ggnn_dtype dtype, hipStream_t stream);
+void launch_query_labelset_16(const LabelSetQueryArgs& args, ggnn_measure measure, ggnn_dtype dtype,
                               hipStream_t stream);
 
 }  // namespace ggnn_amd

@@ -1866,6 +1866,85 @@ struct LabelFilter {
   }
 };
 
+// Label-set filters: query n carries up to kMaxLabelSet labels and, optionally, a filter id into a
+// filter table; a candidate is denied iff its label is in none of the set's entries (an entry -1
+// admits every label), or its bit of the query's table row is clear (LabelSetSpec, common.hpp).  The
+// interface is IdFilter's; request() issues TWO gathers per lane in front of the first-read rows --
+// the label dword as in LabelFilter, then the bitset word as in IdFilter -- and the verdict is taken
+// once per fetch at the replay:
+//   denied = ((label & vmask) != want[j] for all eight j)  ||  bit (id + offset) of `bits` is clear
+// The wave constructor pads a narrower set to eight entries by repeating its first one, so there is
+// one compare chain whatever the width; want[], vmask, both pointers and the offsets are
+// wave-uniform, read once before the loop.  ONE class for calls with and without a bitset: a wave
+// that has none (no filter ids, or id -1) points `bits` at a constant all-ones word and ANDs the
+// byte offset of its gather with 0 (imask), so it indexes nothing it was not given; an id outside
+// the table points at the all-zero word next to it in the same way (an empty result).
+constexpr uint32_t kMaxLabelSet = 8;  // GGNN_MAX_LABEL_SET
+// {all ones, all zeros}: emitted only into the code objects whose kernels name it
+template <class T = void>
+__device__ const uint32_t kFilterConstWords[2] = {~0u, 0u};
+struct LabelSetFilter {
+  static constexpr bool enabled = true;
+  const int32_t* labels;  // the column at the shard's first global id
+  const uint32_t* bits;   // the query's row of the table, or one of the constant words
+  uint32_t offset;        // first global id of the shard (bit offset)
+  uint32_t imask;         // ~3u: `bits` is a row;  0: it is one word
+  uint32_t vmask, want[kMaxLabelSet];
+  int key;               // the candidate this lane asked for (or EMPTY)
+  uint32_t word, bword;  // its label, its word of the bitset
+  // the filter of the wave of query n (scalar: the query number is wave-uniform)
+  GGNN_DEV LabelSetFilter(const uint32_t* table, const uint32_t shard_offset, const FilterTable& t,
+                          const LabelSetSpec& s, const uint32_t n)
+      : labels(s.labels + shard_offset), bits(kFilterConstWords<>), offset(shard_offset), imask(0u),
+        key(kEmptyKey), word(0u), bword(0u)
+  {
+    const int32_t* set = s.sets + static_cast<size_t>(n) * s.width;
+    bool wildcard = false;
+#pragma unroll
+    for (uint32_t j = 0; j < kMaxLabelSet; ++j) {
+      const int32_t L = __builtin_amdgcn_readfirstlane(set[j < s.width ? j : 0u]);
+      wildcard = wildcard || L == -1;
+      want[j] = static_cast<uint32_t>(L);
+    }
+    vmask = wildcard ? 0u : ~0u;
+#pragma unroll
+    for (uint32_t j = 0; j < kMaxLabelSet; ++j)
+      want[j] &= vmask;
+    if (t.ids) {
+      const int32_t f = __builtin_amdgcn_readfirstlane(t.ids[n]);
+      if (static_cast<uint32_t>(f) < t.num_filters) {
+        bits = table + static_cast<size_t>(static_cast<uint32_t>(f)) * t.words;
+        imask = ~3u;
+      }
+      else if (f != -1)
+        bits = kFilterConstWords<> + 1;
+    }
+  }
+  GGNN_DEV void request(const int cand)
+  {
+    key = cand;
+    // EMPTY slots read the label and the bitset word of the shard's first id (verdict ignored)
+    const uint32_t c = static_cast<uint32_t>(max(cand, 0));
+    word = filter_word_at(labels, c << 2);
+    bword = filter_word_at(bits, ((c + offset) >> 3) & imask);
+  }
+  // lanes whose candidate is denied
+  GGNN_DEV unsigned long long denied_lanes() const
+  {
+    const uint32_t w = word & vmask;
+    bool none = true;
+#pragma unroll
+    for (uint32_t j = 0; j < kMaxLabelSet; ++j)
+      none = none && w != want[j];
+    const uint32_t b = static_cast<uint32_t>(key) + offset;
+    return __ballot(key != kEmptyKey && (none || !((bword >> (b & 31u)) & 1u)));
+  }
+  GGNN_DEV bool denied(const unsigned long long dl, const int k) const
+  {
+    return (__ballot(key == k) & dl) != 0ull;
+  }
+};
+
 // One candidate of a replay (simple_knn_cache.cuh:283-285): pushed if it still beats the criteria,
 // which the pushes before it may have tightened.  One-register lists take the test, and the
 // duplicate test of push(), into the masks of push_if(): the loop around this is then ONE basic block

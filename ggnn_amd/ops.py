@@ -346,6 +346,86 @@ def bf_query_labeled(base, query, k_query, labels, query_labels, measure=EUCLIDE
     return ids, dists
 
 
+MAX_LABEL_SET = 8  # GGNN_MAX_LABEL_SET
+
+
+def _need_label_sets(labels, label_sets, filter_table, filter_ids, Nq, n_min):
+    """the label-set arguments of a seam call as the C-ABI takes them: (labels ptr, n_labels, sets
+    ptr, set width, table ptr, F, n_bits, ids ptr)"""
+    _need(labels, torch.int32, "labels"), _need(label_sets, torch.int32, "label_sets")
+    if labels.dim() != 1 or labels.numel() < n_min:
+        raise ValueError("labels must be 1-dimensional with at least bit_offset + N entries")
+    if label_sets.dim() != 2 or label_sets.shape[0] != Nq or \
+            not 1 <= label_sets.shape[1] <= MAX_LABEL_SET:
+        raise ValueError(f"label_sets must be [Nq, 1..{MAX_LABEL_SET}]")
+    F = n_bits = 0
+    if filter_table is not None:
+        _need(filter_table, torch.int32, "filter_table")
+        if filter_table.dim() != 2 or filter_table.shape[0] == 0:
+            raise ValueError("filter_table must be [F, words] with F >= 1")
+        if filter_table.shape[1] * 32 < n_min:
+            raise ValueError("the rows of filter_table are shorter than bit_offset + N bits")
+        F, n_bits = filter_table.shape[0], filter_table.shape[1] * 32
+    if filter_ids is not None:
+        _need(filter_ids, torch.int32, "filter_ids")
+        if filter_ids.dim() != 1 or filter_ids.numel() != Nq:
+            raise ValueError("filter_ids must be 1-dimensional with one entry per query")
+    return (_ptr(labels), labels.numel(), _ptr(label_sets), label_sets.shape[1],
+            _ptr(filter_table), F, n_bits, _ptr(filter_ids))
+
+
+def query_labeled_in(base, query, graph0, start, nn1_stats, k_query, tau_query, labels,
+                     label_sets, filter_table=None, filter_ids=None, max_iterations=400,
+                     measure=EUCLIDEAN, bit_offset=0, shards_per_gpu=1, on_gpu_shard=0,
+                     counters=False, prescreen=None, rows_read=None):
+    """`query_labeled` with a label SET per query and, optionally, a filter id per query: labels is
+    the int32 label column over the global ids (local id i has labels[i + bit_offset]), label_sets
+    is [Nq, 1..8] int32 and query n may be given the rows whose label equals one of its entries (an
+    entry -1 admits every label; entries may repeat) AND whose bit i + bit_offset of row
+    filter_ids[n] of filter_table is set -- id -1 admits every row, any other id outside [0, F)
+    none.  filter_ids=None: labels only (filter_table is then not read)."""
+    _need(base, name="base"), _need(query, base.dtype, "query")
+    _need(graph0, torch.int32, "graph0"), _need(start, torch.int32, "start")
+    _need(nn1_stats, torch.float32, "nn1_stats")
+    Nq = query.shape[0]
+    tail = _need_label_sets(labels, label_sets, filter_table, filter_ids, Nq,
+                            bit_offset + base.shape[0])
+    ids = torch.empty((Nq, k_query * shards_per_gpu), dtype=torch.int32, device=base.device)
+    dists = torch.empty((Nq, k_query * shards_per_gpu), dtype=torch.float32, device=base.device)
+    nd = npop = None
+    if counters:
+        nd = torch.zeros(Nq, dtype=torch.int32, device=base.device)
+        npop = torch.zeros(Nq, dtype=torch.int32, device=base.device)
+    codes, params = prescreen if prescreen is not None else (None, None)
+    if prescreen is not None:
+        _need(base, torch.float32, "base"), _need(codes, torch.uint8, "codes")
+        _need(params, torch.float32, "params")
+    check(lib().ggnn_op_query_labeled_in(
+        _ptr(base), _dtype_code(base), base.shape[0], base.shape[1], _ptr(codes), _ptr(params),
+        _ptr(query), Nq, _ptr(graph0), graph0.shape[1], _ptr(start), start.numel(),
+        _ptr(nn1_stats), k_query, tau_query, max_iterations, measure, shards_per_gpu,
+        on_gpu_shard, _ptr(ids), _ptr(dists), _ptr(nd), _ptr(npop), _ptr(rows_read),
+        *tail, bit_offset, _stream()))
+    if counters:
+        return ids, dists, nd, npop
+    return ids, dists
+
+
+def bf_query_labeled_in(base, query, k_query, labels, label_sets, filter_table=None,
+                        filter_ids=None, measure=EUCLIDEAN, bit_offset=0):
+    """`bf_query_filtered` under label sets (see query_labeled_in); always the scan kernels"""
+    _need(base, name="base"), _need(query, base.dtype, "query")
+    Nq = query.shape[0]
+    tail = _need_label_sets(labels, label_sets, filter_table, filter_ids, Nq,
+                            bit_offset + base.shape[0])
+    ids = torch.empty((Nq, k_query), dtype=torch.int32, device=base.device)
+    dists = torch.empty((Nq, k_query), dtype=torch.float32, device=base.device)
+    check(lib().ggnn_op_bf_query_labeled_in(
+        _ptr(base), _dtype_code(base), base.shape[0], base.shape[1], _ptr(query), Nq, k_query,
+        measure, _ptr(ids), _ptr(dists), *tail, bit_offset, _stream()))
+    return ids, dists
+
+
 def pack_filters(masks):
     """[F, N] boolean CUDA masks -> [F, ceil(N / 32)] int32 bitset words on the same GPU (bit
     i & 31 of word i >> 5 is mask i; padding bits zero)"""

@@ -169,6 +169,52 @@ class GGNN {
     return r;
   }
 
+  // Label sets (ggnn_query_labeled_in): a resident int32 label per base vector (setLabels) and,
+  // optionally, a resident filter table (setFilters: [num_filters x ceil(N / 32)] words).  Query n
+  // is given the base vectors whose label equals one of label_sets[n * set_width + j], 1 <=
+  // set_width <= GGNN_MAX_LABEL_SET (an entry -1 accepts every label), AND whose bit is set in row
+  // filter_ids[n] of the table (-1: every vector; filter_ids == nullptr: no bitset).  Host memory.
+  virtual void setLabels(const int32_t* labels, const uint64_t n)
+  {
+    detail::check(ggnn_set_labels(h_, labels, n, GGNN_CPU, 0), h_);
+  }
+  virtual void setFilters(const uint32_t* bits, const uint32_t num_filters, const uint64_t n_bits)
+  {
+    detail::check(ggnn_set_filters(h_, bits, num_filters, n_bits, GGNN_CPU, 0), h_);
+  }
+  [[nodiscard]] virtual Results queryLabeledIn(
+      const GenericDataset& query, const uint32_t KQuery, const float tau_query,
+      const int32_t* label_sets, const uint32_t set_width, const int32_t* filter_ids = nullptr,
+      const uint32_t max_iterations = 400,
+      const DistanceMeasure measure = DistanceMeasure::Euclidean)
+  {
+    const uint32_t width = on_gpu_ ? KQuery * num_shards() : KQuery;
+    Results r = make_results(query, width);
+    detail::check(
+        ggnn_query_labeled_in(h_, query.raw(), query.N, query.D, dtype_of(query), loc_of(query),
+                              query.gpu_id, KQuery, tau_query, max_iterations,
+                              static_cast<ggnn_measure>(measure), r.ids.data(), r.dists.data(),
+                              on_gpu_ ? GGNN_GPU : GGNN_CPU, label_sets, set_width, GGNN_CPU, 0,
+                              filter_ids, GGNN_CPU, 0),
+        h_);
+    return r;
+  }
+  [[nodiscard]] virtual Results bfQueryLabeledIn(
+      const GenericDataset& query, const int32_t* label_sets, const uint32_t set_width,
+      const int32_t* filter_ids = nullptr, const uint32_t KGT = 100,
+      const DistanceMeasure measure = DistanceMeasure::Euclidean)
+  {
+    Results r = make_results(query, KGT);
+    detail::check(
+        ggnn_bf_query_labeled_in(h_, query.raw(), query.N, query.D, dtype_of(query),
+                                 loc_of(query), query.gpu_id, KGT,
+                                 static_cast<ggnn_measure>(measure), r.ids.data(), r.dists.data(),
+                                 on_gpu_ ? GGNN_GPU : GGNN_CPU, label_sets, set_width, GGNN_CPU, 0,
+                                 filter_ids, GGNN_CPU, 0),
+        h_);
+    return r;
+  }
+
   [[nodiscard]] virtual const Graph& getGraph(const uint32_t global_shard_id = 0)
   {
     ggnn_graph_view v{};

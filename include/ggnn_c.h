@@ -229,8 +229,8 @@ ggnn_status ggnn_query_async_filtered_by(ggnn_t* h, const void* query, uint64_t 
  * counters), the result of ggnn_query_filtered / ggnn_bf_query_filtered of that query with the
  * bitset (labels == L); label -1 searches unfiltered (ggnn_query / ggnn_bf_query), whatever the
  * base labels are.  There is no invalid label value: a label that no row carries gives an empty
- * result, every slot (-1 + id offset, +inf).  Labels are int32 only and a query selects by
- * equality only.
+ * result, every slot (-1 + id offset, +inf).  Labels are int32 only; a query selects by equality
+ * here and by membership in a small set below (*_labeled_in).
  *
  * ggnn_set_labels COPIES labels[n] (int32 over the global base ids, from the host or from GPU
  * gpu_id; n must equal the base's N: GGNN_INVALID_ARGUMENT otherwise, GGNN_INVALID_STATE before
@@ -245,7 +245,7 @@ ggnn_status ggnn_query_async_filtered_by(ggnn_t* h, const void* query, uint64_t 
  *
  * The *_labeled calls are the *_filtered_by calls with query_labels[Nq] in place of filter_ids --
  * the same memory rules, nothing is validated because every value is valid -- and
- * GGNN_INVALID_STATE without labels.  Labels and a bitset cannot be combined in one call. */
+ * GGNN_INVALID_STATE without labels.  These calls take no bitset: see *_labeled_in. */
 ggnn_status ggnn_set_labels(ggnn_t* h, const int32_t* labels, uint64_t n, ggnn_location location,
                             int gpu_id);
 ggnn_status ggnn_update_labels(ggnn_t* h, const int64_t* ids, const int32_t* values,
@@ -268,6 +268,52 @@ ggnn_status ggnn_query_async_labeled(ggnn_t* h, const void* query, uint64_t Nq, 
                                      float tau_query, uint32_t max_iterations,
                                      ggnn_measure measure, int32_t* ids_out, float* dists_out,
                                      uint32_t slot, const int32_t* query_labels);
+
+/* Label sets: "any of these labels", combined with a filter id.
+ * Query n carries a label SET -- row n of query_label_sets[Nq x set_width], 1 <= set_width <=
+ * GGNN_MAX_LABEL_SET -- and, optionally, a filter id filter_ids[n] into the resident filter table
+ * of ggnn_set_filters (the whole array may be null).  Base vector i may be reported to query n iff
+ *   labels[i] equals at least one entry of the set, or some entry of the set is -1 (the wildcard of
+ *   ggnn_query_labeled; entries may repeat, so a short set is padded by repeating an entry; every
+ *   other value is valid and only compared, never used as an index), AND
+ *   the filter id admits i under the rules of ggnn_query_filtered_by: -1 or a null array admits
+ *   every vector, an id in [0, num_filters) needs the vector's bit in that row, any other id
+ *   admits none.
+ * Query n gives, bit for bit (ids, distances, counters), the result of ggnn_query_filtered /
+ * ggnn_bf_query_filtered of that query with the bitset isin(labels, set n) & row(filter_ids[n]);
+ * an empty predicate gives every slot (-1 + id offset, +inf).  set_width 1 with null ids is
+ * ggnn_query_labeled, an all -1 set with ids is ggnn_query_filtered_by.
+ * The sets follow the memory rules of query_labels in the *_labeled calls and the ids those of
+ * filter_ids in the *_filtered_by calls (ggnn_query_async_labeled_in: both live where the query
+ * lives and are not read on the host).  GGNN_INVALID_ARGUMENT for a set_width outside [1, 8], a
+ * null set array and host-resident ids outside [-1, num_filters); GGNN_INVALID_STATE without
+ * labels, and with ids but no filter table; GGNN_UNSUPPORTED on an int8 base and for shards of more
+ * than 2^30 vectors.  Everything else is ggnn_query / ggnn_bf_query.  ggnn_bf_query_labeled_in
+ * always runs the scan kernels: ggnn_last_bf_query_matrix_path reports 0.
+ * What remains: at most 8 labels per query, int32 labels only, no int8 rows, no matrix-core path. */
+#define GGNN_MAX_LABEL_SET 8
+ggnn_status ggnn_query_labeled_in(ggnn_t* h, const void* query, uint64_t Nq, uint32_t D,
+                                  ggnn_dtype dtype, ggnn_location location, int gpu_id,
+                                  uint32_t k_query, float tau_query, uint32_t max_iterations,
+                                  ggnn_measure measure, int32_t* ids_out, float* dists_out,
+                                  ggnn_location out_location, const int32_t* query_label_sets,
+                                  uint32_t set_width, ggnn_location sets_location, int sets_gpu_id,
+                                  const int32_t* filter_ids, ggnn_location ids_location,
+                                  int ids_gpu_id);
+ggnn_status ggnn_bf_query_labeled_in(ggnn_t* h, const void* query, uint64_t Nq, uint32_t D,
+                                     ggnn_dtype dtype, ggnn_location location, int gpu_id,
+                                     uint32_t k_gt, ggnn_measure measure, int32_t* ids_out,
+                                     float* dists_out, ggnn_location out_location,
+                                     const int32_t* query_label_sets, uint32_t set_width,
+                                     ggnn_location sets_location, int sets_gpu_id,
+                                     const int32_t* filter_ids, ggnn_location ids_location,
+                                     int ids_gpu_id);
+ggnn_status ggnn_query_async_labeled_in(ggnn_t* h, const void* query, uint64_t Nq, uint32_t D,
+                                        ggnn_dtype dtype, int gpu_id, uint32_t k_query,
+                                        float tau_query, uint32_t max_iterations,
+                                        ggnn_measure measure, int32_t* ids_out, float* dists_out,
+                                        uint32_t slot, const int32_t* query_label_sets,
+                                        uint32_t set_width, const int32_t* filter_ids);
 
 /* layout of one graph shard, include/ggnn/base/graph_config.h:31-112 */
 typedef struct {
@@ -581,7 +627,36 @@ ggnn_status ggnn_op_bf_query_labeled(const void* base, ggnn_dtype dtype, uint32_
                                      const int32_t* labels, uint64_t n_labels,
                                      const int32_t* query_labels, uint32_t filter_bit_offset,
                                      void* stream);
-/* The three filtered brute-force calls above, reporting how they ran (modelled on
+/* ggnn_op_query_labeled / ggnn_op_bf_query_labeled with a label SET per query and an optional
+ * filter table (all device memory): query_label_sets is int32 [Nq x set_width], 1 <= set_width <=
+ * GGNN_MAX_LABEL_SET; local id i may be given to query n iff labels[i + filter_bit_offset] equals
+ * one of the set's entries (or one of them is -1) AND filter_ids[n] admits it -- -1: every id, f in
+ * [0, num_filters): bit i + filter_bit_offset of row f, anything else: none.  filter_ids may be
+ * NULL (labels only) and so may filter_table with num_filters == 0 (then an id is -1 or admits
+ * nothing); n_bits >= filter_bit_offset + N_base when there is a table.  No int8 rows
+ * (GGNN_UNSUPPORTED); ggnn_op_bf_query_labeled_in always runs the scan kernels. */
+ggnn_status ggnn_op_query_labeled_in(const void* base, ggnn_dtype dtype, uint32_t N_base,
+                                     uint32_t D, const uint8_t* codes, const float* params,
+                                     const void* query, uint32_t Nq, const int32_t* graph0,
+                                     uint32_t KBuild, const int32_t* start, uint32_t num_start,
+                                     const float* nn1_stats, uint32_t k_query, float tau_query,
+                                     uint32_t max_iterations, ggnn_measure measure,
+                                     uint32_t shards_per_gpu, uint32_t on_gpu_shard, int32_t* ids,
+                                     float* dists, uint32_t* n_dist, uint32_t* n_pop,
+                                     uint32_t* n_rows, const int32_t* labels, uint64_t n_labels,
+                                     const int32_t* query_label_sets, uint32_t set_width,
+                                     const uint32_t* filter_table, uint32_t num_filters,
+                                     uint64_t n_bits, const int32_t* filter_ids,
+                                     uint32_t filter_bit_offset, void* stream);
+ggnn_status ggnn_op_bf_query_labeled_in(const void* base, ggnn_dtype dtype, uint32_t N_base,
+                                        uint32_t D, const void* query, uint32_t Nq,
+                                        uint32_t k_query, ggnn_measure measure, int32_t* ids,
+                                        float* dists, const int32_t* labels, uint64_t n_labels,
+                                        const int32_t* query_label_sets, uint32_t set_width,
+                                        const uint32_t* filter_table, uint32_t num_filters,
+                                        uint64_t n_bits, const int32_t* filter_ids,
+                                        uint32_t filter_bit_offset, void* stream);
+/* ggnn_op_bf_query_filtered, _filtered_by and _labeled, reporting how they ran (modelled on
  * ggnn_op_bf_query_certified): *n_rescanned (DEVICE memory, may be NULL) receives the number of
  * queries the matrix-core pre-selection could not certify and the filtered scan answered instead;
  * *matrix_path (HOST memory, may be NULL) is set before the call returns to 1 if the launch ran

@@ -36,7 +36,15 @@ The filtered brute force alone (no graph is built): on one handle, alternating p
 time of each call under hook BF_SCAN = 1 (the scan kernels) and without it (the matrix-core tile
 kernels where the dispatch takes them), every repeat listed, with the path and the rescanned
 count of the matrix run: the unfiltered call, the per-call bitset at 100 / 50 / 10 / 1 % allowed,
-the --tenants-row and --big-table-row filter tables, and the same tenant counts as labels."""
+the --tenants-row and --big-table-row filter tables, and the same tenant counts as labels.
+
+    python scripts/filtered_bench.py --label-sets [--tenants 16]
+
+Label sets (`query_labeled_in`) against `query_labeled` on the same handle, graph and predicate:
+--tenants disjoint tenants, one label per query, width 1 and no filter ids; kernel ms of both calls,
+alternating, every repeat listed.  Then one row for width 8 (eight of the tenants per query) with a
+50 % bitset as the one row of the filter table, next to `query_filtered_by` of the bitset alone (a
+wider predicate: the figure says what a search under the bitset costs, not what the label read adds)."""
 import argparse
 import json
 import os
@@ -64,6 +72,7 @@ def main():
     ap.add_argument("--labels", action="store_true")
     ap.add_argument("--label-tenants", type=int, nargs="+", default=[16, 1024])
     ap.add_argument("--bf", action="store_true")
+    ap.add_argument("--label-sets", action="store_true")
     a = ap.parse_args()
     rs = np.random.default_rng(1)
     centres = rs.normal(size=(256, a.d)).astype(np.float32) * 2
@@ -81,6 +90,9 @@ def main():
         return
     if a.labels:
         labeled(a, g, q)
+        return
+    if a.label_sets:
+        label_sets(a, g, q)
         return
 
     def timed(fn):
@@ -289,6 +301,47 @@ def labeled(a, g, q):
               flush=True)
         g.set_filters(None)
         g.set_labels(None)
+
+
+def label_sets(a, g, q):
+    T = a.tenants
+    rs = np.random.default_rng(T)
+    tenant = torch.from_numpy((rs.permutation(a.n) % T).astype(np.int32)).cuda()
+    qlab = torch.from_numpy(rs.integers(0, T, a.queries).astype(np.int32)).cuda()
+    g.set_labels(tenant)
+
+    def ab(name, calls, **extra):
+        outs = {k: fn() for k, fn in calls.items()}
+        ms = {k: [] for k in calls}
+        for _ in range(a.reps):                               # alternating
+            for k, fn in calls.items():
+                fn()
+                ms[k].append(round(g.last_timing_ms()["query_ms"], 4))
+        print(json.dumps({"label_sets": name, **extra, "kernel_ms": ms}), flush=True)
+        return outs
+
+    one = qlab[:, None].contiguous()
+    o = ab("width 1, no ids", {
+        "query_labeled": lambda: g.query_labeled(q, a.k, a.tau, a.iters, labels=qlab),
+        "query_labeled_in": lambda: g.query_labeled_in(q, a.k, a.tau, a.iters, label_sets=one)},
+        tenants=T)
+    x, y = o["query_labeled"], o["query_labeled_in"]
+    assert torch.equal(x[0], y[0]) and torch.equal(x[1], y[1])
+    # width 8 with a 50 % bitset: eight distinct tenants per query
+    w = min(8, T)
+    sets = np.stack([rs.choice(T, w, replace=False) for _ in range(a.queries)]).astype(np.int32)
+    sets = torch.from_numpy(sets).cuda()
+    bits = ggnn.pack_filter(np.random.default_rng(500).random(a.n) < 0.5).cuda()
+    g.set_filters(bits[None, :])
+    zero = torch.zeros(a.queries, dtype=torch.int32, device="cuda")
+    ab(f"width {w}, 50 % bitset", {
+        "query_labeled_in": lambda: g.query_labeled_in(q, a.k, a.tau, a.iters, label_sets=sets,
+                                                       filter_ids=zero),
+        "query_filtered_by (bitset alone)": lambda: g.query_filtered_by(q, a.k, a.tau, a.iters,
+                                                                        filter_ids=zero)},
+       tenants=T, allowed_share=round(0.5 * w / T, 4))
+    g.set_filters(None)
+    g.set_labels(None)
 
 
 if __name__ == "__main__":
