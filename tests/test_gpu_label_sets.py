@@ -113,7 +113,9 @@ def test_seam_query_labeled_in(graphs, KB, K, iters):
 def test_seam_widths(graphs, variant):
     """width 1 without ids is query_labeled, width 3 equals width 8 on sets of at most three
     entries, an all -1 set with ids is query_filtered_by (ids 99 and -1 included; once more without
-    any table, where an id is -1 or admits nothing)"""
+    any table, where an id is -1 or admits nothing); every width 1 .. 8 equals width 8 padded, a set
+    whose -1 stands last of eight or in the middle is query_filtered_by, and widths and wildcard
+    once more under cosine"""
     from ggnn_amd import ops
     g, base = graphs[24], graphs["base"]
     K, tau, iters = 10, 0.6, 400
@@ -152,6 +154,49 @@ def test_seam_widths(graphs, variant):
         assert x.cpu().numpy()[sel].tobytes() == y.cpu().numpy()[sel].tobytes()
     assert (no_table[0].cpu().numpy()[~sel] == -1).all()
     assert np.isinf(no_table[1].cpu().numpy()[~sel]).all()
+    # every width 1 .. 8, on sets of at most that many entries, is width 8 padded: entry j of a set
+    # is read at [n * width + j], and the entries beyond the width repeat the first
+    pool = SETS + [[3], [-7, 2], [2, 1, 0, 3], [-7, 3, 2, 1, UNUSED], [9, 8, 7, 6, 5, 1],
+                   [9, 8, 7, 6, 5, 4, 2]]
+    assert {len(s) for s in pool} == set(range(1, 9))
+    for width in range(1, 9):
+        fit = [s for s in pool if len(s) <= width]
+        longest = [s for s in fit if len(s) == width]
+        sets = (longest + fit * nq)[:nq]                   # the sets of exactly this width first
+        for ids in (None, d_fids):
+            tab = d_table if ids is not None else None
+            w = ops.query_labeled_in(*args, d_labels, _dev(_padded(sets, width)), tab, ids, **kw)
+            w8 = ops.query_labeled_in(*args, d_labels, _dev(_padded(sets, 8)), tab, ids, **kw)
+            same(w, w8, ("width", width, ids is not None))
+            assert np.isfinite(w[1].cpu().numpy()).any(), width
+    # the wildcard last of eight and in the middle, next to labels no row carries: with ids that is
+    # query_filtered_by, whatever the other entries are
+    last = [[5000 + j for j in range(7)] + [-1]] * nq
+    middle = [[UNUSED, 1, 5002, -1, 5004, 0, INT32_MIN, 5007]] * nq
+    by_ids = ops.query_filtered_by(*args, d_table, d_fids, **kw)
+    assert np.isfinite(by_ids[1].cpu().numpy()).any()
+    for name, wild in (("last", last), ("middle", middle)):
+        same(ops.query_labeled_in(*args, d_labels, _dev(wild), d_table, d_fids,
+                                  **kw), by_ids, ("-1 " + name, "with ids"))
+    # ... and under cosine (query_labelset_kernel<.., kCos, ..> of this layout at K = 10): widths 3
+    # and 5 against width 8, the wildcard in the middle against query_filtered_by.  Graph and nn1
+    # statistics are those built for squared L2 on the unclamped base: sound only because both
+    # sides of each comparison are GPU runs on the same inputs -- no reference stands behind this
+    # block (cosine against py_query_filtered: tests/test_gpu_labelset_layout_matrix.py, width 8)
+    base_c = np.maximum(base, 1.0)                         # (no zero row)
+    c_base, c_q = _cast(base_c, variant), _cast(np.maximum(q, 1.0), variant)
+    c_args = (c_base, c_q) + args[2:]
+    c_kw = dict(kw, measure=1, prescreen=ops.prescreen_encode(c_base, 1) if variant == "f32_ps" else None)
+    for width in (3, 5):
+        fit = [s for s in pool if len(s) <= width]
+        sets = ([s for s in fit if len(s) == width] + fit * nq)[:nq]
+        w = ops.query_labeled_in(*c_args, d_labels, _dev(_padded(sets, width)), d_table, d_fids, **c_kw)
+        w8 = ops.query_labeled_in(*c_args, d_labels, _dev(_padded(sets, 8)), d_table, d_fids, **c_kw)
+        same(w, w8, ("cosine, width", width))
+        assert np.isfinite(w[1].cpu().numpy()).any()
+    same(ops.query_labeled_in(*c_args, d_labels, _dev(middle), d_table, d_fids,
+                              **c_kw),
+         ops.query_filtered_by(*c_args, d_table, d_fids, **c_kw), "cosine, -1 in the middle")
 
 
 def test_seam_shard_offset(graphs):
@@ -227,6 +272,77 @@ def test_seam_bf_query_labeled_in(orc, graphs, variant, measure):
                 assert np.array_equal(ids[i], r_ids[0]) and d[i].tobytes() == r_d[0].tobytes(), (K, i)
             if fids is None:                              # five rows, then padding
                 assert (ids[6, :5] >= 0).all() and (ids[6, 5:] == -1).all() and np.isinf(d[6, 5:]).all()
+
+
+@pytest.mark.parametrize("measure", [0, 1])
+@pytest.mark.parametrize("variant", ["f32", "u8"])
+def test_seam_bf_query_labeled_in_sliced_base(orc, variant, measure):
+    """few queries on a base large enough for several slices: with five queries launch_bf_query_labelset
+    splits 20011 rows into four slices of 5056, every (query, slice) wave reads labels and bitset
+    words from its slice's first row on, and the partial lists are merged lower slice first.  A block
+    of 40 rows is repeated across the first slice boundary (ties come out by lower base index, and
+    two queries are rows of that block), one query's rows lie in the third slice only, one query
+    admits nothing; label column and table are windows at bit offset 37.  The one-label scan
+    (ops.bf_query_labeled) runs on the same base."""
+    from ggnn_amd import ops
+    Nb, nq, off, SLICE = 20011, 5, 37, 5056
+    # launch_bf_query_labelset: below 4096 waves the base is split, into at most Nb / 4096 slices;
+    # bf_slice_rows: their rows rounded up to a multiple of 64
+    slices = min(-(-(256 * 16) // nq), max(1, Nb // 4096)) if nq < 256 * 16 else 1
+    assert slices == 4 and ((Nb + slices - 1) // slices + 63) // 64 * 64 == SLICE
+    assert -(-Nb // SLICE) == slices
+    rs = np.random.default_rng(151 + measure)
+    base = rs.integers(1, 5, (Nb, D)).astype(np.float32)        # many equal distances, no zero row
+    base[SLICE:SLICE + 40] = base[SLICE - 40:SLICE]
+    q = rs.integers(1, 5, (nq, D)).astype(np.float32)
+    q[0], q[3] = base[SLICE - 26], base[SLICE - 36]
+    labels = rs.integers(0, 4, Nb).astype(np.int32)
+    third = np.arange(Nb) // SLICE == 2
+    labels[third & (rs.random(Nb) < 0.1)] = 5                   # label 5: the third slice only
+    labels[SLICE - 40:SLICE + 40] = 0
+    table = np.stack([rs.random(Nb) < 0.3, rs.random(Nb) < 0.05])
+    table[0, SLICE - 40:SLICE + 40] = True
+    sets = [[0, 1], [5], [UNUSED, 77], [-1], [2, 5, 3]]
+    fids = np.array([0, -1, 1, -1, 1], np.int32)
+    qlabels = np.array([0, 5, UNUSED, -1, 2], np.int32)
+    allowed = _composed(labels, sets, table, fids)
+    where = [np.unique(np.nonzero(a)[0] // SLICE).tolist() for a in allowed]
+    assert where == [[0, 1, 2, 3], [2], [], [0, 1, 2, 3], [0, 1, 2, 3]]
+    wide_labels = np.concatenate([rs.integers(0, 6, off), labels, rs.integers(0, 6, 60)])
+    wide_table = rs.random((2, off + Nb + 60)) < 0.5
+    wide_table[:, off:off + Nb] = table
+    d_base, d_q = _cast(base, variant), _cast(q, variant)
+    d_sets, d_fids = _dev(_padded(sets, 8)), _dev(fids)
+    for K in (10, 300):
+        ref = [bf_filtered_reference(orc, base, q[i:i + 1], K, allowed[i], measure) for i in range(nq)]
+        r_ids, r_d = np.concatenate([r[0] for r in ref]), np.concatenate([r[1] for r in ref])
+        # both copies of the queries' own rows lead their lists, the lower slice's first
+        assert r_ids[0, :2].tolist() == [SLICE - 26, SLICE + 14] and r_d[0, 0] == r_d[0, 1]
+        assert r_ids[3, :2].tolist() == [SLICE - 36, SLICE + 4] and r_d[3, 0] == r_d[3, 1]
+        assert (r_ids[2] == -1).all() and (r_ids[1] >= 2 * SLICE).all() and (r_ids[1] < 3 * SLICE).all()
+        runs = {
+            "offset 0": ops.bf_query_labeled_in(d_base, d_q, K, _dev(labels), d_sets,
+                                                _table_bits(table), d_fids, measure),
+            "windows": ops.bf_query_labeled_in(d_base, d_q, K, _dev(wide_labels), d_sets,
+                                               _table_bits(wide_table), d_fids, measure, bit_offset=off),
+            "table of the composed masks": ops.bf_query_filtered_by(
+                d_base, d_q, K, _table_bits(allowed), _dev(np.arange(nq)), measure)}
+        for name, (ids, d) in runs.items():
+            assert np.array_equal(ids.cpu().numpy(), r_ids), (K, name)
+            assert d.cpu().numpy().tobytes() == r_d.tobytes(), (K, name)
+        # one label per query
+        one = [bf_filtered_reference(orc, base, q[i:i + 1], K,
+                                     np.ones(Nb, bool) if L == -1 else labels == L, measure)
+               for i, L in enumerate(qlabels)]
+        o_ids, o_d = np.concatenate([r[0] for r in one]), np.concatenate([r[1] for r in one])
+        assert o_ids[0, :2].tolist() == [SLICE - 26, SLICE + 14]
+        assert (o_ids[2] == -1).all() and (o_ids[1] >= 2 * SLICE).all() and (o_ids[1] < 3 * SLICE).all()
+        for name, (ids, d) in {
+                "offset 0": ops.bf_query_labeled(d_base, d_q, K, _dev(labels), _dev(qlabels), measure),
+                "window": ops.bf_query_labeled(d_base, d_q, K, _dev(wide_labels), _dev(qlabels),
+                                               measure, bit_offset=off)}.items():
+            assert np.array_equal(ids.cpu().numpy(), o_ids), (K, name, "one label")
+            assert d.cpu().numpy().tobytes() == o_d.tobytes(), (K, name, "one label")
 
 
 # ---- the handle ----------------------------------------------------------------------------------
