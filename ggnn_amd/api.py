@@ -212,6 +212,76 @@ def _label_sets(label_sets, Nq):
     return label_sets.contiguous()
 
 
+MAX_LABEL_RANGES = 4  # GGNN_MAX_LABEL_RANGES
+_EMPTY_RANGE = (1, 0)  # lo > hi: contains nothing
+
+
+def _label_ranges(label_ranges, Nq):
+    """the `label_ranges` argument as a contiguous [Nq, 1..4, 2] int32 tensor (CPU or CUDA) of closed
+    intervals (lo, hi): a 3-D int32 / int64 array or tensor is taken as it is (int64 must fit int32);
+    anything else is read as one sequence of 1..4 (lo, hi) pairs per query and padded to the longest
+    row with an empty interval"""
+    if isinstance(label_ranges, np.ndarray):
+        label_ranges = torch.from_numpy(np.ascontiguousarray(label_ranges))
+    if not isinstance(label_ranges, torch.Tensor):
+        rows = [[tuple(int(v) for v in (p.tolist() if hasattr(p, "tolist") else p)) for p in r]
+                for r in label_ranges]
+        for n, r in enumerate(rows):
+            if not 1 <= len(r) <= MAX_LABEL_RANGES:
+                raise ValueError(f"query {n} has {len(r)} label ranges: 1 to "
+                                 f"{MAX_LABEL_RANGES} are allowed")
+            if any(len(p) != 2 for p in r):
+                raise ValueError(f"the label ranges of query {n} must be (lo, hi) pairs")
+        width = max((len(r) for r in rows), default=1)
+        label_ranges = torch.tensor([r + [_EMPTY_RANGE] * (width - len(r)) for r in rows],
+                                    dtype=torch.int64).reshape(len(rows), width, 2)
+    if label_ranges.dim() != 3 or label_ranges.shape[2] != 2:
+        raise TypeError("label_ranges must be [Nq, R, 2], or a sequence of per-query sequences of "
+                        "(lo, hi) pairs")
+    if label_ranges.dtype not in (torch.int32, torch.int64):
+        raise TypeError("label_ranges must be int32 (or int64 with values that fit int32)")
+    if label_ranges.shape[0] != Nq:
+        raise ValueError(f"label_ranges needs one row per query ({Nq})")
+    if not 1 <= label_ranges.shape[1] <= MAX_LABEL_RANGES:
+        raise ValueError(f"a query has 1 to {MAX_LABEL_RANGES} label ranges, not "
+                         f"{label_ranges.shape[1]}")
+    if label_ranges.dtype == torch.int64:
+        if label_ranges.numel() and (int(label_ranges.min()) < _INT32_MIN or
+                                     int(label_ranges.max()) > _INT32_MAX):
+            raise ValueError("label_ranges has values outside the int32 range")
+        label_ranges = label_ranges.to(torch.int32)
+    return label_ranges.contiguous()
+
+
+def ordered_int32(x):
+    """float32 values (array, tensor or scalar) as int32 values in the same order, for a float
+    attribute -- a price, a float timestamp -- in the int32 label column:
+
+        eng.set_labels(ordered_int32(price))
+        eng.query_labeled_range(q, 10, 0.5, label_ranges=[[(ordered_int32(lo), ordered_int32(hi))]])
+
+    a < b iff ordered_int32(a) < ordered_int32(b): the bits b of the float become
+    b ^ ((b >> 31) & 0x7fffffff) (arithmetic shift), -0.0 counts as +0.0, -inf / +inf map to the
+    outermost values used, and NaN is a ValueError.  An array gives an int32 array, a tensor an int32
+    tensor on the same device, a scalar an int."""
+    if isinstance(x, torch.Tensor):
+        if x.dtype != torch.float32:
+            raise TypeError("ordered_int32 takes float32 values")
+        if bool(torch.isnan(x).any()):
+            raise ValueError("ordered_int32: NaN has no place in the order")
+        b = (x + 0.0).contiguous().view(torch.int32)  # (-0.0 + 0.0 is +0.0)
+        return b ^ ((b >> 31) & 0x7fffffff)
+    a = np.asarray(x)
+    if a.dtype != np.float32 and a.ndim:
+        raise TypeError("ordered_int32 takes float32 values")
+    a = a.astype(np.float32)
+    if np.isnan(a).any():
+        raise ValueError("ordered_int32: NaN has no place in the order")
+    b = np.ascontiguousarray(np.atleast_1d(a) + np.float32(0.0)).view(np.int32)
+    out = b ^ ((b >> 31) & np.int32(0x7fffffff))
+    return out.reshape(a.shape) if a.ndim else int(out[0])
+
+
 def _filter_words(filter, N):
     """the `filter` argument of query_filtered / bf_query_filtered as a contiguous int32 tensor of
     ceil(N / 32) words (CPU or CUDA): a boolean mask of length N is packed on the host, an
@@ -344,12 +414,15 @@ class QueryTicket:
     """Result of `GGNN.query_async`: `ids, dists = ticket` works as before; `query` keeps the
     input alive (and `filter_ids` the filter ids, or the query labels, of a batch that has some);
     `done` is set by `synchronize()`."""
-    __slots__ = ("query", "ids", "dists", "slot", "done", "filter_ids", "label_sets")
+    __slots__ = ("query", "ids", "dists", "slot", "done", "filter_ids", "label_sets",
+                 "label_ranges")
 
-    def __init__(self, query, ids, dists, slot, filter_ids=None, label_sets=None):
+    def __init__(self, query, ids, dists, slot, filter_ids=None, label_sets=None,
+                 label_ranges=None):
         self.query, self.ids, self.dists, self.slot, self.done = query, ids, dists, slot, False
         self.filter_ids = filter_ids
         self.label_sets = label_sets
+        self.label_ranges = label_ranges
 
     def __iter__(self):
         return iter((self.ids, self.dists))
@@ -595,7 +668,8 @@ class GGNN:
                               self._where(ql))
 
     def _labeled_in_tail(self, ls, fi):
-        """the filter arguments of the *_labeled_in calls: the sets, then the ids (or null)"""
+        """the filter arguments of the *_labeled_in / *_labeled_range calls: the sets (or ranges:
+        shape[1] is their number either way), then the ids (or null)"""
         ids = self._where(fi) if fi is not None else (None, _lib.CPU, 0)
         return (ls.data_ptr(), ls.shape[1], *_loc(ls), *ids)
 
@@ -632,6 +706,44 @@ class GGNN:
         fi = None if filter_ids is None else _filter_ids(filter_ids, t.shape[0])
         return self._blocking(lib().ggnn_bf_query_labeled_in, t, (int(k_gt), int(measure)),
                               self._labeled_in_tail(ls, fi))
+
+    def query_labeled_range(self, query, k_query, tau_query, max_iterations=400,
+                            measure=DistanceMeasure.Euclidean, label_ranges=None, filter_ids=None):
+        """Extension: `query` under label RANGES (`set_labels`), combined with a filter id per
+        query (`set_filters`).  `label_ranges`: for every query up to 4 closed intervals (lo, hi) of
+        int32 labels -- a 3-D int32 / int64 array or tensor [Nq, 1..4, 2], CPU or GPU, or a sequence
+        of per-query sequences of 1 to 4 pairs (padded with an empty interval; an empty or longer
+        row is a ValueError).  Query n is given base vectors whose label lies in one of its
+        intervals, compared as signed int32 -- lo > hi is an empty interval, and there is no
+        wildcard: -1 is an ordinary label, (-2**31, 2**31 - 1) admits every label -- AND that row
+        `filter_ids[n]` of the filter table allows (`filter_ids` as in `query_filtered_by`; `None`:
+        no bitset) -- bit for bit `query_filtered` with the mask
+        `any_j(lo_j <= base_labels <= hi_j) & table[filter_ids[n]]`.  `label_ranges=None` is no
+        label restriction (`query_filtered_by`); both `None` is `query`.  Float attributes:
+        `ordered_int32`."""
+        if label_ranges is None:
+            return self.query_filtered_by(query, k_query, tau_query, max_iterations, measure,
+                                          filter_ids=filter_ids)
+        t = _as_tensor(query, what="query")
+        lr = _label_ranges(label_ranges, t.shape[0])
+        fi = None if filter_ids is None else _filter_ids(filter_ids, t.shape[0])
+        return self._blocking(lib().ggnn_query_labeled_range, t,
+                              self._search(k_query, tau_query, max_iterations, measure),
+                              self._labeled_in_tail(lr, fi), self._shards)
+
+    def bf_query_labeled_range(self, query, k_gt=100, measure=DistanceMeasure.Euclidean,
+                               label_ranges=None, filter_ids=None):
+        """Extension: the exact `k_gt` nearest among the base vectors `label_ranges` and
+        `filter_ids` admit (see `query_labeled_range`); slots beyond their number are (-1, +inf).
+        Always the scan kernels.  `label_ranges=None` is `bf_query_filtered_by`; both `None` is
+        `bf_query`."""
+        if label_ranges is None:
+            return self.bf_query_filtered_by(query, k_gt, measure, filter_ids=filter_ids)
+        t = _as_tensor(query, what="query")
+        lr = _label_ranges(label_ranges, t.shape[0])
+        fi = None if filter_ids is None else _filter_ids(filter_ids, t.shape[0])
+        return self._blocking(lib().ggnn_bf_query_labeled_range, t, (int(k_gt), int(measure)),
+                              self._labeled_in_tail(lr, fi))
 
     def query_filtered(self, query, k_query, tau_query, max_iterations=400,
                        measure=DistanceMeasure.Euclidean, filter=None):
@@ -726,13 +838,24 @@ class GGNN:
         return self._query_async(query, k_query, tau_query, max_iterations, measure, slot,
                                  filter_ids, None, label_sets)
 
+    def query_async_labeled_range(self, query, k_query, tau_query, max_iterations=400,
+                                  measure=DistanceMeasure.Euclidean, slot=0, label_ranges=None,
+                                  filter_ids=None):
+        """Extension: `query_async` under label ranges and filter ids (`query_labeled_range`), both
+        with the memory and lifetime rules of the `filter_ids` of `query_async` (kept alive on the
+        ticket: `ticket.filter_ids`, `ticket.label_ranges`).  `label_ranges=None` is
+        `query_async`."""
+        return self._query_async(query, k_query, tau_query, max_iterations, measure, slot,
+                                 filter_ids, None, None, label_ranges)
+
     def _query_async(self, query, k_query, tau_query, max_iterations, measure, slot, filter_ids,
-                     labels, label_sets=None):
+                     labels, label_sets=None, label_ranges=None):
         t = _as_tensor(query, what="query")
         fi = None if filter_ids is None else _filter_ids(filter_ids, t.shape[0])
         if labels is not None:
             fi = _labels(labels, t.shape[0], per="query")
         ls = None if label_sets is None else _label_sets(label_sets, t.shape[0])
+        lr = None if label_ranges is None else _label_ranges(label_ranges, t.shape[0])
 
         def follow(x, pinned):
             # sets and ids follow the query's memory rule: its GPU, or page-locked host memory
@@ -747,7 +870,7 @@ class GGNN:
             # engine's copies stay asynchronous
             if not t.is_cuda and not t.is_pinned():
                 t = t.pin_memory()
-            fi, ls = follow(fi, True), follow(ls, True)
+            fi, ls, lr = follow(fi, True), follow(ls, True), follow(lr, True)
             dev = t.device.index if t.is_cuda else -1
             if t.is_cuda:
                 ids, dists = self._out(t.shape[0], int(k_query), True, t.device)
@@ -759,16 +882,20 @@ class GGNN:
             if not t.is_cuda:
                 raise RuntimeError("query_async needs the query on the GPU")
             loc, dev = _loc(t)
-            fi, ls = follow(fi, False), follow(ls, False)
+            fi, ls, lr = follow(fi, False), follow(ls, False), follow(lr, False)
             ids, dists = self._out(t.shape[0], int(k_query) * self._shards, True, t.device)
-        if ls is not None:
-            for x in (ls, fi):
+        if ls is not None or lr is not None:
+            # (sets or ranges: [Nq, width] / [Nq, n_ranges, 2], the same argument list)
+            rows = ls if lr is None else lr
+            call = (lib().ggnn_query_async_labeled_in if lr is None
+                    else lib().ggnn_query_async_labeled_range)
+            for x in (rows, fi):
                 if x is not None and x.is_cuda:
                     torch.cuda.current_stream(x.device).synchronize()
-            self._check(lib().ggnn_query_async_labeled_in(
+            self._check(call(
                 self._h, t.data_ptr(), t.shape[0], t.shape[1], _dtype_code(t), dev, int(k_query),
                 float(tau_query), int(max_iterations), int(measure), ids.data_ptr(),
-                dists.data_ptr(), int(slot), ls.data_ptr(), ls.shape[1],
+                dists.data_ptr(), int(slot), rows.data_ptr(), rows.shape[1],
                 None if fi is None else fi.data_ptr()))
         elif fi is not None:
             if fi.is_cuda:
@@ -784,7 +911,7 @@ class GGNN:
                                                _dtype_code(t), dev, int(k_query), float(tau_query),
                                                int(max_iterations), int(measure), ids.data_ptr(),
                                                dists.data_ptr(), int(slot)))
-        ticket = QueryTicket(t, ids, dists, int(slot), fi, ls)
+        ticket = QueryTicket(t, ids, dists, int(slot), fi, ls, lr)
         held = self._inflight.setdefault(int(slot) % _ASYNC_SLOTS, [])
         if len(held) >= _MAX_TICKETS_PER_SLOT:
             # a serving loop that waits some other way (its own events, torch.cuda.synchronize)

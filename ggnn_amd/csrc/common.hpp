@@ -156,6 +156,17 @@ struct LabelSetSpec {
   const int32_t* sets{nullptr};    // [Nq x width] (device)
   uint32_t width{0};               // 1 .. 8 (GGNN_MAX_LABEL_SET)
 };
+// Label ranges (with a label column): query n carries n_ranges <= 4 closed intervals of signed int32
+// labels, (ranges[(n * n_ranges + j) * 2], ranges[(n * n_ranges + j) * 2 + 1]) = (lo, hi), and a base
+// vector may be given to it iff lo <= its label <= hi for at least one of them.  lo > hi is an empty
+// interval; there is no wildcard value (-1 is an ordinary label); every int32 value is a valid bound.
+// A launch with labels != nullptr is a label-range launch; filter_bits, filter_table.ids and
+// filter_bit_offset are what they are under LabelSetSpec.
+struct LabelRangeSpec {
+  const int32_t* labels{nullptr};  // [>= offset + N_base] (device)
+  const int32_t* ranges{nullptr};  // [Nq x n_ranges x 2] (device)
+  uint32_t n_ranges{0};            // 1 .. 4 (GGNN_MAX_LABEL_RANGES)
+};
 // the two constant rows for a launch that was given none (null if ids is null); free with
 // scratch_free(p, stream) after the launch
 uint32_t* filter_consts_scratch(const FilterTable& t, hipStream_t stream);
@@ -195,6 +206,8 @@ struct QueryLaunch {
   FilterTable filter_table{};
   // label-set filters (labels != nullptr: see LabelSetSpec)
   LabelSetSpec label_sets{};
+  // label-range filters (labels != nullptr: see LabelRangeSpec)
+  LabelRangeSpec label_ranges{};
 };
 void launch_query(const QueryLaunch& a, hipStream_t stream);
 
@@ -248,6 +261,8 @@ struct BfLaunch {
   int* matrix_path{nullptr};
   // label-set filters (labels != nullptr: see LabelSetSpec); always the scan
   LabelSetSpec label_sets{};
+  // label-range filters (labels != nullptr: see LabelRangeSpec); always the scan
+  LabelRangeSpec label_ranges{};
 };
 void launch_bf_query(const BfLaunch& a, hipStream_t stream);
 

@@ -77,6 +77,7 @@ QueryLaunch ggnn_handle::shard_launch(const DeviceCtx& ctx, uint32_t si, const Q
   ql.filter_bit_offset = sh.global_id * cfg.N;
   ql.filter_table = df.table;
   ql.label_sets = df.set;
+  ql.label_ranges = df.ranges;
   return ql;
 }
 
@@ -525,6 +526,7 @@ void ggnn_handle::bf_query(const QueryRequest& r, const QueryFilter& filter)
   bl.filter_bits = df.bits;
   bl.filter_table = df.table;
   bl.label_sets = df.set;
+  bl.label_ranges = df.ranges;
   // (one launch over the whole base: "every shard" is this launch)
   last_bf_matrix_path = 0;
   bl.matrix_path = &last_bf_matrix_path;
@@ -605,13 +607,39 @@ QueryFilter QueryFilter::label_sets(const ggnn_handle& h, const int32_t* sets, u
   return f;
 }
 
-// label sets: the resident column and (with filter ids) the resident table; the sets and the ids
-// are used in place on their own GPU, else staged behind one another in the lane's id stage
-DeviceFilter ggnn_handle::resolve_label_sets(DeviceCtx& ctx, const QueryFilter& f, int lane)
+QueryFilter QueryFilter::label_ranges(const ggnn_handle& h, const int32_t* ranges,
+                                      uint32_t n_ranges, uint64_t Nq, ggnn_location loc, int gpu,
+                                      const int32_t* ids, ggnn_location ids_loc, int ids_gpu,
+                                      bool read_host_ids)
+{
+  GGNN_REQUIRE(n_ranges >= 1 && n_ranges <= GGNN_MAX_LABEL_RANGES, GGNN_INVALID_ARGUMENT,
+               "n_ranges " + std::to_string(n_ranges) + " is outside [1, " +
+                   std::to_string(GGNN_MAX_LABEL_RANGES) + "]");
+  GGNN_REQUIRE(ranges != nullptr, GGNN_INVALID_ARGUMENT, "the label range array is null");
+  GGNN_REQUIRE(!h.labels_host.empty(), GGNN_INVALID_STATE,
+               "There are no labels the label ranges could refer to (ggnn_set_labels).");
+  QueryFilter f{LabelRanges, ranges, Nq * n_ranges * 2, loc, gpu};
+  f.width = n_ranges;
+  if (ids) {
+    // (the rules of the filter ids of ggnn_query_filtered_by)
+    const QueryFilter t = table_ids(h, ids, Nq, ids_loc, ids_gpu, read_host_ids);
+    f.ids = ids;
+    f.ids_loc = t.loc;
+    f.ids_gpu = t.gpu;
+  }
+  GGNN_REQUIRE(h.base_dtype != GGNN_I8, GGNN_UNSUPPORTED,
+               "label ranges are not built for int8 bases");
+  return f;
+}
+
+// label sets and label ranges -- a per-query int32 array of f.stride() words, plus optional ids: the
+// resident column and (with filter ids) the resident table; the rows and the ids are used in place
+// on their own GPU, else staged behind one another in the lane's id stage
+DeviceFilter ggnn_handle::resolve_label_rows(DeviceCtx& ctx, const QueryFilter& f, int lane,
+                                             const int32_t*& column, const int32_t*& rows)
 {
   DeviceFilter d;
-  d.set.labels = place_labels(ctx);
-  d.set.width = f.width;
+  column = place_labels(ctx);
   if (f.ids) {
     d.bits = place_filter_table(ctx);
     d.table.words = filter_words;
@@ -622,7 +650,7 @@ DeviceFilter ggnn_handle::resolve_label_sets(DeviceCtx& ctx, const QueryFilter& 
     return loc == GGNN_GPU && gpu == ctx.device && (reinterpret_cast<uintptr_t>(p) & 3u) == 0;
   };
   const size_t set_bytes = static_cast<size_t>(f.count) * 4;
-  const size_t id_bytes = f.ids ? static_cast<size_t>(f.count / f.width) * 4 : 0;
+  const size_t id_bytes = f.ids ? static_cast<size_t>(f.count / f.stride()) * 4 : 0;
   const bool stage_sets = !in_place(f.ptr, f.loc, f.gpu);
   const bool stage_ids = f.ids && !in_place(f.ids, f.ids_loc, f.ids_gpu);
   DeviceBuffer& stage = blocking ? ctx.filter_ids_stage : ctx.xb[lane].f_stage;
@@ -643,9 +671,25 @@ DeviceFilter ggnn_handle::resolve_label_sets(DeviceCtx& ctx, const QueryFilter& 
     at += n;
     return r;
   };
-  d.set.sets = static_cast<const int32_t*>(here(f.ptr, stage_sets, set_bytes, f.loc));
+  rows = static_cast<const int32_t*>(here(f.ptr, stage_sets, set_bytes, f.loc));
   if (f.ids)
     d.table.ids = static_cast<const int32_t*>(here(f.ids, stage_ids, id_bytes, f.ids_loc));
+  return d;
+}
+
+DeviceFilter ggnn_handle::resolve_label_sets(DeviceCtx& ctx, const QueryFilter& f, int lane)
+{
+  const int32_t *column = nullptr, *rows = nullptr;
+  DeviceFilter d = resolve_label_rows(ctx, f, lane, column, rows);
+  d.set = LabelSetSpec{column, rows, f.width};
+  return d;
+}
+
+DeviceFilter ggnn_handle::resolve_label_ranges(DeviceCtx& ctx, const QueryFilter& f, int lane)
+{
+  const int32_t *column = nullptr, *rows = nullptr;
+  DeviceFilter d = resolve_label_rows(ctx, f, lane, column, rows);
+  d.ranges = LabelRangeSpec{column, rows, f.width};
   return d;
 }
 
@@ -656,6 +700,8 @@ DeviceFilter ggnn_handle::resolve_filter(DeviceCtx& ctx, const QueryFilter& f, i
     return d;
   if (f.kind == QueryFilter::LabelSets)
     return resolve_label_sets(ctx, f, lane);
+  if (f.kind == QueryFilter::LabelRanges)
+    return resolve_label_ranges(ctx, f, lane);
   // what is resident: the filter table, or the label column (the kernels read it through
   // filter_bits, common.hpp: the only place that casts it)
   if (f.kind == QueryFilter::TableIds) {
@@ -690,6 +736,7 @@ DeviceFilter ggnn_handle::resolve_filter(DeviceCtx& ctx, const QueryFilter& f, i
     case QueryFilter::TableIds: d.table.ids = static_cast<const int32_t*>(here); break;
     case QueryFilter::Labels: d.table.query_labels = static_cast<const int32_t*>(here); break;
     case QueryFilter::LabelSets:
+    case QueryFilter::LabelRanges:
     case QueryFilter::None: break;
   }
   return d;

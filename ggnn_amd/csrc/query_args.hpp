@@ -51,4 +51,10 @@ struct LabelSetQueryArgs : FilteredQueryArgs {
   LabelSetSpec set;
 };
 
+// Arguments of the label-range kernels (query_labelrange.hip), likewise: the label column and the
+// queries' intervals beside the optional filter table.
+struct LabelRangeQueryArgs : FilteredQueryArgs {
+  LabelRangeSpec range;
+};
+
 }  // namespace ggnn_amd

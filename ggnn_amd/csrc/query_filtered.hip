@@ -29,6 +29,11 @@
 // GGNN_LABELSET_TU -- query_labelset.hip, query_labelset_16.hip.  Their argument block is
 // LabelSetQueryArgs; there is no int8 unit and no PrescreenExact variant (a lossless base takes the
 // ordinary pre-screened kernel: the same results by construction).
+//
+// Label ranges (the label in one of up to 4 closed intervals per query, with an optional filter id:
+// LabelRangeFilter): the same once more, query_labelrange_kernel* under GGNN_LABELRANGE_TU --
+// query_labelrange.hip, query_labelrange_16.hip -- with LabelRangeQueryArgs; no int8 unit and no
+// PrescreenExact variant either.
 #include <algorithm>
 
 #include "query_wave.hpp"
@@ -115,12 +120,49 @@ __global__ void __launch_bounds__(kWave) query_labelset_kernel_lds(const LabelSe
 #include "query_wave_lds_body.inc"
 }
 
+// Label ranges.  LabelRangeFilter keeps per lane what LabelSetFilter keeps (key, label, bitset word)
+// and per wave four (lo, span) pairs where that has eight wanted labels and a mask; the verdict is
+// four subtract-and-compare pairs instead of eight compares.  The occupancy is chosen by the rule of labelset_waves -- the largest at which every
+// early-rows squared-L2 kernel of float32 / uint8 rows has no private segment -- and the build gives
+// the same answer.  Built with 7 waves (72 registers) throughout, the kernels read directly (float32
+// and uint8 layout {8,1}) take 67-71 registers and no scratch memory, but five of the eight
+// pre-screened early-rows squared-L2 kernels go 12-36 bytes into it, the headline kernels <float, 16,
+// 2> with 20 and 36 bytes the most; at 6 waves (80 registers) they take 75 / 77 registers and none
+// (tests/test_label_ranges.py).
+template <class PSC, bool EARLY>
+constexpr int labelrange_waves()
+{
+  return labelset_waves<PSC, EARLY>();
+}
+
+template <typename BaseT, int LPR, int NCH, int R, int MODE, class PSC, int HB = 0, bool EARLY = false>
+__global__ void __launch_bounds__(kWave) __attribute__((
+    amdgpu_waves_per_eu((R == 1 && NCH <= 3) ? labelrange_waves<PSC, EARLY>() : 1)))
+query_labelrange_kernel(const LabelRangeQueryArgs a)
+{
+  static_assert(HB >= 0, "the filtered kernels keep their visited ring in LDS");
+  static_assert(!PsExact<PSC>::value, "label ranges: no kernels of exact distances from codes");
+  using FILT = LabelRangeFilter;
+  constexpr bool GR = false;
+#include "query_wave_body.inc"
+}
+
+// the LDS-resident list (SORTED > 2048, or > 512 with the pre-screen)
+template <typename BaseT, int LPR, int NCH, int MODE, class PSC>
+__global__ void __launch_bounds__(kWave) query_labelrange_kernel_lds(const LabelRangeQueryArgs a)
+{
+  using FILT = LabelRangeFilter;
+#include "query_wave_lds_body.inc"
+}
+
 // the kernel templates of a filter class
 template <class FILT, typename BaseT, int LPR, int NCH, int R, int MODE, class PSC, int HB = 0,
           bool EARLY = false>
 constexpr auto filtered_kernel()
 {
-  if constexpr (std::is_same<FILT, LabelSetFilter>::value)
+  if constexpr (std::is_same<FILT, LabelRangeFilter>::value)
+    return &query_labelrange_kernel<BaseT, LPR, NCH, R, MODE, PSC, HB, EARLY>;
+  else if constexpr (std::is_same<FILT, LabelSetFilter>::value)
     return &query_labelset_kernel<BaseT, LPR, NCH, R, MODE, PSC, HB, EARLY>;
   else if constexpr (std::is_same<FILT, LabelFilter>::value)
     return &query_labeled_kernel<BaseT, LPR, NCH, R, MODE, PSC, HB, EARLY>;
@@ -130,7 +172,9 @@ constexpr auto filtered_kernel()
 template <class FILT, typename BaseT, int LPR, int NCH, int MODE, class PSC>
 constexpr auto filtered_kernel_lds()
 {
-  if constexpr (std::is_same<FILT, LabelSetFilter>::value)
+  if constexpr (std::is_same<FILT, LabelRangeFilter>::value)
+    return &query_labelrange_kernel_lds<BaseT, LPR, NCH, MODE, PSC>;
+  else if constexpr (std::is_same<FILT, LabelSetFilter>::value)
     return &query_labelset_kernel_lds<BaseT, LPR, NCH, MODE, PSC>;
   else if constexpr (std::is_same<FILT, LabelFilter>::value)
     return &query_labeled_kernel_lds<BaseT, LPR, NCH, MODE, PSC>;
@@ -141,7 +185,7 @@ constexpr auto filtered_kernel_lds()
 // the kernel of one row layout, measure and pre-screen (launch_query_cfg, query_wave.hpp)
 template <class FILT>
 struct FilteredLadder {
-  // (ARGS: FilteredQueryArgs, or LabelSetQueryArgs under LabelSetFilter)
+  // (ARGS: FilteredQueryArgs, or LabelSetQueryArgs / LabelRangeQueryArgs under their filters)
   template <typename BaseT, int LPR, int NCH, int MODE, class PSC, class ARGS>
   static void launch(const ARGS& args, hipStream_t stream)
   {
@@ -152,9 +196,10 @@ struct FilteredLadder {
       if (hb != 0 && args.KBuild <= 8 * kEarlySteps && hook(kHookQueryEarly) != 0) {
         const size_t qrow = DistEngine<BaseT, LPR, NCH, PSC::enabled>::kQueryLdsBytes;
         // (PSX: the two-phase variant for a base known to be lossless, as in QueryLadder)
-        // (label sets have no such variant: PSX = PSC and `exact` is false)
-        using PSX = std::conditional_t<std::is_same<FILT, LabelSetFilter>::value, PSC,
-                                       typename ExactOf<PSC>::type>;
+        // (label sets and ranges have no such variant: PSX = PSC and `exact` is false)
+        using PSX = std::conditional_t<std::is_same<FILT, LabelSetFilter>::value ||
+                                           std::is_same<FILT, LabelRangeFilter>::value,
+                                       PSC, typename ExactOf<PSC>::type>;
         const bool exact = args.ps_lossless != 0 && !std::is_same<PSX, PSC>::value;
         if (hb == 1)
           launch_wave_per_query(exact ? filtered_kernel<FILT, BaseT, LPR, NCH, 1, MODE, PSX, 1, true>()
@@ -184,7 +229,49 @@ using TuFilter = LabelFilter;
 using TuFilter = IdFilter;
 #endif
 
-#ifdef GGNN_LABELSET_TU
+#ifdef GGNN_LABELRANGE_TU
+#ifdef GGNN_ROWS_16_TU
+void launch_query_labelrange_16(const LabelRangeQueryArgs& args, ggnn_measure measure,
+                                ggnn_dtype dtype, hipStream_t stream)
+{
+#define GGNN_LAUNCH_QF(T, LPR, NCH) \
+  launch_query_cfg<FilteredLadder<LabelRangeFilter>, T, LPR, NCH>(args, false, measure, stream)
+  GGNN_DISPATCH_DIST_16(dtype, args.D, GGNN_LAUNCH_QF);
+#undef GGNN_LAUNCH_QF
+}
+#else
+// base: filled by launch_query (query.hip); table: the filter table in base.filter_bits (or null)
+// and the filter id per query (or null); range: the label column and the queries' intervals
+void launch_query_labelrange(const QueryArgs& base, const FilterTable& table,
+                             const LabelRangeSpec& range, bool use_ps, ggnn_measure measure,
+                             ggnn_dtype dtype, hipStream_t stream)
+{
+  GGNN_REQUIRE(range.labels != nullptr && range.ranges != nullptr, GGNN_INVALID_ARGUMENT,
+               "the label column or the label ranges are missing");
+  GGNN_REQUIRE(range.n_ranges >= 1 && range.n_ranges <= kMaxLabelRanges, GGNN_INVALID_ARGUMENT,
+               "a query has 1 to 4 label ranges");
+  GGNN_REQUIRE(!table.query_labels, GGNN_INVALID_ARGUMENT,
+               "label ranges exclude the one-label form");
+  GGNN_REQUIRE(!table.ids || !table.num_filters || (base.filter_bits && table.words),
+               GGNN_INVALID_ARGUMENT, "filter ids into a table need the table");
+  GGNN_REQUIRE(dtype != GGNN_I8, GGNN_UNSUPPORTED, "label ranges are not built for int8 rows");
+  GGNN_REQUIRE(base.N_base <= kMaxLabeledShardRows, GGNN_UNSUPPORTED,
+               "label filters need shards of at most 2^30 base vectors");
+  LabelRangeQueryArgs args{};
+  static_cast<QueryArgs&>(args) = base;
+  args.filter_table = table;
+  args.range = range;
+  if (dtype_is_16bit(dtype)) {
+    launch_query_labelrange_16(args, measure, dtype, stream);
+    return;
+  }
+#define GGNN_LAUNCH_QF(T, LPR, NCH) \
+  launch_query_cfg<FilteredLadder<LabelRangeFilter>, T, LPR, NCH>(args, use_ps, measure, stream)
+  GGNN_DISPATCH_DIST_32_8(dtype, args.D, GGNN_LAUNCH_QF);
+#undef GGNN_LAUNCH_QF
+}
+#endif
+#elif defined(GGNN_LABELSET_TU)
 #ifdef GGNN_ROWS_16_TU
 void launch_query_labelset_16(const LabelSetQueryArgs& args, ggnn_measure measure, ggnn_dtype dtype,
                               hipStream_t stream)

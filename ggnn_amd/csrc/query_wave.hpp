@@ -21,7 +21,9 @@ GGNN_DEV void load_prescreen(PSC& ps, const QueryArgs& a, const BaseT* qrow)
 template <class FILT, class ARGS>
 GGNN_DEV FILT wave_filter(const ARGS& a, const uint32_t n)
 {
-  if constexpr (std::is_same<FILT, LabelSetFilter>::value)
+  if constexpr (std::is_same<FILT, LabelRangeFilter>::value)
+    return LabelRangeFilter(a.filter_bits, a.filter_bit_offset, a.filter_table, a.range, n);
+  else if constexpr (std::is_same<FILT, LabelSetFilter>::value)
     return LabelSetFilter(a.filter_bits, a.filter_bit_offset, a.filter_table, a.set, n);
   else if constexpr (std::is_same<FILT, LabelFilter>::value)
     return LabelFilter(a.filter_bits, a.filter_bit_offset, a.filter_table, n);
@@ -178,5 +180,11 @@ void launch_query_labelset(const QueryArgs& base, const FilterTable& table, cons
                            bool use_ps, ggnn_measure measure, ggnn_dtype dtype, hipStream_t stream);
 void launch_query_labelset_16(const LabelSetQueryArgs& args, ggnn_measure measure, ggnn_dtype dtype,
                               hipStream_t stream);
+// Label ranges (LabelRangeFilter): query_labelrange / query_labelrange_16, likewise without int8
+void launch_query_labelrange(const QueryArgs& base, const FilterTable& table,
+                             const LabelRangeSpec& range, bool use_ps, ggnn_measure measure,
+                             ggnn_dtype dtype, hipStream_t stream);
+void launch_query_labelrange_16(const LabelRangeQueryArgs& args, ggnn_measure measure,
+                                ggnn_dtype dtype, hipStream_t stream);
 
 }  // namespace ggnn_amd

@@ -1945,6 +1945,99 @@ struct LabelSetFilter {
   }
 };
 
+// Label-range filters: query n carries up to kMaxLabelRanges closed intervals (lo, hi) of signed
+// int32 labels and, optionally, a filter id into a filter table; a candidate is denied iff its label
+// lies in none of the intervals, or its bit of the query's table row is clear (LabelRangeSpec,
+// common.hpp).  There is no wildcard value: -1 is a label like any other.  request() is
+// LabelSetFilter's -- the label dword, then the bitset word, in front of the first-read rows -- and
+// the verdict is taken once per fetch at the replay:
+//   denied = (uint32(label - lo[j]) > span[j] for all four j)  ||  bit (id + offset) of `bits` is clear
+// with span = uint32(hi - lo): one subtract and one unsigned compare per interval, exact for every
+// signed lo <= hi, (INT32_MIN, INT32_MAX) included (span ~0u).  The form is WRONG for an empty
+// interval (lo > hi: (1, 0) has span ~0u and would admit everything), so the wave constructor, which
+// is scalar and runs before the loop, normalises: an empty interval becomes a copy of the query's
+// first non-empty one, a list shorter than four is padded in the same way, and a query whose
+// intervals are all empty points `bits` at the constant all-zero word with imask 0, as an
+// out-of-table id does.  lo[], span[], both pointers and the offsets are wave-uniform: the same
+// eight scalar registers as LabelSetFilter's want[8].
+constexpr uint32_t kMaxLabelRanges = 4;  // GGNN_MAX_LABEL_RANGES
+struct LabelRangeFilter {
+  static constexpr bool enabled = true;
+  const int32_t* labels;  // the column at the shard's first global id
+  const uint32_t* bits;   // the query's row of the table, or one of the constant words
+  uint32_t offset;        // first global id of the shard (bit offset)
+  uint32_t imask;         // ~3u: `bits` is a row;  0: it is one word
+  uint32_t lo[kMaxLabelRanges], span[kMaxLabelRanges];
+  int key;               // the candidate this lane asked for (or EMPTY)
+  uint32_t word, bword;  // its label, its word of the bitset
+  // the filter of the wave of query n (scalar: the query number is wave-uniform)
+  GGNN_DEV LabelRangeFilter(const uint32_t* table, const uint32_t shard_offset, const FilterTable& t,
+                            const LabelRangeSpec& s, const uint32_t n)
+      : labels(s.labels + shard_offset), bits(kFilterConstWords<>), offset(shard_offset), imask(0u),
+        key(kEmptyKey), word(0u), bword(0u)
+  {
+    const int32_t* r = s.ranges + static_cast<size_t>(n) * s.n_ranges * 2;
+    bool valid[kMaxLabelRanges];
+    bool any = false;
+    uint32_t lo0 = 0u, span0 = 0u;  // the first non-empty interval
+#pragma unroll
+    for (uint32_t j = 0; j < kMaxLabelRanges; ++j) {
+      const uint32_t jj = j < s.n_ranges ? j : 0u;
+      const int32_t l = __builtin_amdgcn_readfirstlane(r[2 * jj]);
+      const int32_t h = __builtin_amdgcn_readfirstlane(r[2 * jj + 1]);
+      valid[j] = l <= h;
+      lo[j] = static_cast<uint32_t>(l);
+      span[j] = static_cast<uint32_t>(h) - static_cast<uint32_t>(l);
+      if (valid[j] && !any) {
+        lo0 = lo[j];
+        span0 = span[j];
+        any = true;
+      }
+    }
+#pragma unroll
+    for (uint32_t j = 0; j < kMaxLabelRanges; ++j) {
+      lo[j] = valid[j] ? lo[j] : lo0;
+      span[j] = valid[j] ? span[j] : span0;
+    }
+    if (t.ids) {
+      const int32_t f = __builtin_amdgcn_readfirstlane(t.ids[n]);
+      if (static_cast<uint32_t>(f) < t.num_filters) {
+        bits = table + static_cast<size_t>(static_cast<uint32_t>(f)) * t.words;
+        imask = ~3u;
+      }
+      else if (f != -1)
+        bits = kFilterConstWords<> + 1;
+    }
+    if (!any) {
+      // every interval is empty: the all-zero word, whatever the id said
+      bits = kFilterConstWords<> + 1;
+      imask = 0u;
+    }
+  }
+  GGNN_DEV void request(const int cand)
+  {
+    key = cand;
+    // EMPTY slots read the label and the bitset word of the shard's first id (verdict ignored)
+    const uint32_t c = static_cast<uint32_t>(max(cand, 0));
+    word = filter_word_at(labels, c << 2);
+    bword = filter_word_at(bits, ((c + offset) >> 3) & imask);
+  }
+  // lanes whose candidate is denied
+  GGNN_DEV unsigned long long denied_lanes() const
+  {
+    bool none = true;
+#pragma unroll
+    for (uint32_t j = 0; j < kMaxLabelRanges; ++j)
+      none = none && (word - lo[j]) > span[j];
+    const uint32_t b = static_cast<uint32_t>(key) + offset;
+    return __ballot(key != kEmptyKey && (none || !((bword >> (b & 31u)) & 1u)));
+  }
+  GGNN_DEV bool denied(const unsigned long long dl, const int k) const
+  {
+    return (__ballot(key == k) & dl) != 0ull;
+  }
+};
+
 // One candidate of a replay (simple_knn_cache.cuh:283-285): pushed if it still beats the criteria,
 // which the pushes before it may have tightened.  One-register lists take the test, and the
 // duplicate test of push(), into the masks of push_if(): the loop around this is then ONE basic block

@@ -349,15 +349,13 @@ def bf_query_labeled(base, query, k_query, labels, query_labels, measure=EUCLIDE
 MAX_LABEL_SET = 8  # GGNN_MAX_LABEL_SET
 
 
-def _need_label_sets(labels, label_sets, filter_table, filter_ids, Nq, n_min):
-    """the label-set arguments of a seam call as the C-ABI takes them: (labels ptr, n_labels, sets
-    ptr, set width, table ptr, F, n_bits, ids ptr)"""
-    _need(labels, torch.int32, "labels"), _need(label_sets, torch.int32, "label_sets")
+def _need_label_rows(labels, rows, n_rows, filter_table, filter_ids, Nq, n_min):
+    """the column, per-query rows (label sets or ranges, checked by the caller), table and ids of a
+    seam call as the C-ABI takes them: (labels ptr, n_labels, rows ptr, n_rows, table ptr, F,
+    n_bits, ids ptr)"""
+    _need(labels, torch.int32, "labels")
     if labels.dim() != 1 or labels.numel() < n_min:
         raise ValueError("labels must be 1-dimensional with at least bit_offset + N entries")
-    if label_sets.dim() != 2 or label_sets.shape[0] != Nq or \
-            not 1 <= label_sets.shape[1] <= MAX_LABEL_SET:
-        raise ValueError(f"label_sets must be [Nq, 1..{MAX_LABEL_SET}]")
     F = n_bits = 0
     if filter_table is not None:
         _need(filter_table, torch.int32, "filter_table")
@@ -370,8 +368,19 @@ def _need_label_sets(labels, label_sets, filter_table, filter_ids, Nq, n_min):
         _need(filter_ids, torch.int32, "filter_ids")
         if filter_ids.dim() != 1 or filter_ids.numel() != Nq:
             raise ValueError("filter_ids must be 1-dimensional with one entry per query")
-    return (_ptr(labels), labels.numel(), _ptr(label_sets), label_sets.shape[1],
-            _ptr(filter_table), F, n_bits, _ptr(filter_ids))
+    return (_ptr(labels), labels.numel(), _ptr(rows), n_rows, _ptr(filter_table), F, n_bits,
+            _ptr(filter_ids))
+
+
+def _need_label_sets(labels, label_sets, filter_table, filter_ids, Nq, n_min):
+    """the label-set arguments of a seam call as the C-ABI takes them: (labels ptr, n_labels, sets
+    ptr, set width, table ptr, F, n_bits, ids ptr)"""
+    _need(label_sets, torch.int32, "label_sets")
+    if label_sets.dim() != 2 or label_sets.shape[0] != Nq or \
+            not 1 <= label_sets.shape[1] <= MAX_LABEL_SET:
+        raise ValueError(f"label_sets must be [Nq, 1..{MAX_LABEL_SET}]")
+    return _need_label_rows(labels, label_sets, label_sets.shape[1], filter_table, filter_ids, Nq,
+                            n_min)
 
 
 def query_labeled_in(base, query, graph0, start, nn1_stats, k_query, tau_query, labels,
@@ -421,6 +430,72 @@ def bf_query_labeled_in(base, query, k_query, labels, label_sets, filter_table=N
     ids = torch.empty((Nq, k_query), dtype=torch.int32, device=base.device)
     dists = torch.empty((Nq, k_query), dtype=torch.float32, device=base.device)
     check(lib().ggnn_op_bf_query_labeled_in(
+        _ptr(base), _dtype_code(base), base.shape[0], base.shape[1], _ptr(query), Nq, k_query,
+        measure, _ptr(ids), _ptr(dists), *tail, bit_offset, _stream()))
+    return ids, dists
+
+
+MAX_LABEL_RANGES = 4  # GGNN_MAX_LABEL_RANGES
+
+
+def _need_label_ranges(labels, label_ranges, filter_table, filter_ids, Nq, n_min):
+    """the label-range arguments of a seam call as the C-ABI takes them: (labels ptr, n_labels,
+    ranges ptr, n_ranges, table ptr, F, n_bits, ids ptr)"""
+    _need(label_ranges, torch.int32, "label_ranges")
+    if label_ranges.dim() != 3 or label_ranges.shape[0] != Nq or label_ranges.shape[2] != 2 or \
+            not 1 <= label_ranges.shape[1] <= MAX_LABEL_RANGES:
+        raise ValueError(f"label_ranges must be [Nq, 1..{MAX_LABEL_RANGES}, 2]")
+    return _need_label_rows(labels, label_ranges, label_ranges.shape[1], filter_table, filter_ids,
+                            Nq, n_min)
+
+
+def query_labeled_range(base, query, graph0, start, nn1_stats, k_query, tau_query, labels,
+                        label_ranges, filter_table=None, filter_ids=None, max_iterations=400,
+                        measure=EUCLIDEAN, bit_offset=0, shards_per_gpu=1, on_gpu_shard=0,
+                        counters=False, prescreen=None, rows_read=None):
+    """`query_labeled_in` with label RANGES in place of label sets: label_ranges is [Nq, 1..4, 2]
+    int32, closed intervals (lo, hi), and query n may be given the rows with lo <= labels[i +
+    bit_offset] <= hi (signed) for one of its intervals AND whose bit i + bit_offset of row
+    filter_ids[n] of filter_table is set -- id -1 admits every row, any other id outside [0, F)
+    none.  lo > hi is an empty interval; there is no wildcard value (-1 is an ordinary label).
+    filter_ids=None: ranges only (filter_table is then not read)."""
+    _need(base, name="base"), _need(query, base.dtype, "query")
+    _need(graph0, torch.int32, "graph0"), _need(start, torch.int32, "start")
+    _need(nn1_stats, torch.float32, "nn1_stats")
+    Nq = query.shape[0]
+    tail = _need_label_ranges(labels, label_ranges, filter_table, filter_ids, Nq,
+                              bit_offset + base.shape[0])
+    ids = torch.empty((Nq, k_query * shards_per_gpu), dtype=torch.int32, device=base.device)
+    dists = torch.empty((Nq, k_query * shards_per_gpu), dtype=torch.float32, device=base.device)
+    nd = npop = None
+    if counters:
+        nd = torch.zeros(Nq, dtype=torch.int32, device=base.device)
+        npop = torch.zeros(Nq, dtype=torch.int32, device=base.device)
+    codes, params = prescreen if prescreen is not None else (None, None)
+    if prescreen is not None:
+        _need(base, torch.float32, "base"), _need(codes, torch.uint8, "codes")
+        _need(params, torch.float32, "params")
+    check(lib().ggnn_op_query_labeled_range(
+        _ptr(base), _dtype_code(base), base.shape[0], base.shape[1], _ptr(codes), _ptr(params),
+        _ptr(query), Nq, _ptr(graph0), graph0.shape[1], _ptr(start), start.numel(),
+        _ptr(nn1_stats), k_query, tau_query, max_iterations, measure, shards_per_gpu,
+        on_gpu_shard, _ptr(ids), _ptr(dists), _ptr(nd), _ptr(npop), _ptr(rows_read),
+        *tail, bit_offset, _stream()))
+    if counters:
+        return ids, dists, nd, npop
+    return ids, dists
+
+
+def bf_query_labeled_range(base, query, k_query, labels, label_ranges, filter_table=None,
+                           filter_ids=None, measure=EUCLIDEAN, bit_offset=0):
+    """`bf_query_filtered` under label ranges (see query_labeled_range); always the scan kernels"""
+    _need(base, name="base"), _need(query, base.dtype, "query")
+    Nq = query.shape[0]
+    tail = _need_label_ranges(labels, label_ranges, filter_table, filter_ids, Nq,
+                              bit_offset + base.shape[0])
+    ids = torch.empty((Nq, k_query), dtype=torch.int32, device=base.device)
+    dists = torch.empty((Nq, k_query), dtype=torch.float32, device=base.device)
+    check(lib().ggnn_op_bf_query_labeled_range(
         _ptr(base), _dtype_code(base), base.shape[0], base.shape[1], _ptr(query), Nq, k_query,
         measure, _ptr(ids), _ptr(dists), *tail, bit_offset, _stream()))
     return ids, dists

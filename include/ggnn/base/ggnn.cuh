@@ -215,6 +215,44 @@ class GGNN {
     return r;
   }
 
+  // Label ranges (ggnn_query_labeled_range): query n is given the base vectors whose label lies in
+  // one of its n_ranges closed intervals (label_ranges[(n * n_ranges + j) * 2], ...[... + 1]) = (lo,
+  // hi), 1 <= n_ranges <= GGNN_MAX_LABEL_RANGES, compared as signed int32 -- lo > hi is an empty
+  // interval and there is no wildcard value, -1 is an ordinary label -- AND whose bit is set in row
+  // filter_ids[n] of the table (-1: every vector; filter_ids == nullptr: no bitset).  Host memory.
+  [[nodiscard]] virtual Results queryLabeledRange(
+      const GenericDataset& query, const uint32_t KQuery, const float tau_query,
+      const int32_t* label_ranges, const uint32_t n_ranges, const int32_t* filter_ids = nullptr,
+      const uint32_t max_iterations = 400,
+      const DistanceMeasure measure = DistanceMeasure::Euclidean)
+  {
+    const uint32_t width = on_gpu_ ? KQuery * num_shards() : KQuery;
+    Results r = make_results(query, width);
+    detail::check(
+        ggnn_query_labeled_range(h_, query.raw(), query.N, query.D, dtype_of(query),
+                                 loc_of(query), query.gpu_id, KQuery, tau_query, max_iterations,
+                                 static_cast<ggnn_measure>(measure), r.ids.data(), r.dists.data(),
+                                 on_gpu_ ? GGNN_GPU : GGNN_CPU, label_ranges, n_ranges, GGNN_CPU, 0,
+                                 filter_ids, GGNN_CPU, 0),
+        h_);
+    return r;
+  }
+  [[nodiscard]] virtual Results bfQueryLabeledRange(
+      const GenericDataset& query, const int32_t* label_ranges, const uint32_t n_ranges,
+      const int32_t* filter_ids = nullptr, const uint32_t KGT = 100,
+      const DistanceMeasure measure = DistanceMeasure::Euclidean)
+  {
+    Results r = make_results(query, KGT);
+    detail::check(
+        ggnn_bf_query_labeled_range(h_, query.raw(), query.N, query.D, dtype_of(query),
+                                    loc_of(query), query.gpu_id, KGT,
+                                    static_cast<ggnn_measure>(measure), r.ids.data(),
+                                    r.dists.data(), on_gpu_ ? GGNN_GPU : GGNN_CPU, label_ranges,
+                                    n_ranges, GGNN_CPU, 0, filter_ids, GGNN_CPU, 0),
+        h_);
+    return r;
+  }
+
   [[nodiscard]] virtual const Graph& getGraph(const uint32_t global_shard_id = 0)
   {
     ggnn_graph_view v{};

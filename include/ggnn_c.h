@@ -290,7 +290,8 @@ ggnn_status ggnn_query_async_labeled(ggnn_t* h, const void* query, uint64_t Nq, 
  * labels, and with ids but no filter table; GGNN_UNSUPPORTED on an int8 base and for shards of more
  * than 2^30 vectors.  Everything else is ggnn_query / ggnn_bf_query.  ggnn_bf_query_labeled_in
  * always runs the scan kernels: ggnn_last_bf_query_matrix_path reports 0.
- * What remains: at most 8 labels per query, int32 labels only, no int8 rows, no matrix-core path. */
+ * What remains: at most 8 labels per query (numeric predicates: the label ranges below), int32
+ * labels only, no int8 rows, no matrix-core path. */
 #define GGNN_MAX_LABEL_SET 8
 ggnn_status ggnn_query_labeled_in(ggnn_t* h, const void* query, uint64_t Nq, uint32_t D,
                                   ggnn_dtype dtype, ggnn_location location, int gpu_id,
@@ -314,6 +315,62 @@ ggnn_status ggnn_query_async_labeled_in(ggnn_t* h, const void* query, uint64_t N
                                         ggnn_measure measure, int32_t* ids_out, float* dists_out,
                                         uint32_t slot, const int32_t* query_label_sets,
                                         uint32_t set_width, const int32_t* filter_ids);
+
+/* Label ranges: "the label lies in one of these intervals", combined with a filter id.
+ * Query n carries n_ranges closed intervals -- row n of query_label_ranges[Nq x n_ranges x 2], int32
+ * pairs (lo, hi), 1 <= n_ranges <= GGNN_MAX_LABEL_RANGES -- and, optionally, a filter id
+ * filter_ids[n] into the resident filter table of ggnn_set_filters (the whole array may be null).
+ * Base vector i may be reported to query n iff
+ *   lo_j <= labels[i] <= hi_j for at least one j, compared as SIGNED int32, AND
+ *   the filter id admits i under the rules of ggnn_query_filtered_by: -1 or a null array admits
+ *   every vector, an id in [0, num_filters) needs the vector's bit in that row, any other id
+ *   admits none.
+ * Query n gives, bit for bit (ids, distances, counters), the result of ggnn_query_filtered /
+ * ggnn_bf_query_filtered of that query with the bitset any_j(lo_j <= labels <= hi_j) &
+ * row(filter_ids[n]); an empty predicate gives every slot (-1 + id offset, +inf).
+ *   An interval with lo > hi is EMPTY: it contains nothing, it is neither wrapped around nor
+ *   swapped.  A short list is padded by repeating an interval or with an empty one such as (1, 0);
+ *   a query whose intervals are all empty has an empty result.
+ *   There is NO WILDCARD value, unlike *_labeled and *_labeled_in: -1 is an ordinary label here --
+ *   (-5, 5) admits the rows labelled -5 .. 5 and nothing else -- and (INT32_MIN, INT32_MAX) admits
+ *   every label.  Every int32 value is a valid bound: bounds are compared, never used as an index.
+ * One interval (L, L) with L != -1 and null ids is ggnn_query_labeled with label L; intervals (a, a),
+ * (b, b), ... are ggnn_query_labeled_in with the set {a, b, ...} when no entry is -1; (INT32_MIN,
+ * INT32_MAX) with ids is ggnn_query_filtered_by, and with null ids ggnn_query.
+ * The ranges follow the memory rules of query_label_sets and the ids those of filter_ids in the
+ * *_labeled_in calls (ggnn_query_async_labeled_range: both live where the query lives and are not
+ * read on the host).  GGNN_INVALID_ARGUMENT for n_ranges outside [1, 4], a null range array and
+ * host-resident ids outside [-1, num_filters); GGNN_INVALID_STATE without labels, and with ids but
+ * no filter table; GGNN_UNSUPPORTED on an int8 base and for shards of more than 2^30 vectors.
+ * Everything else is ggnn_query / ggnn_bf_query.  ggnn_bf_query_labeled_range always runs the scan
+ * kernels: ggnn_last_bf_query_matrix_path reports 0.
+ * What remains: at most 4 intervals per query, one int32 column (float32 attributes: map them to
+ * int32 in order first), closed intervals only, no int8 rows, no matrix-core path. */
+#define GGNN_MAX_LABEL_RANGES 4
+ggnn_status ggnn_query_labeled_range(ggnn_t* h, const void* query, uint64_t Nq, uint32_t D,
+                                     ggnn_dtype dtype, ggnn_location location, int gpu_id,
+                                     uint32_t k_query, float tau_query, uint32_t max_iterations,
+                                     ggnn_measure measure, int32_t* ids_out, float* dists_out,
+                                     ggnn_location out_location,
+                                     const int32_t* query_label_ranges, uint32_t n_ranges,
+                                     ggnn_location ranges_location, int ranges_gpu_id,
+                                     const int32_t* filter_ids, ggnn_location ids_location,
+                                     int ids_gpu_id);
+ggnn_status ggnn_bf_query_labeled_range(ggnn_t* h, const void* query, uint64_t Nq, uint32_t D,
+                                        ggnn_dtype dtype, ggnn_location location, int gpu_id,
+                                        uint32_t k_gt, ggnn_measure measure, int32_t* ids_out,
+                                        float* dists_out, ggnn_location out_location,
+                                        const int32_t* query_label_ranges, uint32_t n_ranges,
+                                        ggnn_location ranges_location, int ranges_gpu_id,
+                                        const int32_t* filter_ids, ggnn_location ids_location,
+                                        int ids_gpu_id);
+ggnn_status ggnn_query_async_labeled_range(ggnn_t* h, const void* query, uint64_t Nq, uint32_t D,
+                                           ggnn_dtype dtype, int gpu_id, uint32_t k_query,
+                                           float tau_query, uint32_t max_iterations,
+                                           ggnn_measure measure, int32_t* ids_out,
+                                           float* dists_out, uint32_t slot,
+                                           const int32_t* query_label_ranges, uint32_t n_ranges,
+                                           const int32_t* filter_ids);
 
 /* layout of one graph shard, include/ggnn/base/graph_config.h:31-112 */
 typedef struct {
@@ -656,6 +713,34 @@ ggnn_status ggnn_op_bf_query_labeled_in(const void* base, ggnn_dtype dtype, uint
                                         const uint32_t* filter_table, uint32_t num_filters,
                                         uint64_t n_bits, const int32_t* filter_ids,
                                         uint32_t filter_bit_offset, void* stream);
+/* ggnn_op_query_labeled_in / ggnn_op_bf_query_labeled_in with label RANGES in place of label sets:
+ * query_label_ranges is int32 [Nq x n_ranges x 2], (lo, hi) pairs, 1 <= n_ranges <=
+ * GGNN_MAX_LABEL_RANGES; local id i may be given to query n iff lo <= labels[i + filter_bit_offset]
+ * <= hi (signed) for one of its pairs AND filter_ids[n] admits it, as above.  lo > hi is an empty
+ * interval and there is no wildcard value (see ggnn_query_labeled_range).  No int8 rows
+ * (GGNN_UNSUPPORTED); ggnn_op_bf_query_labeled_range always runs the scan kernels. */
+ggnn_status ggnn_op_query_labeled_range(const void* base, ggnn_dtype dtype, uint32_t N_base,
+                                        uint32_t D, const uint8_t* codes, const float* params,
+                                        const void* query, uint32_t Nq, const int32_t* graph0,
+                                        uint32_t KBuild, const int32_t* start, uint32_t num_start,
+                                        const float* nn1_stats, uint32_t k_query, float tau_query,
+                                        uint32_t max_iterations, ggnn_measure measure,
+                                        uint32_t shards_per_gpu, uint32_t on_gpu_shard,
+                                        int32_t* ids, float* dists, uint32_t* n_dist,
+                                        uint32_t* n_pop, uint32_t* n_rows, const int32_t* labels,
+                                        uint64_t n_labels, const int32_t* query_label_ranges,
+                                        uint32_t n_ranges, const uint32_t* filter_table,
+                                        uint32_t num_filters, uint64_t n_bits,
+                                        const int32_t* filter_ids, uint32_t filter_bit_offset,
+                                        void* stream);
+ggnn_status ggnn_op_bf_query_labeled_range(const void* base, ggnn_dtype dtype, uint32_t N_base,
+                                           uint32_t D, const void* query, uint32_t Nq,
+                                           uint32_t k_query, ggnn_measure measure, int32_t* ids,
+                                           float* dists, const int32_t* labels, uint64_t n_labels,
+                                           const int32_t* query_label_ranges, uint32_t n_ranges,
+                                           const uint32_t* filter_table, uint32_t num_filters,
+                                           uint64_t n_bits, const int32_t* filter_ids,
+                                           uint32_t filter_bit_offset, void* stream);
 /* ggnn_op_bf_query_filtered, _filtered_by and _labeled, reporting how they ran (modelled on
  * ggnn_op_bf_query_certified): *n_rescanned (DEVICE memory, may be NULL) receives the number of
  * queries the matrix-core pre-selection could not certify and the filtered scan answered instead;

@@ -44,7 +44,15 @@ Label sets (`query_labeled_in`) against `query_labeled` on the same handle, grap
 --tenants disjoint tenants, one label per query, width 1 and no filter ids; kernel ms of both calls,
 alternating, every repeat listed.  Then one row for width 8 (eight of the tenants per query) with a
 50 % bitset as the one row of the filter table, next to `query_filtered_by` of the bitset alone (a
-wider predicate: the figure says what a search under the bitset costs, not what the label read adds)."""
+wider predicate: the figure says what a search under the bitset costs, not what the label read adds).
+
+    python scripts/filtered_bench.py --ranges
+
+Label ranges (`query_labeled_range`) against label sets (`query_labeled_in`) on the same handle,
+graph and masks: a label column whose values 0..7 cover 50 % of the rows, 8..15 10 % and 16..17
+1 %, every query under the same mask, written once as a set of the values and once as one interval
+around them; results asserted equal, then kernel ms and queries/s (host clock around calls that end
+synchronised) of both calls, alternating, every repeat listed."""
 import argparse
 import json
 import os
@@ -73,6 +81,7 @@ def main():
     ap.add_argument("--label-tenants", type=int, nargs="+", default=[16, 1024])
     ap.add_argument("--bf", action="store_true")
     ap.add_argument("--label-sets", action="store_true")
+    ap.add_argument("--ranges", action="store_true")
     a = ap.parse_args()
     rs = np.random.default_rng(1)
     centres = rs.normal(size=(256, a.d)).astype(np.float32) * 2
@@ -93,6 +102,9 @@ def main():
         return
     if a.label_sets:
         label_sets(a, g, q)
+        return
+    if a.ranges:
+        label_ranges(a, g, q)
         return
 
     def timed(fn):
@@ -341,6 +353,37 @@ def label_sets(a, g, q):
                                                                         filter_ids=zero)},
        tenants=T, allowed_share=round(0.5 * w / T, 4))
     g.set_filters(None)
+    g.set_labels(None)
+
+
+def label_ranges(a, g, q):
+    import time
+    rs = np.random.default_rng(19)
+    # values 0..7: 6.25 % of the rows each, 8..15: 1.25 % each, 16..17: 0.5 % each, 18: the rest
+    p = np.array([0.0625] * 8 + [0.0125] * 8 + [0.005] * 2 + [0.39])
+    column = rs.choice(len(p), a.n, p=p / p.sum()).astype(np.int32)
+    g.set_labels(torch.from_numpy(column).cuda())
+    for name, lo, hi in (("50 %", 0, 7), ("10 %", 8, 15), ("1 %", 16, 17)):
+        values = list(range(lo, hi + 1))
+        sets = torch.tensor([values] * a.queries, dtype=torch.int32).cuda()
+        ranges = torch.tensor([[[lo, hi]]] * a.queries, dtype=torch.int32).cuda()
+        calls = {"query_labeled_in": lambda: g.query_labeled_in(q, a.k, a.tau, a.iters, label_sets=sets),
+                 "query_labeled_range": lambda: g.query_labeled_range(q, a.k, a.tau, a.iters,
+                                                                      label_ranges=ranges)}
+        x, y = (fn() for fn in calls.values())
+        assert torch.equal(x[0], y[0]) and torch.equal(x[1], y[1])
+        ms, qps = {k: [] for k in calls}, {k: [] for k in calls}
+        for _ in range(a.reps):                               # alternating
+            for k, fn in calls.items():
+                torch.cuda.synchronize()
+                t = time.perf_counter()
+                fn()
+                torch.cuda.synchronize()
+                qps[k].append(round(a.queries / (time.perf_counter() - t)))
+                ms[k].append(round(g.last_timing_ms()["query_ms"], 4))
+        print(json.dumps({"ranges": name, "labels": values, "interval": [lo, hi],
+                          "allowed": int(((column >= lo) & (column <= hi)).sum()),
+                          "kernel_ms": ms, "queries_per_s": qps}), flush=True)
     g.set_labels(None)
 
 
