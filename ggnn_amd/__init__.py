@@ -4,10 +4,10 @@ The compute path is hand-written HIP for gfx950 in ggnn_amd/csrc (libggnn_amd.so
 C-ABI of include/ggnn_c.h; this package is the thin host side.  There is no CPU fallback.
 """
 from .api import (GGNN, CharDataset, DistanceMeasure, Evaluation, Evaluator, FloatDataset, Graph,
-                  IntDataset, UCharDataset, ordered_int32, pack_filter, pack_filters,
-                  set_log_level)
+                  IntDataset, UCharDataset, label_mask, ordered_int32, pack_filter,
+                  pack_filters, set_log_level)
 
 __all__ = ["GGNN", "DistanceMeasure", "Evaluation", "Evaluator", "FloatDataset", "Graph",
-           "IntDataset", "UCharDataset", "CharDataset", "ordered_int32", "pack_filter",
+           "IntDataset", "UCharDataset", "CharDataset", "label_mask", "ordered_int32", "pack_filter",
            "pack_filters", "set_log_level"]
 __version__ = "0.1.0"

@@ -134,6 +134,14 @@ SIGNATURES = {
                                            _int]),
     "ggnn_query_async_labeled_range": (_int, [_vp, _vp, _u64, _u32, _int, _int, _u32, _f32, _u32,
                                               _int, _vp, _vp, _u32, _vp, _u32, _vp]),
+    "ggnn_query_labeled_mask": (_int, [_vp, _vp, _u64, _u32, _int, _int, _int, _u32, _f32, _u32,
+                                       _int, _vp, _vp, _int, _vp, _u32, _int, _int, _vp, _int,
+                                       _int]),
+    "ggnn_bf_query_labeled_mask": (_int, [_vp, _vp, _u64, _u32, _int, _int, _int, _u32, _int,
+                                          _vp, _vp, _int, _vp, _u32, _int, _int, _vp, _int,
+                                          _int]),
+    "ggnn_query_async_labeled_mask": (_int, [_vp, _vp, _u64, _u32, _int, _int, _u32, _f32, _u32,
+                                             _int, _vp, _vp, _u32, _vp, _u32, _vp]),
     "ggnn_get_graph": (_int, [_vp, _u32, C.POINTER(GraphView)]),
     "ggnn_last_timing_ms": (_int, [_vp, C.POINTER(_f32), C.POINTER(_f32), C.POINTER(_f32)]),
     "ggnn_last_query_counters": (_int, [_vp, C.POINTER(_u64), C.POINTER(_u64)]),
@@ -193,6 +201,13 @@ SIGNATURES = {
     "ggnn_op_bf_query_labeled_range": (_int, [_vp, _int, _u32, _u32, _vp, _u32, _u32, _int, _vp,
                                               _vp, _vp, _u64, _vp, _u32, _vp, _u32, _u64, _vp,
                                               _u32, _vp]),
+    "ggnn_op_query_labeled_mask": (_int, [_vp, _int, _u32, _u32, _vp, _vp, _vp, _u32, _vp, _u32,
+                                          _vp, _u32, _vp, _u32, _f32, _u32, _int, _u32, _u32,
+                                          _vp, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _u32, _vp,
+                                          _u32, _u64, _vp, _u32, _vp]),
+    "ggnn_op_bf_query_labeled_mask": (_int, [_vp, _int, _u32, _u32, _vp, _u32, _u32, _int, _vp,
+                                             _vp, _vp, _u64, _vp, _u32, _vp, _u32, _u64, _vp,
+                                             _u32, _vp]),
     "ggnn_op_bf_query": (_int, [_vp, _int, _u32, _u32, _vp, _u32, _u32, _int, _vp, _vp, _vp]),
     "ggnn_op_bf_query_certified": (_int, [_vp, _int, _u32, _u32, _vp, _u32, _u32, _int, _vp, _vp,
                                           _vp, _vp]),

@@ -253,6 +253,88 @@ def _label_ranges(label_ranges, Nq):
     return label_ranges.contiguous()
 
 
+MAX_LABEL_MASKS = 2  # GGNN_MAX_LABEL_MASKS
+_UINT32_MAX = 2 ** 32 - 1
+
+
+def _wrap_int32(v):
+    """an integer in [-2**31, 2**32) as the int32 with the same low 32 bits"""
+    return v - 2 ** 32 if v > _INT32_MAX else v
+
+
+def _label_masks(label_masks, Nq):
+    """the `label_masks` argument as a contiguous [Nq, 1..2, 3] int32 tensor (CPU or CUDA) of clauses
+    (mask, value, any): a 3-D [Nq, 1..2, 3] or 2-D [Nq, 3] int32 / int64 array or tensor is taken as
+    it is; anything else is read as one sequence of 1 or 2 triples per query and padded to the
+    longest row by repeating the row's first triple.  Values in [-2**31, 2**32) are accepted and
+    wrapped to int32, so 0x80000000 can be written as it reads."""
+    if isinstance(label_masks, np.ndarray):
+        if label_masks.dtype in (np.uint32, np.uint64):
+            raise TypeError("label_masks must be int32 or int64 (values up to 2**32 - 1 wrap)")
+        label_masks = torch.from_numpy(np.ascontiguousarray(label_masks))
+    if not isinstance(label_masks, torch.Tensor):
+        rows = [[tuple(int(v) for v in (c.tolist() if hasattr(c, "tolist") else c)) for c in r]
+                for r in label_masks]
+        for n, r in enumerate(rows):
+            if not 1 <= len(r) <= MAX_LABEL_MASKS:
+                raise ValueError(f"query {n} has {len(r)} label mask clauses: 1 to "
+                                 f"{MAX_LABEL_MASKS} are allowed")
+            if any(len(c) != 3 for c in r):
+                raise ValueError(f"the label masks of query {n} must be (mask, value, any) triples")
+            if any(not _INT32_MIN <= v <= _UINT32_MAX for c in r for v in c):
+                raise ValueError("label_masks has values outside [-2**31, 2**32)")
+        width = max((len(r) for r in rows), default=1)
+        label_masks = torch.tensor([r + [r[0]] * (width - len(r)) for r in rows],
+                                   dtype=torch.int64).reshape(len(rows), width, 3)
+    if label_masks.dim() == 2 and label_masks.shape[1] == 3:
+        label_masks = label_masks.reshape(label_masks.shape[0], 1, 3)
+    if label_masks.dim() != 3 or label_masks.shape[2] != 3:
+        raise TypeError("label_masks must be [Nq, M, 3] or [Nq, 3], or a sequence of per-query "
+                        "sequences of (mask, value, any) triples")
+    if label_masks.dtype not in (torch.int32, torch.int64):
+        raise TypeError("label_masks must be int32 or int64 (values up to 2**32 - 1 wrap)")
+    if label_masks.shape[0] != Nq:
+        raise ValueError(f"label_masks needs one row per query ({Nq})")
+    if not 1 <= label_masks.shape[1] <= MAX_LABEL_MASKS:
+        raise ValueError(f"a query has 1 to {MAX_LABEL_MASKS} label mask clauses, not "
+                         f"{label_masks.shape[1]}")
+    if label_masks.dtype == torch.int64:
+        if label_masks.numel() and (int(label_masks.min()) < _INT32_MIN or
+                                    int(label_masks.max()) > _UINT32_MAX):
+            raise ValueError("label_masks has values outside [-2**31, 2**32)")
+        label_masks = torch.where(label_masks > _INT32_MAX, label_masks - 2 ** 32,
+                                  label_masks).to(torch.int32)
+    return label_masks.contiguous()
+
+
+def label_mask(all_of=0, none_of=0, any_of=0, field_mask=0, field_value=0):
+    """one clause (mask, value, any) for `query_labeled_mask`, from sets of tag bits: the row has
+    every bit of `all_of`, no bit of `none_of`, at least one bit of `any_of` (0: no such condition),
+    and its bits under `field_mask` equal `field_value` (given at the field's position) --
+
+        (all_of | none_of | field_mask,  all_of | field_value,  any_of)
+
+    wrapped to int32.  The arguments are bit sets in [0, 2**32) (or their int32 form).  ValueError
+    where the clause would silently mean something else: `all_of` and `none_of` share a bit,
+    `field_value` has a bit outside `field_mask`, or `field_mask` overlaps `all_of | none_of`."""
+    bits = []
+    for name, v in (("all_of", all_of), ("none_of", none_of), ("any_of", any_of),
+                    ("field_mask", field_mask), ("field_value", field_value)):
+        v = int(v)
+        if not _INT32_MIN <= v <= _UINT32_MAX:
+            raise ValueError(f"label_mask: {name} is outside [-2**31, 2**32)")
+        bits.append(v & _UINT32_MAX)
+    all_of, none_of, any_of, field_mask, field_value = bits
+    if all_of & none_of:
+        raise ValueError("label_mask: all_of and none_of share a bit: no row could pass")
+    if field_value & ~field_mask:
+        raise ValueError("label_mask: field_value has a bit outside field_mask")
+    if field_mask & (all_of | none_of):
+        raise ValueError("label_mask: field_mask overlaps all_of | none_of")
+    return (_wrap_int32(all_of | none_of | field_mask), _wrap_int32(all_of | field_value),
+            _wrap_int32(any_of))
+
+
 def ordered_int32(x):
     """float32 values (array, tensor or scalar) as int32 values in the same order, for a float
     attribute -- a price, a float timestamp -- in the int32 label column:
@@ -415,14 +497,15 @@ class QueryTicket:
     input alive (and `filter_ids` the filter ids, or the query labels, of a batch that has some);
     `done` is set by `synchronize()`."""
     __slots__ = ("query", "ids", "dists", "slot", "done", "filter_ids", "label_sets",
-                 "label_ranges")
+                 "label_ranges", "label_masks")
 
     def __init__(self, query, ids, dists, slot, filter_ids=None, label_sets=None,
-                 label_ranges=None):
+                 label_ranges=None, label_masks=None):
         self.query, self.ids, self.dists, self.slot, self.done = query, ids, dists, slot, False
         self.filter_ids = filter_ids
         self.label_sets = label_sets
         self.label_ranges = label_ranges
+        self.label_masks = label_masks
 
     def __iter__(self):
         return iter((self.ids, self.dists))
@@ -668,8 +751,8 @@ class GGNN:
                               self._where(ql))
 
     def _labeled_in_tail(self, ls, fi):
-        """the filter arguments of the *_labeled_in / *_labeled_range calls: the sets (or ranges:
-        shape[1] is their number either way), then the ids (or null)"""
+        """the filter arguments of the *_labeled_in / *_labeled_range / *_labeled_mask calls: the
+        sets (or ranges, or clauses: shape[1] is their number either way), then the ids (or null)"""
         ids = self._where(fi) if fi is not None else (None, _lib.CPU, 0)
         return (ls.data_ptr(), ls.shape[1], *_loc(ls), *ids)
 
@@ -744,6 +827,44 @@ class GGNN:
         fi = None if filter_ids is None else _filter_ids(filter_ids, t.shape[0])
         return self._blocking(lib().ggnn_bf_query_labeled_range, t, (int(k_gt), int(measure)),
                               self._labeled_in_tail(lr, fi))
+
+    def query_labeled_mask(self, query, k_query, tau_query, max_iterations=400,
+                           measure=DistanceMeasure.Euclidean, label_masks=None, filter_ids=None):
+        """Extension: `query` under label MASKS -- the int32 label of `set_labels` read as 32 tag
+        bits -- combined with a filter id per query (`set_filters`).  `label_masks`: for every query
+        1 or 2 clauses (mask, value, any) -- a [Nq, 1..2, 3] or [Nq, 3] int32 / int64 array or
+        tensor, CPU or GPU, or a sequence of per-query sequences of 1 or 2 triples (a shorter row is
+        padded by repeating its first triple; an empty or longer row is a ValueError); values in
+        [-2**31, 2**32) wrap to int32; `label_mask` builds a triple.  A base vector with label L
+        passes a clause iff (L & mask) == value and (any == 0 or (L & any) != 0); query n is given
+        the vectors that pass one of its clauses AND that row `filter_ids[n]` of the filter table
+        allows (`filter_ids` as in `query_filtered_by`; `None`: no bitset) -- bit for bit
+        `query_filtered` with that mask.  (0, 0, 0) admits every vector, a value with a bit outside
+        its mask none (value is never pre-masked), there is no wildcard value and bit 31 is a bit
+        like any other.  `label_masks=None` is no label restriction (`query_filtered_by`); both
+        `None` is `query`."""
+        if label_masks is None:
+            return self.query_filtered_by(query, k_query, tau_query, max_iterations, measure,
+                                          filter_ids=filter_ids)
+        t = _as_tensor(query, what="query")
+        lm = _label_masks(label_masks, t.shape[0])
+        fi = None if filter_ids is None else _filter_ids(filter_ids, t.shape[0])
+        return self._blocking(lib().ggnn_query_labeled_mask, t,
+                              self._search(k_query, tau_query, max_iterations, measure),
+                              self._labeled_in_tail(lm, fi), self._shards)
+
+    def bf_query_labeled_mask(self, query, k_gt=100, measure=DistanceMeasure.Euclidean,
+                              label_masks=None, filter_ids=None):
+        """Extension: the exact `k_gt` nearest among the base vectors `label_masks` and `filter_ids`
+        admit (see `query_labeled_mask`); slots beyond their number are (-1, +inf).  Always the scan
+        kernels.  `label_masks=None` is `bf_query_filtered_by`; both `None` is `bf_query`."""
+        if label_masks is None:
+            return self.bf_query_filtered_by(query, k_gt, measure, filter_ids=filter_ids)
+        t = _as_tensor(query, what="query")
+        lm = _label_masks(label_masks, t.shape[0])
+        fi = None if filter_ids is None else _filter_ids(filter_ids, t.shape[0])
+        return self._blocking(lib().ggnn_bf_query_labeled_mask, t, (int(k_gt), int(measure)),
+                              self._labeled_in_tail(lm, fi))
 
     def query_filtered(self, query, k_query, tau_query, max_iterations=400,
                        measure=DistanceMeasure.Euclidean, filter=None):
@@ -848,14 +969,24 @@ class GGNN:
         return self._query_async(query, k_query, tau_query, max_iterations, measure, slot,
                                  filter_ids, None, None, label_ranges)
 
+    def query_async_labeled_mask(self, query, k_query, tau_query, max_iterations=400,
+                                 measure=DistanceMeasure.Euclidean, slot=0, label_masks=None,
+                                 filter_ids=None):
+        """Extension: `query_async` under label masks and filter ids (`query_labeled_mask`), both
+        with the memory and lifetime rules of the `filter_ids` of `query_async` (kept alive on the
+        ticket: `ticket.filter_ids`, `ticket.label_masks`).  `label_masks=None` is `query_async`."""
+        return self._query_async(query, k_query, tau_query, max_iterations, measure, slot,
+                                 filter_ids, None, None, None, label_masks)
+
     def _query_async(self, query, k_query, tau_query, max_iterations, measure, slot, filter_ids,
-                     labels, label_sets=None, label_ranges=None):
+                     labels, label_sets=None, label_ranges=None, label_masks=None):
         t = _as_tensor(query, what="query")
         fi = None if filter_ids is None else _filter_ids(filter_ids, t.shape[0])
         if labels is not None:
             fi = _labels(labels, t.shape[0], per="query")
         ls = None if label_sets is None else _label_sets(label_sets, t.shape[0])
         lr = None if label_ranges is None else _label_ranges(label_ranges, t.shape[0])
+        lm = None if label_masks is None else _label_masks(label_masks, t.shape[0])
 
         def follow(x, pinned):
             # sets and ids follow the query's memory rule: its GPU, or page-locked host memory
@@ -871,6 +1002,7 @@ class GGNN:
             if not t.is_cuda and not t.is_pinned():
                 t = t.pin_memory()
             fi, ls, lr = follow(fi, True), follow(ls, True), follow(lr, True)
+            lm = follow(lm, True)
             dev = t.device.index if t.is_cuda else -1
             if t.is_cuda:
                 ids, dists = self._out(t.shape[0], int(k_query), True, t.device)
@@ -883,12 +1015,17 @@ class GGNN:
                 raise RuntimeError("query_async needs the query on the GPU")
             loc, dev = _loc(t)
             fi, ls, lr = follow(fi, False), follow(ls, False), follow(lr, False)
+            lm = follow(lm, False)
             ids, dists = self._out(t.shape[0], int(k_query) * self._shards, True, t.device)
-        if ls is not None or lr is not None:
-            # (sets or ranges: [Nq, width] / [Nq, n_ranges, 2], the same argument list)
-            rows = ls if lr is None else lr
-            call = (lib().ggnn_query_async_labeled_in if lr is None
-                    else lib().ggnn_query_async_labeled_range)
+        if ls is not None or lr is not None or lm is not None:
+            # (sets, ranges or clauses: [Nq, width] / [Nq, n_ranges, 2] / [Nq, n_masks, 3], the same
+            # argument list)
+            if lm is not None:
+                rows, call = lm, lib().ggnn_query_async_labeled_mask
+            elif lr is not None:
+                rows, call = lr, lib().ggnn_query_async_labeled_range
+            else:
+                rows, call = ls, lib().ggnn_query_async_labeled_in
             for x in (rows, fi):
                 if x is not None and x.is_cuda:
                     torch.cuda.current_stream(x.device).synchronize()
@@ -911,7 +1048,7 @@ class GGNN:
                                                _dtype_code(t), dev, int(k_query), float(tau_query),
                                                int(max_iterations), int(measure), ids.data_ptr(),
                                                dists.data_ptr(), int(slot)))
-        ticket = QueryTicket(t, ids, dists, int(slot), fi, ls, lr)
+        ticket = QueryTicket(t, ids, dists, int(slot), fi, ls, lr, lm)
         held = self._inflight.setdefault(int(slot) % _ASYNC_SLOTS, [])
         if len(held) >= _MAX_TICKETS_PER_SLOT:
             # a serving loop that waits some other way (its own events, torch.cuda.synchronize)

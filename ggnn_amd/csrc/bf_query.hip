@@ -439,6 +439,7 @@ bool bf_mfma_supported(const BfLaunch& a);
 bool bf_mfma_uses_i8(const BfLaunch& a);
 void launch_bf_query_labelset(const BfLaunch& a, hipStream_t stream);  // bf_query_labelset.hip
 void launch_bf_query_labelrange(const BfLaunch& a, hipStream_t stream);  // bf_query_labelrange.hip
+void launch_bf_query_labelmask(const BfLaunch& a, hipStream_t stream);  // bf_query_labelmask.hip
 void launch_bf_query_mfma(const BfLaunch& a, hipStream_t stream);
 
 // scan of all queries (qlist == nullptr) or of the subset qlist[0, *qcount); slices > 1 needs
@@ -480,7 +481,7 @@ static void launch_bf_scan(const BfLaunch& a, uint32_t slices, uint32_t rows_per
                                 a.dists, qlist, qcount, stream);
 }
 
-// (shared with bf_query_labelset.hip and bf_query_labelrange.hip)
+// (shared with bf_query_labelset.hip, bf_query_labelrange.hip and bf_query_labelmask.hip)
 void bf_slice_rows(uint32_t N_base, uint32_t& slices, uint32_t& rows_per_slice)
 {
   const uint32_t row_quant = 64;  // multiple of ROWS*STEPS for every configuration
@@ -520,7 +521,11 @@ void launch_bf_query(const BfLaunch& a_in, hipStream_t stream)
     *a_in.matrix_path = 0;
   if (a_in.Nq == 0)
     return;
-  // label ranges, label sets: scan kernels of their own, no matrix-core form
+  // label masks, label ranges, label sets: scan kernels of their own, no matrix-core form
+  if (a_in.label_masks.labels) {
+    launch_bf_query_labelmask(a_in, stream);
+    return;
+  }
   if (a_in.label_ranges.labels) {
     launch_bf_query_labelrange(a_in, stream);
     return;

@@ -167,6 +167,18 @@ struct LabelRangeSpec {
   const int32_t* ranges{nullptr};  // [Nq x n_ranges x 2] (device)
   uint32_t n_ranges{0};            // 1 .. 4 (GGNN_MAX_LABEL_RANGES)
 };
+// Label masks (with a label column read as 32 tag bits): query n carries n_masks <= 2 clauses of
+// three int32 words, masks[(n * n_masks + j) * 3 + 0 .. 2] = (mask, value, any), and a base vector may
+// be given to it iff, for at least one clause, (label & mask) == value AND (any == 0 OR (label & any)
+// != 0).  (0, 0, 0) admits every row; a value with a bit outside its mask admits none (value is never
+// pre-masked); there is no wildcard value and no invalid clause.  A launch with labels != nullptr is
+// a label-mask launch; filter_bits, filter_table.ids and filter_bit_offset are what they are under
+// LabelSetSpec.
+struct LabelMaskSpec {
+  const int32_t* labels{nullptr};  // [>= offset + N_base] (device)
+  const int32_t* masks{nullptr};   // [Nq x n_masks x 3] (device)
+  uint32_t n_masks{0};             // 1 .. 2 (GGNN_MAX_LABEL_MASKS)
+};
 // the two constant rows for a launch that was given none (null if ids is null); free with
 // scratch_free(p, stream) after the launch
 uint32_t* filter_consts_scratch(const FilterTable& t, hipStream_t stream);
@@ -208,6 +220,8 @@ struct QueryLaunch {
   LabelSetSpec label_sets{};
   // label-range filters (labels != nullptr: see LabelRangeSpec)
   LabelRangeSpec label_ranges{};
+  // label-mask filters (labels != nullptr: see LabelMaskSpec)
+  LabelMaskSpec label_masks{};
 };
 void launch_query(const QueryLaunch& a, hipStream_t stream);
 
@@ -263,6 +277,8 @@ struct BfLaunch {
   LabelSetSpec label_sets{};
   // label-range filters (labels != nullptr: see LabelRangeSpec); always the scan
   LabelRangeSpec label_ranges{};
+  // label-mask filters (labels != nullptr: see LabelMaskSpec); always the scan
+  LabelMaskSpec label_masks{};
 };
 void launch_bf_query(const BfLaunch& a, hipStream_t stream);
 

@@ -471,17 +471,21 @@ struct QueryRequest {
 // Nq).  The three constructors validate against the handle; a search is filtered iff it is handed
 // one of these, never by anything the handle remembers.
 struct QueryFilter {
-  enum Kind { None, Bitset, TableIds, Labels, LabelSets, LabelRanges } kind{None};
+  enum Kind { None, Bitset, TableIds, Labels, LabelSets, LabelRanges, LabelMasks } kind{None};
   const void* ptr{nullptr};
   uint64_t count{0};
   ggnn_location loc{GGNN_CPU};
   int gpu{0};
   // LabelSets: ptr is the [Nq x width] label sets (count = Nq * width) and ids the filter id per
   // query ([Nq], or null: labels only), each with its own location.  LabelRanges: the same with
-  // ptr the [Nq x width x 2] (lo, hi) pairs, width = n_ranges (count = Nq * width * 2)
+  // ptr the [Nq x width x 2] (lo, hi) pairs, width = n_ranges (count = Nq * width * 2).  LabelMasks:
+  // ptr the [Nq x width x 3] (mask, value, any) clauses, width = n_masks (count = Nq * width * 3)
   uint32_t width{0};
   // int32 words of ptr per query
-  uint32_t stride() const { return kind == LabelRanges ? 2 * width : width; }
+  uint32_t stride() const
+  {
+    return kind == LabelMasks ? 3 * width : kind == LabelRanges ? 2 * width : width;
+  }
   const int32_t* ids{nullptr};
   ggnn_location ids_loc{GGNN_CPU};
   int ids_gpu{0};
@@ -500,18 +504,23 @@ struct QueryFilter {
   static QueryFilter label_ranges(const ggnn_handle& h, const int32_t* ranges, uint32_t n_ranges,
                                   uint64_t Nq, ggnn_location loc, int gpu, const int32_t* ids,
                                   ggnn_location ids_loc, int ids_gpu, bool read_host_ids = true);
+  // (no clause value is invalid: only n_masks is checked)
+  static QueryFilter label_masks(const ggnn_handle& h, const int32_t* masks, uint32_t n_masks,
+                                 uint64_t Nq, ggnn_location loc, int gpu, const int32_t* ids,
+                                 ggnn_location ids_loc, int ids_gpu, bool read_host_ids = true);
 };
 
 // A QueryFilter on one GPU, as a launch takes it (filter_bits / filter_table of QueryLaunch and
 // BfLaunch): bits is the bitset, the resident table (table.ids set) or the resident label column
 // (table.query_labels set); all null: unfiltered.  Label sets: set.labels is the resident label column
 // and bits / table.ids the resident table and the filter ids, or null; label ranges: the same with
-// `ranges` in place of `set`.
+// `ranges` in place of `set`; label masks: with `masks`.
 struct DeviceFilter {
   const uint32_t* bits{nullptr};
   FilterTable table{};
   LabelSetSpec set{};
   LabelRangeSpec ranges{};
+  LabelMaskSpec masks{};
   // ... of the queries from `first` on (a half-batch; a bitset is shared by all queries)
   DeviceFilter from(uint32_t first) const
   {
@@ -524,6 +533,8 @@ struct DeviceFilter {
       d.set.sets += static_cast<size_t>(first) * d.set.width;
     if (d.ranges.ranges)
       d.ranges.ranges += static_cast<size_t>(first) * d.ranges.n_ranges * 2;
+    if (d.masks.masks)
+      d.masks.masks += static_cast<size_t>(first) * d.masks.n_masks * 3;
     return d;
   }
 };
@@ -683,12 +694,13 @@ struct ggnn_handle {
   // the lane's stream (blocking lane: ctx.filter_stage / filter_ids_stage, a slot's lane: its
   // f_stage); the resident table or label column is placed if it is missing or stale
   DeviceFilter resolve_filter(DeviceCtx& ctx, const QueryFilter& f, int lane);
-  // label sets and label ranges: the resident column (`column`) and table, and the queries' int32
-  // rows (f.stride() words each, returned in `rows`) and ids in place or staged
+  // label sets, label ranges and label masks: the resident column (`column`) and table, and the
+  // queries' int32 rows (f.stride() words each, returned in `rows`) and ids in place or staged
   DeviceFilter resolve_label_rows(DeviceCtx& ctx, const QueryFilter& f, int lane,
                                   const int32_t*& column, const int32_t*& rows);
   DeviceFilter resolve_label_sets(DeviceCtx& ctx, const QueryFilter& f, int lane);
   DeviceFilter resolve_label_ranges(DeviceCtx& ctx, const QueryFilter& f, int lane);
+  DeviceFilter resolve_label_masks(DeviceCtx& ctx, const QueryFilter& f, int lane);
 
   // the search of local shard si for nq queries of request r, without work counters
   QueryLaunch shard_launch(const DeviceCtx& ctx, uint32_t si, const QueryRequest& r,

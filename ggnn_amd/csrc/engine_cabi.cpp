@@ -153,6 +153,27 @@ void seam_label_ranges(LAUNCH& l, const int32_t* labels, uint64_t n_labels,
   l.label_ranges.ranges = query_label_ranges;
   l.label_ranges.n_ranges = n_ranges;
 }
+
+// the label-mask arguments of the *_labeled_mask seam calls, likewise: fills label_masks,
+// filter_bits, filter_bit_offset and filter_table
+template <class LAUNCH>
+void seam_label_masks(LAUNCH& l, const int32_t* labels, uint64_t n_labels,
+                      const int32_t* query_label_masks, uint32_t n_masks,
+                      const uint32_t* filter_table, uint32_t num_filters, uint64_t n_bits,
+                      const int32_t* filter_ids, uint32_t filter_bit_offset, uint32_t N_base)
+{
+  GGNN_REQUIRE(n_masks >= 1 && n_masks <= GGNN_MAX_LABEL_MASKS, GGNN_INVALID_ARGUMENT,
+               "n_masks must be in [1, 2]");
+  GGNN_REQUIRE(query_label_masks != nullptr, GGNN_INVALID_ARGUMENT,
+               "the label mask array is null");
+  // (the column, the table and the ids: the checks and the fields of the label-set seam)
+  seam_label_sets(l, labels, n_labels, query_label_masks, 1, filter_table, num_filters, n_bits,
+                  filter_ids, filter_bit_offset, N_base);
+  l.label_sets = LabelSetSpec{};
+  l.label_masks.labels = labels;
+  l.label_masks.masks = query_label_masks;
+  l.label_masks.n_masks = n_masks;
+}
 }  // namespace
 
 extern "C" {
@@ -754,6 +775,62 @@ ggnn_status ggnn_query_async_labeled_range(ggnn_t* h, const void* query, uint64_
   });
 }
 
+ggnn_status ggnn_query_labeled_mask(ggnn_t* h, const void* query, uint64_t Nq, uint32_t D,
+                                    ggnn_dtype dtype, ggnn_location location, int gpu_id,
+                                    uint32_t k_query, float tau_query, uint32_t max_iterations,
+                                    ggnn_measure measure, int32_t* ids_out, float* dists_out,
+                                    ggnn_location out_location,
+                                    const int32_t* query_label_masks, uint32_t n_masks,
+                                    ggnn_location masks_location, int masks_gpu_id,
+                                    const int32_t* filter_ids, ggnn_location ids_location,
+                                    int ids_gpu_id)
+{
+  GGNN_NEED_HANDLE(h);
+  return guarded(h, [&] {
+    h->query({query, Nq, D, dtype, location, gpu_id, k_query, measure, ids_out, dists_out,
+              out_location, tau_query, max_iterations},
+             QueryFilter::label_masks(*h, query_label_masks, n_masks, Nq, masks_location,
+                                      masks_gpu_id, filter_ids, ids_location, ids_gpu_id));
+  });
+}
+
+ggnn_status ggnn_bf_query_labeled_mask(ggnn_t* h, const void* query, uint64_t Nq, uint32_t D,
+                                       ggnn_dtype dtype, ggnn_location location, int gpu_id,
+                                       uint32_t k_gt, ggnn_measure measure, int32_t* ids_out,
+                                       float* dists_out, ggnn_location out_location,
+                                       const int32_t* query_label_masks, uint32_t n_masks,
+                                       ggnn_location masks_location, int masks_gpu_id,
+                                       const int32_t* filter_ids, ggnn_location ids_location,
+                                       int ids_gpu_id)
+{
+  GGNN_NEED_HANDLE(h);
+  return guarded(h, [&] {
+    h->bf_query({query, Nq, D, dtype, location, gpu_id, k_gt, measure, ids_out, dists_out,
+                 out_location},
+                QueryFilter::label_masks(*h, query_label_masks, n_masks, Nq, masks_location,
+                                         masks_gpu_id, filter_ids, ids_location, ids_gpu_id));
+  });
+}
+
+ggnn_status ggnn_query_async_labeled_mask(ggnn_t* h, const void* query, uint64_t Nq, uint32_t D,
+                                          ggnn_dtype dtype, int gpu_id, uint32_t k_query,
+                                          float tau_query, uint32_t max_iterations,
+                                          ggnn_measure measure, int32_t* ids_out,
+                                          float* dists_out, uint32_t slot,
+                                          const int32_t* query_label_masks, uint32_t n_masks,
+                                          const int32_t* filter_ids)
+{
+  GGNN_NEED_HANDLE(h);
+  return guarded(h, [&] {
+    const QueryRequest r = async_request(query, Nq, D, dtype, gpu_id, k_query, tau_query,
+                                         max_iterations, measure, ids_out, dists_out);
+    // (clauses and ids live where the query lives and are not read on the host)
+    h->query_async(r, slot,
+                   QueryFilter::label_masks(*h, query_label_masks, n_masks, Nq, r.loc, r.gpu,
+                                            filter_ids, r.loc, r.gpu, /*read_host_ids=*/false));
+  });
+}
+
 ggnn_status ggnn_get_graph(ggnn_t* h, uint32_t global_shard_id, ggnn_graph_view* out)
 {
   GGNN_NEED_HANDLE(h);
@@ -1196,6 +1273,49 @@ ggnn_status ggnn_op_bf_query_labeled_range(const void* base, ggnn_dtype dtype, u
     BfLaunch b{base, query, dtype, N_base, D, Nq, k_query, measure, ids, dists};
     seam_label_ranges(b, labels, n_labels, query_label_ranges, n_ranges, filter_table, num_filters,
                       n_bits, filter_ids, filter_bit_offset, N_base);
+    launch_bf_query(b, static_cast<hipStream_t>(stream));
+  });
+}
+
+ggnn_status ggnn_op_query_labeled_mask(const void* base, ggnn_dtype dtype, uint32_t N_base,
+                                       uint32_t D, const uint8_t* codes, const float* params,
+                                       const void* query, uint32_t Nq, const int32_t* graph0,
+                                       uint32_t KBuild, const int32_t* start, uint32_t num_start,
+                                       const float* nn1_stats, uint32_t k_query, float tau_query,
+                                       uint32_t max_iterations, ggnn_measure measure,
+                                       uint32_t shards_per_gpu, uint32_t on_gpu_shard,
+                                       int32_t* ids, float* dists, uint32_t* n_dist,
+                                       uint32_t* n_pop, uint32_t* n_rows, const int32_t* labels,
+                                       uint64_t n_labels, const int32_t* query_label_masks,
+                                       uint32_t n_masks, const uint32_t* filter_table,
+                                       uint32_t num_filters, uint64_t n_bits,
+                                       const int32_t* filter_ids, uint32_t filter_bit_offset,
+                                       void* stream)
+{
+  return guarded(nullptr, [&] {
+    QueryLaunch q = seam_query(base, dtype, N_base, D, codes, params, query, Nq, graph0, KBuild,
+                               start, num_start, nn1_stats, k_query, tau_query, max_iterations,
+                               measure, shards_per_gpu, on_gpu_shard, ids, dists, n_dist, n_pop,
+                               n_rows);
+    seam_label_masks(q, labels, n_labels, query_label_masks, n_masks, filter_table, num_filters,
+                     n_bits, filter_ids, filter_bit_offset, N_base);
+    launch_query(q, static_cast<hipStream_t>(stream));
+  });
+}
+
+ggnn_status ggnn_op_bf_query_labeled_mask(const void* base, ggnn_dtype dtype, uint32_t N_base,
+                                          uint32_t D, const void* query, uint32_t Nq,
+                                          uint32_t k_query, ggnn_measure measure, int32_t* ids,
+                                          float* dists, const int32_t* labels, uint64_t n_labels,
+                                          const int32_t* query_label_masks, uint32_t n_masks,
+                                          const uint32_t* filter_table, uint32_t num_filters,
+                                          uint64_t n_bits, const int32_t* filter_ids,
+                                          uint32_t filter_bit_offset, void* stream)
+{
+  return guarded(nullptr, [&] {
+    BfLaunch b{base, query, dtype, N_base, D, Nq, k_query, measure, ids, dists};
+    seam_label_masks(b, labels, n_labels, query_label_masks, n_masks, filter_table, num_filters,
+                     n_bits, filter_ids, filter_bit_offset, N_base);
     launch_bf_query(b, static_cast<hipStream_t>(stream));
   });
 }

@@ -78,6 +78,7 @@ QueryLaunch ggnn_handle::shard_launch(const DeviceCtx& ctx, uint32_t si, const Q
   ql.filter_table = df.table;
   ql.label_sets = df.set;
   ql.label_ranges = df.ranges;
+  ql.label_masks = df.masks;
   return ql;
 }
 
@@ -527,6 +528,7 @@ void ggnn_handle::bf_query(const QueryRequest& r, const QueryFilter& filter)
   bl.filter_table = df.table;
   bl.label_sets = df.set;
   bl.label_ranges = df.ranges;
+  bl.label_masks = df.masks;
   // (one launch over the whole base: "every shard" is this launch)
   last_bf_matrix_path = 0;
   bl.matrix_path = &last_bf_matrix_path;
@@ -632,9 +634,33 @@ QueryFilter QueryFilter::label_ranges(const ggnn_handle& h, const int32_t* range
   return f;
 }
 
-// label sets and label ranges -- a per-query int32 array of f.stride() words, plus optional ids: the
-// resident column and (with filter ids) the resident table; the rows and the ids are used in place
-// on their own GPU, else staged behind one another in the lane's id stage
+QueryFilter QueryFilter::label_masks(const ggnn_handle& h, const int32_t* masks, uint32_t n_masks,
+                                     uint64_t Nq, ggnn_location loc, int gpu, const int32_t* ids,
+                                     ggnn_location ids_loc, int ids_gpu, bool read_host_ids)
+{
+  GGNN_REQUIRE(n_masks >= 1 && n_masks <= GGNN_MAX_LABEL_MASKS, GGNN_INVALID_ARGUMENT,
+               "n_masks " + std::to_string(n_masks) + " is outside [1, " +
+                   std::to_string(GGNN_MAX_LABEL_MASKS) + "]");
+  GGNN_REQUIRE(masks != nullptr, GGNN_INVALID_ARGUMENT, "the label mask array is null");
+  GGNN_REQUIRE(!h.labels_host.empty(), GGNN_INVALID_STATE,
+               "There are no labels the label masks could refer to (ggnn_set_labels).");
+  QueryFilter f{LabelMasks, masks, Nq * n_masks * 3, loc, gpu};
+  f.width = n_masks;
+  if (ids) {
+    // (the rules of the filter ids of ggnn_query_filtered_by)
+    const QueryFilter t = table_ids(h, ids, Nq, ids_loc, ids_gpu, read_host_ids);
+    f.ids = ids;
+    f.ids_loc = t.loc;
+    f.ids_gpu = t.gpu;
+  }
+  GGNN_REQUIRE(h.base_dtype != GGNN_I8, GGNN_UNSUPPORTED,
+               "label masks are not built for int8 bases");
+  return f;
+}
+
+// label sets, label ranges and label masks -- a per-query int32 array of f.stride() words, plus
+// optional ids: the resident column and (with filter ids) the resident table; the rows and the ids
+// are used in place on their own GPU, else staged behind one another in the lane's id stage
 DeviceFilter ggnn_handle::resolve_label_rows(DeviceCtx& ctx, const QueryFilter& f, int lane,
                                              const int32_t*& column, const int32_t*& rows)
 {
@@ -693,6 +719,14 @@ DeviceFilter ggnn_handle::resolve_label_ranges(DeviceCtx& ctx, const QueryFilter
   return d;
 }
 
+DeviceFilter ggnn_handle::resolve_label_masks(DeviceCtx& ctx, const QueryFilter& f, int lane)
+{
+  const int32_t *column = nullptr, *rows = nullptr;
+  DeviceFilter d = resolve_label_rows(ctx, f, lane, column, rows);
+  d.masks = LabelMaskSpec{column, rows, f.width};
+  return d;
+}
+
 DeviceFilter ggnn_handle::resolve_filter(DeviceCtx& ctx, const QueryFilter& f, int lane)
 {
   DeviceFilter d;
@@ -702,6 +736,8 @@ DeviceFilter ggnn_handle::resolve_filter(DeviceCtx& ctx, const QueryFilter& f, i
     return resolve_label_sets(ctx, f, lane);
   if (f.kind == QueryFilter::LabelRanges)
     return resolve_label_ranges(ctx, f, lane);
+  if (f.kind == QueryFilter::LabelMasks)
+    return resolve_label_masks(ctx, f, lane);
   // what is resident: the filter table, or the label column (the kernels read it through
   // filter_bits, common.hpp: the only place that casts it)
   if (f.kind == QueryFilter::TableIds) {
@@ -737,6 +773,7 @@ DeviceFilter ggnn_handle::resolve_filter(DeviceCtx& ctx, const QueryFilter& f, i
     case QueryFilter::Labels: d.table.query_labels = static_cast<const int32_t*>(here); break;
     case QueryFilter::LabelSets:
     case QueryFilter::LabelRanges:
+    case QueryFilter::LabelMasks:
     case QueryFilter::None: break;
   }
   return d;

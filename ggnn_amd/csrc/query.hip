@@ -210,7 +210,7 @@ void launch_query(const QueryLaunch& a, hipStream_t stream)
                            a.KBuild <= 8 * kEarlySteps && hook(kHookQueryEarly) != 0 &&
                            hook(kHookQueryGlobalRing) != 0 && early_shape && set_shape;
   // (the filtered kernels keep their ring in LDS: no scratch)
-  if (!a.filter_bits && !a.label_sets.labels && !a.label_ranges.labels &&
+  if (!a.filter_bits && !a.label_sets.labels && !a.label_ranges.labels && !a.label_masks.labels &&
       (global_ring || (args.sorted <= 64 && set_shape && tag_set_usable(vis, a.N_base) &&
                        hook(kHookVisTagSet) != 0))) {
     args.tag_bits = global_ring ? 0 : tag_set_bucket_bits(vis);
@@ -239,7 +239,16 @@ void launch_query(const QueryLaunch& a, hipStream_t stream)
     args.ps_lossless = (a.ps_lossless && a.measure == GGNN_EUCLIDEAN && hook(kHookPsExact) != 0) ? 1u : 0u;
   }
 
-  if (a.label_ranges.labels) {
+  if (a.label_masks.labels) {
+    // the label's tag bits under one of up to 2 clauses per query, with an optional filter id
+    // (query_labelmask.hip)
+    GGNN_REQUIRE(!a.label_sets.labels && !a.label_ranges.labels, GGNN_INVALID_ARGUMENT,
+                 "label masks cannot be combined with label sets or label ranges in one launch");
+    args.filter_bits = a.filter_bits;
+    args.filter_bit_offset = a.filter_bit_offset;
+    launch_query_labelmask(args, a.filter_table, a.label_masks, use_ps, a.measure, a.dtype, stream);
+  }
+  else if (a.label_ranges.labels) {
     // the label in one of up to 4 intervals per query, with an optional filter id
     // (query_labelrange.hip)
     GGNN_REQUIRE(!a.label_sets.labels, GGNN_INVALID_ARGUMENT,

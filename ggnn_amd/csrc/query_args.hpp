@@ -57,4 +57,10 @@ struct LabelRangeQueryArgs : FilteredQueryArgs {
   LabelRangeSpec range;
 };
 
+// Arguments of the label-mask kernels (query_labelmask.hip), likewise: the label column and the
+// queries' clauses beside the optional filter table.
+struct LabelMaskQueryArgs : FilteredQueryArgs {
+  LabelMaskSpec mask;
+};
+
 }  // namespace ggnn_amd

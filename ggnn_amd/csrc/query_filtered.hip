@@ -34,6 +34,11 @@
 // LabelRangeFilter): the same once more, query_labelrange_kernel* under GGNN_LABELRANGE_TU --
 // query_labelrange.hip, query_labelrange_16.hip -- with LabelRangeQueryArgs; no int8 unit and no
 // PrescreenExact variant either.
+//
+// Label masks (the label's tag bits under one of up to 2 (mask, value, any) clauses per query, with an
+// optional filter id: LabelMaskFilter): and once more, query_labelmask_kernel* under GGNN_LABELMASK_TU
+// -- query_labelmask.hip, query_labelmask_16.hip -- with LabelMaskQueryArgs; no int8 unit and no
+// PrescreenExact variant.
 #include <algorithm>
 
 #include "query_wave.hpp"
@@ -155,12 +160,46 @@ __global__ void __launch_bounds__(kWave) query_labelrange_kernel_lds(const Label
 #include "query_wave_lds_body.inc"
 }
 
+// Label masks.  LabelMaskFilter keeps per lane what LabelRangeFilter keeps (key, label, bitset word)
+// and per wave two (mask, value, any) clauses where that has four (lo, span) pairs: six scalars for
+// eight; the verdict is two ands and two compares per clause and a scalar test of any == 0.  The occupancy
+// follows the rule of labelrange_waves -- the largest at which the kernel's private segment is 0, read
+// from the built code object -- and the build gives the same answer: 6 waves for the pre-screened
+// early-rows kernels, 7 for the others (tests/test_label_masks.py).
+template <class PSC, bool EARLY>
+constexpr int labelmask_waves()
+{
+  return labelrange_waves<PSC, EARLY>();
+}
+
+template <typename BaseT, int LPR, int NCH, int R, int MODE, class PSC, int HB = 0, bool EARLY = false>
+__global__ void __launch_bounds__(kWave) __attribute__((
+    amdgpu_waves_per_eu((R == 1 && NCH <= 3) ? labelmask_waves<PSC, EARLY>() : 1)))
+query_labelmask_kernel(const LabelMaskQueryArgs a)
+{
+  static_assert(HB >= 0, "the filtered kernels keep their visited ring in LDS");
+  static_assert(!PsExact<PSC>::value, "label masks: no kernels of exact distances from codes");
+  using FILT = LabelMaskFilter;
+  constexpr bool GR = false;
+#include "query_wave_body.inc"
+}
+
+// the LDS-resident list (SORTED > 2048, or > 512 with the pre-screen)
+template <typename BaseT, int LPR, int NCH, int MODE, class PSC>
+__global__ void __launch_bounds__(kWave) query_labelmask_kernel_lds(const LabelMaskQueryArgs a)
+{
+  using FILT = LabelMaskFilter;
+#include "query_wave_lds_body.inc"
+}
+
 // the kernel templates of a filter class
 template <class FILT, typename BaseT, int LPR, int NCH, int R, int MODE, class PSC, int HB = 0,
           bool EARLY = false>
 constexpr auto filtered_kernel()
 {
-  if constexpr (std::is_same<FILT, LabelRangeFilter>::value)
+  if constexpr (std::is_same<FILT, LabelMaskFilter>::value)
+    return &query_labelmask_kernel<BaseT, LPR, NCH, R, MODE, PSC, HB, EARLY>;
+  else if constexpr (std::is_same<FILT, LabelRangeFilter>::value)
     return &query_labelrange_kernel<BaseT, LPR, NCH, R, MODE, PSC, HB, EARLY>;
   else if constexpr (std::is_same<FILT, LabelSetFilter>::value)
     return &query_labelset_kernel<BaseT, LPR, NCH, R, MODE, PSC, HB, EARLY>;
@@ -172,7 +211,9 @@ constexpr auto filtered_kernel()
 template <class FILT, typename BaseT, int LPR, int NCH, int MODE, class PSC>
 constexpr auto filtered_kernel_lds()
 {
-  if constexpr (std::is_same<FILT, LabelRangeFilter>::value)
+  if constexpr (std::is_same<FILT, LabelMaskFilter>::value)
+    return &query_labelmask_kernel_lds<BaseT, LPR, NCH, MODE, PSC>;
+  else if constexpr (std::is_same<FILT, LabelRangeFilter>::value)
     return &query_labelrange_kernel_lds<BaseT, LPR, NCH, MODE, PSC>;
   else if constexpr (std::is_same<FILT, LabelSetFilter>::value)
     return &query_labelset_kernel_lds<BaseT, LPR, NCH, MODE, PSC>;
@@ -185,7 +226,8 @@ constexpr auto filtered_kernel_lds()
 // the kernel of one row layout, measure and pre-screen (launch_query_cfg, query_wave.hpp)
 template <class FILT>
 struct FilteredLadder {
-  // (ARGS: FilteredQueryArgs, or LabelSetQueryArgs / LabelRangeQueryArgs under their filters)
+  // (ARGS: FilteredQueryArgs, or LabelSetQueryArgs / LabelRangeQueryArgs / LabelMaskQueryArgs under
+  // their filters)
   template <typename BaseT, int LPR, int NCH, int MODE, class PSC, class ARGS>
   static void launch(const ARGS& args, hipStream_t stream)
   {
@@ -196,9 +238,10 @@ struct FilteredLadder {
       if (hb != 0 && args.KBuild <= 8 * kEarlySteps && hook(kHookQueryEarly) != 0) {
         const size_t qrow = DistEngine<BaseT, LPR, NCH, PSC::enabled>::kQueryLdsBytes;
         // (PSX: the two-phase variant for a base known to be lossless, as in QueryLadder)
-        // (label sets and ranges have no such variant: PSX = PSC and `exact` is false)
+        // (label sets, ranges and masks have no such variant: PSX = PSC and `exact` is false)
         using PSX = std::conditional_t<std::is_same<FILT, LabelSetFilter>::value ||
-                                           std::is_same<FILT, LabelRangeFilter>::value,
+                                           std::is_same<FILT, LabelRangeFilter>::value ||
+                                           std::is_same<FILT, LabelMaskFilter>::value,
                                        PSC, typename ExactOf<PSC>::type>;
         const bool exact = args.ps_lossless != 0 && !std::is_same<PSX, PSC>::value;
         if (hb == 1)
@@ -229,7 +272,49 @@ using TuFilter = LabelFilter;
 using TuFilter = IdFilter;
 #endif
 
-#ifdef GGNN_LABELRANGE_TU
+#ifdef GGNN_LABELMASK_TU
+#ifdef GGNN_ROWS_16_TU
+void launch_query_labelmask_16(const LabelMaskQueryArgs& args, ggnn_measure measure,
+                               ggnn_dtype dtype, hipStream_t stream)
+{
+#define GGNN_LAUNCH_QF(T, LPR, NCH) \
+  launch_query_cfg<FilteredLadder<LabelMaskFilter>, T, LPR, NCH>(args, false, measure, stream)
+  GGNN_DISPATCH_DIST_16(dtype, args.D, GGNN_LAUNCH_QF);
+#undef GGNN_LAUNCH_QF
+}
+#else
+// base: filled by launch_query (query.hip); table: the filter table in base.filter_bits (or null)
+// and the filter id per query (or null); mask: the label column and the queries' clauses
+void launch_query_labelmask(const QueryArgs& base, const FilterTable& table,
+                            const LabelMaskSpec& mask, bool use_ps, ggnn_measure measure,
+                            ggnn_dtype dtype, hipStream_t stream)
+{
+  GGNN_REQUIRE(mask.labels != nullptr && mask.masks != nullptr, GGNN_INVALID_ARGUMENT,
+               "the label column or the label masks are missing");
+  GGNN_REQUIRE(mask.n_masks >= 1 && mask.n_masks <= kMaxLabelMasks, GGNN_INVALID_ARGUMENT,
+               "a query has 1 or 2 label mask clauses");
+  GGNN_REQUIRE(!table.query_labels, GGNN_INVALID_ARGUMENT,
+               "label masks exclude the one-label form");
+  GGNN_REQUIRE(!table.ids || !table.num_filters || (base.filter_bits && table.words),
+               GGNN_INVALID_ARGUMENT, "filter ids into a table need the table");
+  GGNN_REQUIRE(dtype != GGNN_I8, GGNN_UNSUPPORTED, "label masks are not built for int8 rows");
+  GGNN_REQUIRE(base.N_base <= kMaxLabeledShardRows, GGNN_UNSUPPORTED,
+               "label filters need shards of at most 2^30 base vectors");
+  LabelMaskQueryArgs args{};
+  static_cast<QueryArgs&>(args) = base;
+  args.filter_table = table;
+  args.mask = mask;
+  if (dtype_is_16bit(dtype)) {
+    launch_query_labelmask_16(args, measure, dtype, stream);
+    return;
+  }
+#define GGNN_LAUNCH_QF(T, LPR, NCH) \
+  launch_query_cfg<FilteredLadder<LabelMaskFilter>, T, LPR, NCH>(args, use_ps, measure, stream)
+  GGNN_DISPATCH_DIST_32_8(dtype, args.D, GGNN_LAUNCH_QF);
+#undef GGNN_LAUNCH_QF
+}
+#endif
+#elif defined(GGNN_LABELRANGE_TU)
 #ifdef GGNN_ROWS_16_TU
 void launch_query_labelrange_16(const LabelRangeQueryArgs& args, ggnn_measure measure,
                                 ggnn_dtype dtype, hipStream_t stream)

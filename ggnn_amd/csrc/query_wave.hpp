@@ -21,7 +21,9 @@ GGNN_DEV void load_prescreen(PSC& ps, const QueryArgs& a, const BaseT* qrow)
 template <class FILT, class ARGS>
 GGNN_DEV FILT wave_filter(const ARGS& a, const uint32_t n)
 {
-  if constexpr (std::is_same<FILT, LabelRangeFilter>::value)
+  if constexpr (std::is_same<FILT, LabelMaskFilter>::value)
+    return LabelMaskFilter(a.filter_bits, a.filter_bit_offset, a.filter_table, a.mask, n);
+  else if constexpr (std::is_same<FILT, LabelRangeFilter>::value)
     return LabelRangeFilter(a.filter_bits, a.filter_bit_offset, a.filter_table, a.range, n);
   else if constexpr (std::is_same<FILT, LabelSetFilter>::value)
     return LabelSetFilter(a.filter_bits, a.filter_bit_offset, a.filter_table, a.set, n);
@@ -186,5 +188,11 @@ void launch_query_labelrange(const QueryArgs& base, const FilterTable& table,
                              ggnn_dtype dtype, hipStream_t stream);
 void launch_query_labelrange_16(const LabelRangeQueryArgs& args, ggnn_measure measure,
                                 ggnn_dtype dtype, hipStream_t stream);
+// Label masks (LabelMaskFilter): query_labelmask / query_labelmask_16, likewise without int8
+void launch_query_labelmask(const QueryArgs& base, const FilterTable& table,
+                            const LabelMaskSpec& mask, bool use_ps, ggnn_measure measure,
+                            ggnn_dtype dtype, hipStream_t stream);
+void launch_query_labelmask_16(const LabelMaskQueryArgs& args, ggnn_measure measure,
+                               ggnn_dtype dtype, hipStream_t stream);
 
 }  // namespace ggnn_amd

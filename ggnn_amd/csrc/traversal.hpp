@@ -2038,6 +2038,86 @@ struct LabelRangeFilter {
   }
 };
 
+// Label-mask filters: the label of a base row read as 32 tag bits.  Query n carries up to
+// kMaxLabelMasks clauses (mask, value, any) and, optionally, a filter id into a filter table; a
+// candidate is denied iff it passes none of the clauses, or its bit of the query's table row is
+// clear (LabelMaskSpec, common.hpp).  A row passes a clause iff
+//   (label & mask) == value  &&  (any == 0 || (label & any) != 0)
+// `value` is compared as it was given, never pre-masked: a value with a bit outside its mask admits
+// nothing, by definition.  There is no wildcard value, no invalid clause and nothing to normalise:
+// (0, 0, 0) admits every row and bit 31 is a bit like any other.  request() is LabelRangeFilter's --
+// the label dword, then the bitset word, in front of the first-read rows -- and the verdict is taken
+// once per fetch at the replay, without a branch (| and & on the lane masks, not || and &&).  The
+// wave constructor, scalar and in front of the loop, pads a one-clause query by repeating that
+// clause.  mask[], value[] and any[] are wave-uniform: six scalar registers where LabelRangeFilter
+// has the eight of lo[4] and span[4].  `any == 0` is a scalar compare at the verdict, not a stored
+// word free = (any == 0) for ((label & any) | free) != 0: with every scalar register of these kernels
+// taken, the compiler keeps two such words in VECTOR registers for the whole loop, and the headline
+// kernels then need 77 / 79 registers where they need 75 / 77 like their label-range siblings
+// without (read from the code object).
+constexpr uint32_t kMaxLabelMasks = 2;  // GGNN_MAX_LABEL_MASKS
+struct LabelMaskFilter {
+  static constexpr bool enabled = true;
+  const int32_t* labels;  // the column at the shard's first global id
+  const uint32_t* bits;   // the query's row of the table, or one of the constant words
+  uint32_t offset;        // first global id of the shard (bit offset)
+  uint32_t imask;         // ~3u: `bits` is a row;  0: it is one word
+  uint32_t mask[kMaxLabelMasks], value[kMaxLabelMasks], any[kMaxLabelMasks];
+  int key;               // the candidate this lane asked for (or EMPTY)
+  uint32_t word, bword;  // its label, its word of the bitset
+  // the filter of the wave of query n (scalar: the query number is wave-uniform)
+  GGNN_DEV LabelMaskFilter(const uint32_t* table, const uint32_t shard_offset, const FilterTable& t,
+                           const LabelMaskSpec& s, const uint32_t n)
+      : labels(s.labels + shard_offset), bits(kFilterConstWords<>), offset(shard_offset), imask(0u),
+        key(kEmptyKey), word(0u), bword(0u)
+  {
+    const int32_t* c = s.masks + static_cast<size_t>(n) * s.n_masks * 3;
+#pragma unroll
+    for (uint32_t j = 0; j < kMaxLabelMasks; ++j) {
+      const uint32_t jj = j < s.n_masks ? j : 0u;
+      mask[j] = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(c[3 * jj]));
+      value[j] = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(c[3 * jj + 1]));
+      any[j] = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(c[3 * jj + 2]));
+    }
+    if (t.ids) {
+      const int32_t f = __builtin_amdgcn_readfirstlane(t.ids[n]);
+      if (static_cast<uint32_t>(f) < t.num_filters) {
+        bits = table + static_cast<size_t>(static_cast<uint32_t>(f)) * t.words;
+        imask = ~3u;
+      }
+      else if (f != -1)
+        bits = kFilterConstWords<> + 1;
+    }
+  }
+  GGNN_DEV void request(const int cand)
+  {
+    key = cand;
+    // EMPTY slots read the label and the bitset word of the shard's first id (verdict ignored)
+    const uint32_t c = static_cast<uint32_t>(max(cand, 0));
+    word = filter_word_at(labels, c << 2);
+    bword = filter_word_at(bits, ((c + offset) >> 3) & imask);
+  }
+  // does a row with label w pass one of the clauses
+  GGNN_DEV bool passes(const uint32_t w) const
+  {
+    bool one = false;
+#pragma unroll
+    for (uint32_t j = 0; j < kMaxLabelMasks; ++j)
+      one = one | (((w & mask[j]) == value[j]) & (((w & any[j]) != 0u) | (any[j] == 0u)));
+    return one;
+  }
+  // lanes whose candidate is denied
+  GGNN_DEV unsigned long long denied_lanes() const
+  {
+    const uint32_t b = static_cast<uint32_t>(key) + offset;
+    return __ballot(key != kEmptyKey && (!passes(word) || !((bword >> (b & 31u)) & 1u)));
+  }
+  GGNN_DEV bool denied(const unsigned long long dl, const int k) const
+  {
+    return (__ballot(key == k) & dl) != 0ull;
+  }
+};
+
 // One candidate of a replay (simple_knn_cache.cuh:283-285): pushed if it still beats the criteria,
 // which the pushes before it may have tightened.  One-register lists take the test, and the
 // duplicate test of push(), into the masks of push_if(): the loop around this is then ONE basic block

@@ -501,6 +501,73 @@ def bf_query_labeled_range(base, query, k_query, labels, label_ranges, filter_ta
     return ids, dists
 
 
+MAX_LABEL_MASKS = 2  # GGNN_MAX_LABEL_MASKS
+
+
+def _need_label_masks(labels, label_masks, filter_table, filter_ids, Nq, n_min):
+    """the label-mask arguments of a seam call as the C-ABI takes them: (labels ptr, n_labels,
+    clauses ptr, n_masks, table ptr, F, n_bits, ids ptr)"""
+    _need(label_masks, torch.int32, "label_masks")
+    if label_masks.dim() != 3 or label_masks.shape[0] != Nq or label_masks.shape[2] != 3 or \
+            not 1 <= label_masks.shape[1] <= MAX_LABEL_MASKS:
+        raise ValueError(f"label_masks must be [Nq, 1..{MAX_LABEL_MASKS}, 3]")
+    return _need_label_rows(labels, label_masks, label_masks.shape[1], filter_table, filter_ids,
+                            Nq, n_min)
+
+
+def query_labeled_mask(base, query, graph0, start, nn1_stats, k_query, tau_query, labels,
+                       label_masks, filter_table=None, filter_ids=None, max_iterations=400,
+                       measure=EUCLIDEAN, bit_offset=0, shards_per_gpu=1, on_gpu_shard=0,
+                       counters=False, prescreen=None, rows_read=None):
+    """`query_labeled_range` with label MASKS in place of label ranges: the label is read as 32 tag
+    bits, label_masks is [Nq, 1..2, 3] int32, clauses (mask, value, any), and query n may be given
+    the rows whose label L = labels[i + bit_offset] has (L & mask) == value and (any == 0 or
+    (L & any) != 0) for one of its clauses AND whose bit i + bit_offset of row filter_ids[n] of
+    filter_table is set -- id -1 admits every row, any other id outside [0, F) none.  value is
+    never pre-masked (a bit outside mask admits nothing); there is no wildcard value.
+    filter_ids=None: clauses only (filter_table is then not read)."""
+    _need(base, name="base"), _need(query, base.dtype, "query")
+    _need(graph0, torch.int32, "graph0"), _need(start, torch.int32, "start")
+    _need(nn1_stats, torch.float32, "nn1_stats")
+    Nq = query.shape[0]
+    tail = _need_label_masks(labels, label_masks, filter_table, filter_ids, Nq,
+                             bit_offset + base.shape[0])
+    ids = torch.empty((Nq, k_query * shards_per_gpu), dtype=torch.int32, device=base.device)
+    dists = torch.empty((Nq, k_query * shards_per_gpu), dtype=torch.float32, device=base.device)
+    nd = npop = None
+    if counters:
+        nd = torch.zeros(Nq, dtype=torch.int32, device=base.device)
+        npop = torch.zeros(Nq, dtype=torch.int32, device=base.device)
+    codes, params = prescreen if prescreen is not None else (None, None)
+    if prescreen is not None:
+        _need(base, torch.float32, "base"), _need(codes, torch.uint8, "codes")
+        _need(params, torch.float32, "params")
+    check(lib().ggnn_op_query_labeled_mask(
+        _ptr(base), _dtype_code(base), base.shape[0], base.shape[1], _ptr(codes), _ptr(params),
+        _ptr(query), Nq, _ptr(graph0), graph0.shape[1], _ptr(start), start.numel(),
+        _ptr(nn1_stats), k_query, tau_query, max_iterations, measure, shards_per_gpu,
+        on_gpu_shard, _ptr(ids), _ptr(dists), _ptr(nd), _ptr(npop), _ptr(rows_read),
+        *tail, bit_offset, _stream()))
+    if counters:
+        return ids, dists, nd, npop
+    return ids, dists
+
+
+def bf_query_labeled_mask(base, query, k_query, labels, label_masks, filter_table=None,
+                          filter_ids=None, measure=EUCLIDEAN, bit_offset=0):
+    """`bf_query_filtered` under label masks (see query_labeled_mask); always the scan kernels"""
+    _need(base, name="base"), _need(query, base.dtype, "query")
+    Nq = query.shape[0]
+    tail = _need_label_masks(labels, label_masks, filter_table, filter_ids, Nq,
+                             bit_offset + base.shape[0])
+    ids = torch.empty((Nq, k_query), dtype=torch.int32, device=base.device)
+    dists = torch.empty((Nq, k_query), dtype=torch.float32, device=base.device)
+    check(lib().ggnn_op_bf_query_labeled_mask(
+        _ptr(base), _dtype_code(base), base.shape[0], base.shape[1], _ptr(query), Nq, k_query,
+        measure, _ptr(ids), _ptr(dists), *tail, bit_offset, _stream()))
+    return ids, dists
+
+
 def pack_filters(masks):
     """[F, N] boolean CUDA masks -> [F, ceil(N / 32)] int32 bitset words on the same GPU (bit
     i & 31 of word i >> 5 is mask i; padding bits zero)"""

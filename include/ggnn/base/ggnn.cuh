@@ -253,6 +253,45 @@ class GGNN {
     return r;
   }
 
+  // Label masks (ggnn_query_labeled_mask): the label read as 32 tag bits.  Query n is given the base
+  // vectors whose label passes one of its n_masks clauses (label_masks[(n * n_masks + j) * 3 + 0 .. 2])
+  // = (mask, value, any), 1 <= n_masks <= GGNN_MAX_LABEL_MASKS -- (label & mask) == value and (any == 0
+  // or (label & any) != 0); value is never pre-masked and there is no wildcard value -- AND whose bit
+  // is set in row filter_ids[n] of the table (-1: every vector; filter_ids == nullptr: no bitset).
+  // Host memory.
+  [[nodiscard]] virtual Results queryLabeledMask(
+      const GenericDataset& query, const uint32_t KQuery, const float tau_query,
+      const int32_t* label_masks, const uint32_t n_masks, const int32_t* filter_ids = nullptr,
+      const uint32_t max_iterations = 400,
+      const DistanceMeasure measure = DistanceMeasure::Euclidean)
+  {
+    const uint32_t width = on_gpu_ ? KQuery * num_shards() : KQuery;
+    Results r = make_results(query, width);
+    detail::check(
+        ggnn_query_labeled_mask(h_, query.raw(), query.N, query.D, dtype_of(query),
+                                loc_of(query), query.gpu_id, KQuery, tau_query, max_iterations,
+                                static_cast<ggnn_measure>(measure), r.ids.data(), r.dists.data(),
+                                on_gpu_ ? GGNN_GPU : GGNN_CPU, label_masks, n_masks, GGNN_CPU, 0,
+                                filter_ids, GGNN_CPU, 0),
+        h_);
+    return r;
+  }
+  [[nodiscard]] virtual Results bfQueryLabeledMask(
+      const GenericDataset& query, const int32_t* label_masks, const uint32_t n_masks,
+      const int32_t* filter_ids = nullptr, const uint32_t KGT = 100,
+      const DistanceMeasure measure = DistanceMeasure::Euclidean)
+  {
+    Results r = make_results(query, KGT);
+    detail::check(
+        ggnn_bf_query_labeled_mask(h_, query.raw(), query.N, query.D, dtype_of(query),
+                                   loc_of(query), query.gpu_id, KGT,
+                                   static_cast<ggnn_measure>(measure), r.ids.data(),
+                                   r.dists.data(), on_gpu_ ? GGNN_GPU : GGNN_CPU, label_masks,
+                                   n_masks, GGNN_CPU, 0, filter_ids, GGNN_CPU, 0),
+        h_);
+    return r;
+  }
+
   [[nodiscard]] virtual const Graph& getGraph(const uint32_t global_shard_id = 0)
   {
     ggnn_graph_view v{};

@@ -372,6 +372,60 @@ ggnn_status ggnn_query_async_labeled_range(ggnn_t* h, const void* query, uint64_
                                            const int32_t* query_label_ranges, uint32_t n_ranges,
                                            const int32_t* filter_ids);
 
+/* Label masks: the label of a base vector read as 32 TAG BITS, combined with a filter id.
+ * Query n carries n_masks clauses -- row n of query_label_masks[Nq x n_masks x 3], int32 triples
+ * (mask, value, any), 1 <= n_masks <= GGNN_MAX_LABEL_MASKS -- and, optionally, a filter id
+ * filter_ids[n] into the resident filter table of ggnn_set_filters (the whole array may be null).
+ * Base vector i passes a clause iff
+ *   (labels[i] & mask) == value  AND  (any == 0 OR (labels[i] & any) != 0)
+ * and may be reported to query n iff it passes at least one of the query's clauses AND the filter id
+ * admits i under the rules of ggnn_query_filtered_by: -1 or a null array admits every vector, an id
+ * in [0, num_filters) needs the vector's bit in that row, any other id admits none.
+ * Query n gives, bit for bit (ids, distances, counters), the result of ggnn_query_filtered /
+ * ggnn_bf_query_filtered of that query with the bitset
+ *   any_j(((labels & mask_j) == value_j) & ((any_j == 0) | ((labels & any_j) != 0))) & row(filter_ids[n]);
+ * an empty predicate gives every slot (-1 + id offset, +inf).
+ *   (0, 0, 0) admits every vector.  There is NO WILDCARD value.  Bit 31 is a bit like any other.
+ *   A clause whose value has a bit outside its mask admits NOTHING: that is the definition, not an
+ *   error, and value is never pre-masked.  No clause value is invalid.  A short list is padded by
+ *   repeating a clause.
+ * One clause says "all of A, none of B, any of C" as mask = A | B, value = A, any = C, and "field
+ * equals v" with mask = the field's bits, value = v at the field's position; two clauses say "mine or
+ * public".  (~0, L, 0) with null ids is ggnn_query_labeled with label L != -1.
+ * The clauses follow the memory rules of query_label_ranges and the ids those of filter_ids in the
+ * *_labeled_range calls (ggnn_query_async_labeled_mask: both live where the query lives and are not
+ * read on the host).  GGNN_INVALID_ARGUMENT for n_masks outside [1, 2], a null clause array and
+ * host-resident ids outside [-1, num_filters); GGNN_INVALID_STATE without labels, and with ids but
+ * no filter table; GGNN_UNSUPPORTED on an int8 base and for shards of more than 2^30 vectors.
+ * Everything else is ggnn_query / ggnn_bf_query.  ggnn_bf_query_labeled_mask always runs the scan
+ * kernels: ggnn_last_bf_query_matrix_path reports 0.
+ * What remains: at most 2 clauses per query, one int32 column, no int8 rows, no matrix-core path. */
+#define GGNN_MAX_LABEL_MASKS 2
+ggnn_status ggnn_query_labeled_mask(ggnn_t* h, const void* query, uint64_t Nq, uint32_t D,
+                                    ggnn_dtype dtype, ggnn_location location, int gpu_id,
+                                    uint32_t k_query, float tau_query, uint32_t max_iterations,
+                                    ggnn_measure measure, int32_t* ids_out, float* dists_out,
+                                    ggnn_location out_location,
+                                    const int32_t* query_label_masks, uint32_t n_masks,
+                                    ggnn_location masks_location, int masks_gpu_id,
+                                    const int32_t* filter_ids, ggnn_location ids_location,
+                                    int ids_gpu_id);
+ggnn_status ggnn_bf_query_labeled_mask(ggnn_t* h, const void* query, uint64_t Nq, uint32_t D,
+                                       ggnn_dtype dtype, ggnn_location location, int gpu_id,
+                                       uint32_t k_gt, ggnn_measure measure, int32_t* ids_out,
+                                       float* dists_out, ggnn_location out_location,
+                                       const int32_t* query_label_masks, uint32_t n_masks,
+                                       ggnn_location masks_location, int masks_gpu_id,
+                                       const int32_t* filter_ids, ggnn_location ids_location,
+                                       int ids_gpu_id);
+ggnn_status ggnn_query_async_labeled_mask(ggnn_t* h, const void* query, uint64_t Nq, uint32_t D,
+                                          ggnn_dtype dtype, int gpu_id, uint32_t k_query,
+                                          float tau_query, uint32_t max_iterations,
+                                          ggnn_measure measure, int32_t* ids_out,
+                                          float* dists_out, uint32_t slot,
+                                          const int32_t* query_label_masks, uint32_t n_masks,
+                                          const int32_t* filter_ids);
+
 /* layout of one graph shard, include/ggnn/base/graph_config.h:31-112 */
 typedef struct {
   uint32_t N, D, KBuild;
@@ -741,6 +795,35 @@ ggnn_status ggnn_op_bf_query_labeled_range(const void* base, ggnn_dtype dtype, u
                                            const uint32_t* filter_table, uint32_t num_filters,
                                            uint64_t n_bits, const int32_t* filter_ids,
                                            uint32_t filter_bit_offset, void* stream);
+/* ggnn_op_query_labeled_range / ggnn_op_bf_query_labeled_range with label MASKS in place of label
+ * ranges: query_label_masks is int32 [Nq x n_masks x 3], (mask, value, any) triples, 1 <= n_masks <=
+ * GGNN_MAX_LABEL_MASKS; local id i may be given to query n iff L = labels[i + filter_bit_offset] has
+ * (L & mask) == value and (any == 0 or (L & any) != 0) for one of its triples AND filter_ids[n] admits
+ * it, as above.  value is never pre-masked and there is no wildcard value (see
+ * ggnn_query_labeled_mask).  No int8 rows (GGNN_UNSUPPORTED); ggnn_op_bf_query_labeled_mask always
+ * runs the scan kernels. */
+ggnn_status ggnn_op_query_labeled_mask(const void* base, ggnn_dtype dtype, uint32_t N_base,
+                                       uint32_t D, const uint8_t* codes, const float* params,
+                                       const void* query, uint32_t Nq, const int32_t* graph0,
+                                       uint32_t KBuild, const int32_t* start, uint32_t num_start,
+                                       const float* nn1_stats, uint32_t k_query, float tau_query,
+                                       uint32_t max_iterations, ggnn_measure measure,
+                                       uint32_t shards_per_gpu, uint32_t on_gpu_shard,
+                                       int32_t* ids, float* dists, uint32_t* n_dist,
+                                       uint32_t* n_pop, uint32_t* n_rows, const int32_t* labels,
+                                       uint64_t n_labels, const int32_t* query_label_masks,
+                                       uint32_t n_masks, const uint32_t* filter_table,
+                                       uint32_t num_filters, uint64_t n_bits,
+                                       const int32_t* filter_ids, uint32_t filter_bit_offset,
+                                       void* stream);
+ggnn_status ggnn_op_bf_query_labeled_mask(const void* base, ggnn_dtype dtype, uint32_t N_base,
+                                          uint32_t D, const void* query, uint32_t Nq,
+                                          uint32_t k_query, ggnn_measure measure, int32_t* ids,
+                                          float* dists, const int32_t* labels, uint64_t n_labels,
+                                          const int32_t* query_label_masks, uint32_t n_masks,
+                                          const uint32_t* filter_table, uint32_t num_filters,
+                                          uint64_t n_bits, const int32_t* filter_ids,
+                                          uint32_t filter_bit_offset, void* stream);
 /* ggnn_op_bf_query_filtered, _filtered_by and _labeled, reporting how they ran (modelled on
  * ggnn_op_bf_query_certified): *n_rescanned (DEVICE memory, may be NULL) receives the number of
  * queries the matrix-core pre-selection could not certify and the filtered scan answered instead;

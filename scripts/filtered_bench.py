@@ -52,7 +52,13 @@ Label ranges (`query_labeled_range`) against label sets (`query_labeled_in`) on 
 graph and masks: a label column whose values 0..7 cover 50 % of the rows, 8..15 10 % and 16..17
 1 %, every query under the same mask, written once as a set of the values and once as one interval
 around them; results asserted equal, then kernel ms and queries/s (host clock around calls that end
-synchronised) of both calls, alternating, every repeat listed."""
+synchronised) of both calls, alternating, every repeat listed.
+
+    python scripts/filtered_bench.py --masks
+
+Label masks (`query_labeled_mask`) against label ranges (`query_labeled_range`) in the same way, on
+the column of --ranges: the three intervals are aligned blocks of values, so each is also one clause
+(mask, value, 0) on the bits above the block -- the same rows, 50 %, 10 % and 1 % of them."""
 import argparse
 import json
 import os
@@ -82,6 +88,7 @@ def main():
     ap.add_argument("--bf", action="store_true")
     ap.add_argument("--label-sets", action="store_true")
     ap.add_argument("--ranges", action="store_true")
+    ap.add_argument("--masks", action="store_true")
     a = ap.parse_args()
     rs = np.random.default_rng(1)
     centres = rs.normal(size=(256, a.d)).astype(np.float32) * 2
@@ -105,6 +112,9 @@ def main():
         return
     if a.ranges:
         label_ranges(a, g, q)
+        return
+    if a.masks:
+        label_masks(a, g, q)
         return
 
     def timed(fn):
@@ -383,6 +393,39 @@ def label_ranges(a, g, q):
                 ms[k].append(round(g.last_timing_ms()["query_ms"], 4))
         print(json.dumps({"ranges": name, "labels": values, "interval": [lo, hi],
                           "allowed": int(((column >= lo) & (column <= hi)).sum()),
+                          "kernel_ms": ms, "queries_per_s": qps}), flush=True)
+    g.set_labels(None)
+
+
+def label_masks(a, g, q):
+    import time
+    rs = np.random.default_rng(19)
+    # the column of label_ranges: values 0..7 6.25 % of the rows each, 8..15 1.25 %, 16..17 0.5 %
+    p = np.array([0.0625] * 8 + [0.0125] * 8 + [0.005] * 2 + [0.39])
+    column = rs.choice(len(p), a.n, p=p / p.sum()).astype(np.int32)
+    g.set_labels(torch.from_numpy(column).cuda())
+    for name, lo, hi in (("50 %", 0, 7), ("10 %", 8, 15), ("1 %", 16, 17)):
+        clause = (~(hi - lo), lo, 0)                          # the bits above an aligned block
+        assert lo & (hi - lo) == 0 and (hi - lo) & (hi - lo + 1) == 0
+        ranges = torch.tensor([[[lo, hi]]] * a.queries, dtype=torch.int32).cuda()
+        masks = torch.tensor([[clause]] * a.queries, dtype=torch.int32).cuda()
+        calls = {"query_labeled_range": lambda: g.query_labeled_range(q, a.k, a.tau, a.iters,
+                                                                      label_ranges=ranges),
+                 "query_labeled_mask": lambda: g.query_labeled_mask(q, a.k, a.tau, a.iters,
+                                                                    label_masks=masks)}
+        x, y = (fn() for fn in calls.values())
+        assert torch.equal(x[0], y[0]) and torch.equal(x[1], y[1])
+        ms, qps = {k: [] for k in calls}, {k: [] for k in calls}
+        for _ in range(a.reps):                               # alternating
+            for k, fn in calls.items():
+                torch.cuda.synchronize()
+                t = time.perf_counter()
+                fn()
+                torch.cuda.synchronize()
+                qps[k].append(round(a.queries / (time.perf_counter() - t)))
+                ms[k].append(round(g.last_timing_ms()["query_ms"], 4))
+        print(json.dumps({"masks": name, "interval": [lo, hi], "clause": list(clause),
+                          "allowed": int(((column & clause[0]) == clause[1]).sum()),
                           "kernel_ms": ms, "queries_per_s": qps}), flush=True)
     g.set_labels(None)
 
