@@ -123,6 +123,10 @@ SIGNATURES = {
     "ggnn_op_bf_query_label_index": (_int, [_vp, _int, _u32, _u32, _vp, _u32, _u32, _int, _vp,
                                             _u32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ggnn_op_label_index_classify": (_int, [_vp, _u32, _vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp]),
+    "ggnn_op_label_spans_resolve": (_int, [_vp, _u32, _vp, _int, _vp, _u32, _u32, _vp, _vp, _vp]),
+    "ggnn_op_bf_query_label_spans": (_int, [_vp, _int, _u32, _u32, _vp, _u32, _u32, _int, _vp, _vp,
+                                            _u32, _vp, _u32, _u64, _vp, _vp, _vp, _vp]),
+    "ggnn_op_label_spans_classify": (_int, [_vp, _u32, _u32, _vp, _vp, _vp, _vp]),
     "ggnn_query_labeled_in": (_int, [_vp, _vp, _u64, _u32, _int, _int, _int, _u32, _f32, _u32,
                                      _int, _vp, _vp, _int, _vp, _u32, _int, _int, _vp, _int,
                                      _int]),

@@ -314,6 +314,44 @@ void launch_label_index_classify(const int32_t* keys, uint32_t n_keys, const uin
                                  uint32_t* routed_list, uint32_t* rest_list, uint32_t* counts,
                                  hipStream_t stream);
 
+// Label spans (label_spans.hip): a label set or up to four label ranges of a query as at most eight
+// spans [begin, end) of positions into rows[] of a label index, in normal form -- sorted by begin,
+// pairwise disjoint, not touching, non-empty, unused slots (0, 0) at the tail -- so that no row is
+// reachable twice.  spans [Nq x 8 x 2], totals [Nq] (the sum of a query's span lengths).
+constexpr uint32_t kMaxLabelSpans = 8;
+enum LabelSpanMode : int { kLabelSpanSets = 0, kLabelSpanRanges = 1 };
+// sel: kLabelSpanSets [Nq x n_sel] labels (n_sel 1 .. 8; -1: the whole index; entries may repeat, an
+// entry that is no key gives nothing); kLabelSpanRanges [Nq x n_sel x 2] closed signed intervals
+// (n_sel 1 .. 4; lo > hi and intervals without a key give nothing; no wildcard)
+void launch_label_spans_resolve(const int32_t* keys, uint32_t n_keys, const uint32_t* offsets,
+                                int mode, const int32_t* sel, uint32_t n_sel, uint32_t Nq,
+                                uint32_t* spans, uint32_t* totals, hipStream_t stream);
+// The exact K nearest of every query among the rows at its spans' positions and, with filter ids, whose
+// bit of the query's row of the filter table is set (FilterTable's rules, bit offset 0).  Ranked by
+// (distance, id): bit for bit what the scan of the whole base gives under the same label set or ranges.
+struct LabelSpansLaunch {
+  const void* base;
+  const void* query;
+  ggnn_dtype dtype;
+  uint32_t N_base, D, Nq, k_query;
+  ggnn_measure measure;
+  int32_t* ids;  // [Nq x k_query]
+  float* dists;
+  const int32_t* rows;    // [N_base]
+  const uint32_t* spans;  // [Nq x 8 x 2]
+  // the cutoff the caller classified with (0: unknown): sizes the slices only; longer queries are
+  // still answered in full
+  uint32_t span_limit{0};
+  const uint32_t* filter_table{nullptr};  // [num_filters x words] or null
+  uint32_t num_filters{0}, words{0};
+  const int32_t* filter_ids{nullptr};  // [Nq] or null: spans only
+};
+void launch_label_spans_scan(const LabelSpansLaunch& a, hipStream_t stream);
+// launch_label_index_classify by totals: routed iff totals[n] <= cutoff
+void launch_label_spans_classify(const uint32_t* totals, uint32_t Nq, uint32_t cutoff,
+                                 uint32_t* routed_list, uint32_t* rest_list, uint32_t* counts,
+                                 hipStream_t stream);
+
 struct TopLaunch {
   const void* base;
   ggnn_dtype dtype;

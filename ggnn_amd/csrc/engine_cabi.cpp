@@ -1208,6 +1208,51 @@ ggnn_status ggnn_op_label_index_classify(const int32_t* keys, uint32_t n_keys,
   });
 }
 
+ggnn_status ggnn_op_label_spans_resolve(const int32_t* keys, uint32_t n_keys,
+                                        const uint32_t* offsets, int mode, const int32_t* sel,
+                                        uint32_t n_sel, uint32_t Nq, uint32_t* spans,
+                                        uint32_t* totals, void* stream)
+{
+  return guarded(nullptr, [&] {
+    launch_label_spans_resolve(keys, n_keys, offsets, mode, sel, n_sel, Nq, spans, totals,
+                               static_cast<hipStream_t>(stream));
+  });
+}
+
+ggnn_status ggnn_op_bf_query_label_spans(const void* base, ggnn_dtype dtype, uint32_t N_base,
+                                         uint32_t D, const void* query, uint32_t Nq,
+                                         uint32_t k_query, ggnn_measure measure,
+                                         const int32_t* rows, const uint32_t* spans,
+                                         uint32_t span_limit, const uint32_t* filter_table,
+                                         uint32_t num_filters, uint64_t n_bits,
+                                         const int32_t* filter_ids, int32_t* ids, float* dists,
+                                         void* stream)
+{
+  return guarded(nullptr, [&] {
+    GGNN_REQUIRE((filter_table != nullptr) == (num_filters > 0), GGNN_INVALID_ARGUMENT,
+                 "filter_table and num_filters go together");
+    GGNN_REQUIRE(!filter_table || (n_bits >= N_base && n_bits <= 0xffffffffull),
+                 GGNN_INVALID_ARGUMENT, "a filter needs N_base bits");
+    LabelSpansLaunch l{base, query, dtype, N_base, D, Nq, k_query, measure, ids, dists, rows, spans};
+    l.span_limit = span_limit;
+    l.filter_table = filter_table;
+    l.num_filters = num_filters;
+    l.words = filter_table ? static_cast<uint32_t>((n_bits + 31) / 32) : 0u;
+    l.filter_ids = filter_ids;
+    launch_label_spans_scan(l, static_cast<hipStream_t>(stream));
+  });
+}
+
+ggnn_status ggnn_op_label_spans_classify(const uint32_t* totals, uint32_t Nq, uint32_t cutoff,
+                                         uint32_t* routed_list, uint32_t* rest_list,
+                                         uint32_t* counts, void* stream)
+{
+  return guarded(nullptr, [&] {
+    launch_label_spans_classify(totals, Nq, cutoff, routed_list, rest_list, counts,
+                                static_cast<hipStream_t>(stream));
+  });
+}
+
 ggnn_status ggnn_op_bf_query_labeled_certified(const void* base, ggnn_dtype dtype,
                                                uint32_t N_base, uint32_t D, const void* query,
                                                uint32_t Nq, uint32_t k_query, ggnn_measure measure,

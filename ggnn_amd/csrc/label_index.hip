@@ -24,7 +24,7 @@
 #include <vector>
 
 #include "hooks.hpp"
-#include "traversal.hpp"
+#include "label_index.hpp"
 
 namespace ggnn_amd {
 
@@ -70,20 +70,7 @@ struct LabelIndexArgs {
   const int32_t* query_labels;
 };
 
-// position of label L in keys, or n_keys.  Every lane computes the same thing when L is wave-uniform;
-// the classify kernel calls it per lane.
-GGNN_DEV uint32_t label_index_find(const int32_t* keys, const uint32_t n_keys, const int32_t L)
-{
-  uint32_t lo = 0, hi = n_keys;
-  while (lo < hi) {
-    const uint32_t mid = (lo + hi) >> 1;
-    if (keys[mid] < L)
-      lo = mid + 1;
-    else
-      hi = mid;
-  }
-  return (lo < n_keys && keys[lo] == L) ? lo : n_keys;
-}
+// (label_index_find and label_index_batch: label_index.hpp, shared with label_spans.hip)
 
 // the positions [begin, end) of one (query, slice) wave, scalar; direct: position p is row p (label -1)
 struct LabelIndexSpan {
@@ -134,41 +121,6 @@ GGNN_DEV int label_index_ids(const LabelIndexArgs& a, const LabelIndexSpan& sp, 
     return -1;
   const int id = sp.direct ? static_cast<int>(p) : a.rows[p];
   return static_cast<uint32_t>(id) < a.N_base ? id : -1;
-}
-
-// the distances of one batch into s_d: rows idv of lanes [0, ROWS * STEPS) (bf_query.hip's sequence)
-template <typename BaseT, int LPR, int NCH, int MODE, class DE>
-GGNN_DEV void label_index_batch(const DE& de, const int idv, float* s_d)
-{
-  constexpr int ROWS = kWave / LPR;
-  constexpr int STEPS = StepsOf<LPR, NCH>::value;
-  using Chunk = typename DE::Chunk;
-  const int grp = threadIdx.x / LPR;
-  Chunk v[STEPS][NCH];
-#pragma unroll
-  for (int s = 0; s < STEPS; ++s) {
-    const int id = __shfl(idv, s * ROWS + grp);
-    const bool valid = id >= 0;
-    const BaseT* rp = de.row_ptr(valid ? id : 0);
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-      v[s][c] = ChunkOf<BaseT>::zero();
-      if (valid && de.chunk_valid(c))
-        v[s][c] = de.load_chunk(rp, c);
-    }
-  }
-  __syncthreads();
-#pragma unroll
-  for (int s = 0; s < STEPS; ++s) {
-    float x, y;
-    de.template partial<MODE>(v[s], x, y);
-    x = group_sum<LPR>(x);
-    if (MODE == kCos)
-      y = group_sum<LPR>(y);
-    if (de.g == 0)
-      s_d[s * ROWS + grp] = (MODE == kCos) ? de.finish_cos(x, y) : x;
-  }
-  __syncthreads();
 }
 
 template <typename BaseT, int LPR, int NCH, int R, int MODE>
@@ -486,9 +438,16 @@ void launch_label_index_classify(const int32_t* keys, uint32_t n_keys, const uin
   hipLaunchKernelGGL(label_index_classify_kernel, grid_for(words), dim3(kWave), 0, stream, keys,
                      n_keys, offsets, query_labels, Nq, cutoff,
                      static_cast<unsigned long long*>(flags.p));
-  hipLaunchKernelGGL(label_index_compact_kernel, dim3(1), dim3(kCompactThreads), 0, stream,
-                     static_cast<const unsigned long long*>(flags.p), Nq, routed_list, rest_list,
-                     counts);
+  GGNN_HIP_CHECK(hipGetLastError());
+  launch_label_index_compact(static_cast<const unsigned long long*>(flags.p), Nq, routed_list,
+                             rest_list, counts, stream);
+}
+
+void launch_label_index_compact(const unsigned long long* flags, uint32_t Nq, uint32_t* routed_list,
+                                uint32_t* rest_list, uint32_t* counts, hipStream_t stream)
+{
+  hipLaunchKernelGGL(label_index_compact_kernel, dim3(1), dim3(kCompactThreads), 0, stream, flags,
+                     Nq, routed_list, rest_list, counts);
   GGNN_HIP_CHECK(hipGetLastError());
 }
 

@@ -564,6 +564,104 @@ def bf_query_labeled_range(base, query, k_query, labels, label_ranges, filter_ta
     return ids, dists
 
 
+MAX_LABEL_SPANS = 8
+
+
+def label_spans_resolve(keys, offsets, label_sets=None, label_ranges=None):
+    """The label sets ([Nq, 1..8] int32, as query_labeled_in takes them) or the label ranges ([Nq,
+    1..4, 2] int32, as query_labeled_range) of a batch as spans of positions into `rows` of a label
+    index: (spans [Nq, 8, 2] int32, totals [Nq] int32).  Exactly one of the two is given.  The spans
+    of a query are sorted, disjoint, never touching and non-empty, unused slots are (0, 0) at the
+    tail, and totals[n] is the number of rows query n will read."""
+    if (label_sets is None) == (label_ranges is None):
+        raise ValueError("give label_sets or label_ranges, one of the two")
+    _need(keys, torch.int32, "keys"), _need(offsets, torch.int32, "offsets")
+    if keys.dim() != 1 or keys.numel() < 1 or offsets.dim() != 1 or offsets.numel() != keys.numel() + 1:
+        raise ValueError("keys [L] and offsets [L + 1] must be 1-dimensional, L >= 1")
+    if label_sets is not None:
+        sel, mode = _need(label_sets, torch.int32, "label_sets"), 0
+        if sel.dim() != 2 or not 1 <= sel.shape[1] <= MAX_LABEL_SET:
+            raise ValueError(f"label_sets must be [Nq, 1..{MAX_LABEL_SET}]")
+    else:
+        sel, mode = _need(label_ranges, torch.int32, "label_ranges"), 1
+        if sel.dim() != 3 or sel.shape[2] != 2 or not 1 <= sel.shape[1] <= MAX_LABEL_RANGES:
+            raise ValueError(f"label_ranges must be [Nq, 1..{MAX_LABEL_RANGES}, 2]")
+    Nq = sel.shape[0]
+    spans = torch.empty((Nq, MAX_LABEL_SPANS, 2), dtype=torch.int32, device=keys.device)
+    totals = torch.empty(Nq, dtype=torch.int32, device=keys.device)
+    check(lib().ggnn_op_label_spans_resolve(_ptr(keys), keys.numel(), _ptr(offsets), mode, _ptr(sel),
+                                            sel.shape[1], Nq, _ptr(spans), _ptr(totals), _stream()))
+    return spans, totals
+
+
+def bf_query_label_spans(base, query, k_query, rows, spans, filter_table=None, filter_ids=None,
+                         measure=EUCLIDEAN, span_limit=0):
+    """The exact k_query nearest of every query among the rows at the positions of its spans
+    (label_spans_resolve) of `rows` (label_index_build), and -- with filter_ids -- whose bit of row
+    filter_ids[n] of filter_table is set (id -1 admits every row, any other id outside [0, F) none).
+    Ranked by (distance, id): every output bit equals bf_query_labeled_in / bf_query_labeled_range on
+    the same column.  Every element type, int8 included.  span_limit: the cutoff the batch was
+    classified with (0: unknown); it sizes the slices only."""
+    _need(base, name="base"), _need(query, base.dtype, "query")
+    Nq, N = query.shape[0], base.shape[0]
+    _need(rows, torch.int32, "rows"), _need(spans, torch.int32, "spans")
+    if rows.dim() != 1 or rows.numel() != N:
+        raise ValueError("rows must be 1-dimensional with one entry per base row")
+    if spans.dim() != 3 or tuple(spans.shape) != (Nq, MAX_LABEL_SPANS, 2):
+        raise ValueError(f"spans must be [Nq, {MAX_LABEL_SPANS}, 2]")
+    F = n_bits = 0
+    if filter_table is not None:
+        _need(filter_table, torch.int32, "filter_table")
+        if filter_table.dim() != 2 or filter_table.shape[0] == 0:
+            raise ValueError("filter_table must be [F, words] with F >= 1")
+        if filter_table.shape[1] * 32 < N:
+            raise ValueError("the rows of filter_table are shorter than N bits")
+        F, n_bits = filter_table.shape[0], filter_table.shape[1] * 32
+    if filter_ids is not None:
+        _need(filter_ids, torch.int32, "filter_ids")
+        if filter_ids.dim() != 1 or filter_ids.numel() != Nq:
+            raise ValueError("filter_ids must be 1-dimensional with one entry per query")
+    ids = torch.empty((Nq, k_query), dtype=torch.int32, device=base.device)
+    dists = torch.empty((Nq, k_query), dtype=torch.float32, device=base.device)
+    check(lib().ggnn_op_bf_query_label_spans(
+        _ptr(base), _dtype_code(base), N, base.shape[1], _ptr(query), Nq, k_query, measure,
+        _ptr(rows), _ptr(spans), int(span_limit), _ptr(filter_table), F, n_bits, _ptr(filter_ids),
+        _ptr(ids), _ptr(dists), _stream()))
+    return ids, dists
+
+
+def label_spans_classify(totals, cutoff):
+    """(routed, rest): the queries with totals[n] <= cutoff and the others, each in ascending order
+    (int32 CUDA tensors); totals as label_spans_resolve gives them"""
+    _need(totals, torch.int32, "totals")
+    if totals.dim() != 1:
+        raise ValueError("totals must be 1-dimensional")
+    Nq = totals.numel()
+    lists = torch.empty((2, max(Nq, 1)), dtype=torch.int32, device=totals.device)
+    counts = torch.zeros(2, dtype=torch.int32, device=totals.device)
+    check(lib().ggnn_op_label_spans_classify(_ptr(totals), Nq, int(cutoff), _ptr(lists[0]),
+                                             _ptr(lists[1]), _ptr(counts), _stream()))
+    n_routed, n_rest = (int(v) for v in counts.tolist())
+    return lists[0, :n_routed], lists[1, :n_rest]
+
+
+def bf_query_label_index_in(base, query, k_query, keys, offsets, rows, label_sets,
+                            filter_table=None, filter_ids=None, measure=EUCLIDEAN, span_limit=0):
+    """`bf_query_labeled_in` through a label index: label_spans_resolve, then bf_query_label_spans"""
+    spans, _ = label_spans_resolve(keys, offsets, label_sets=label_sets)
+    return bf_query_label_spans(base, query, k_query, rows, spans, filter_table, filter_ids, measure,
+                                span_limit)
+
+
+def bf_query_label_index_range(base, query, k_query, keys, offsets, rows, label_ranges,
+                               filter_table=None, filter_ids=None, measure=EUCLIDEAN, span_limit=0):
+    """`bf_query_labeled_range` through a label index: label_spans_resolve, then
+    bf_query_label_spans"""
+    spans, _ = label_spans_resolve(keys, offsets, label_ranges=label_ranges)
+    return bf_query_label_spans(base, query, k_query, rows, spans, filter_table, filter_ids, measure,
+                                span_limit)
+
+
 MAX_LABEL_MASKS = 2  # GGNN_MAX_LABEL_MASKS
 
 

@@ -275,8 +275,14 @@ ggnn_status ggnn_query_async_labeled(ggnn_t* h, const void* query, uint64_t Nq, 
  * ggnn_op_bf_query_label_index (section 2) answers every query exactly from the rows of its label
  * alone, at about one distance evaluation per row of the label however large the base is, and
  * ggnn_op_label_index_classify says which queries of a batch have a label of at most `cutoff` rows.
- * The handle's *_labeled calls do not use an index: they search as described above, and a caller that
- * wants small labels answered from their rows routes with these two operators. */
+ * Label sets and label ranges go through the same index: a closed label interval is one contiguous run
+ * of its rows, a set of eight labels at most eight (ggnn_op_label_spans_resolve,
+ * ggnn_op_bf_query_label_spans, ggnn_op_label_spans_classify, section 2) -- for int8 rows the only way
+ * to search by a label set or a label range.  Label masks have no index form: tag bits are not a sort
+ * key.  The handle's *_labeled calls do not use an index: they search as described above, and a caller
+ * that wants small labels or narrow ranges answered from their rows routes with these operators.
+ * (Routing inside the handle was tried and taken out again: with it in the tree an out-of-core build
+ * faulted on the GPU, and the cause has not been found.) */
 /* The index of a label column (pure host): keys[n_keys] the distinct labels in ascending signed
  * order, offsets[n_keys + 1] with offsets[0] = 0 and offsets[n_keys] = n, rows[n] the ids sorted by
  * (label, id).  The caller provides keys[n], offsets[n + 1], rows[n].  n must be in [1, 2^30]:
@@ -613,9 +619,10 @@ void ggnn_set_log_level(int level);
  *                             launched by the engine, which knows the copy's flag; the operator
  *                             seam always runs the float rows); 0 = always the float rows (same
  *                             results; A/B and test hook)
- *   LABEL_INDEX_SLICES  0     slices the index scan cuts a label's rows into (1..64): 0 = chosen from
- *                             the longest segment the call can touch and the number of queries (same
- *                             results for every count; test hook) */
+ *   LABEL_INDEX_SLICES  0     slices the index scans (one label, label spans) cut a query's rows into
+ *                             (1..64): 0 = chosen from the longest segment the call can touch -- for
+ *                             spans, span_limit -- and the number of queries (same results for every
+ *                             count; test hook) */
 ggnn_status ggnn_set_hook(const char* name, int64_t value);
 /* back to environment / default */
 ggnn_status ggnn_reset_hook(const char* name);
@@ -777,6 +784,59 @@ ggnn_status ggnn_op_label_index_classify(const int32_t* keys, uint32_t n_keys,
                                          const uint32_t* offsets, const int32_t* query_labels,
                                          uint32_t Nq, uint32_t cutoff, uint32_t* routed_list,
                                          uint32_t* rest_list, uint32_t* counts, void* stream);
+/* Label sets and label ranges through a label index: three operators (all device memory).
+ *
+ * rows[] of the index is sorted by (label, id), so the rows of one label -- and of one closed label
+ * interval -- are one contiguous run of positions.  ggnn_op_label_spans_resolve turns every query's
+ * label set or label ranges into at most eight such runs:
+ *   mode 0  sel is int32 [Nq x n_sel], 1 <= n_sel <= GGNN_MAX_LABEL_SET, the label sets of
+ *           ggnn_op_bf_query_labeled_in: an entry that is a key gives that key's rows, an entry that is
+ *           no key nothing, an entry -1 the whole index; entries may repeat
+ *   mode 1  sel is int32 [Nq x n_sel x 2], 1 <= n_sel <= GGNN_MAX_LABEL_RANGES, the closed signed
+ *           intervals (lo, hi) of ggnn_op_bf_query_labeled_range: the rows of every key in [lo, hi];
+ *           lo > hi and an interval without a key give nothing; there is no wildcard
+ * spans is uint32 [Nq x 8 x 2], (begin, end) positions into rows[], in normal form: sorted by begin,
+ * overlapping and touching spans merged (pairwise disjoint, never end == next begin), none empty,
+ * unused slots (0, 0) at the tail -- the same input always gives the same words, and no row is
+ * reachable twice whatever repeats or overlaps in sel.  totals[Nq] is the sum of a query's span
+ * lengths: the number of rows the query will read.
+ *
+ * ggnn_op_bf_query_label_spans is the exact K nearest of every query among the rows at the positions
+ * of its spans, and -- with filter_ids -- whose bit of the query's row of filter_table is set, under
+ * the rules of ggnn_op_bf_query_labeled_in with filter_bit_offset 0: id -1 admits every row, f in
+ * [0, num_filters) tests bit `row id` of row f, any other id gives an empty result without reading a
+ * base row; filter_ids == NULL: spans only (the table is then not read); filter_table may be NULL
+ * with num_filters == 0, and n_bits >= N_base when there is one (GGNN_INVALID_ARGUMENT otherwise).
+ * The K-best list is ordered by the pair (distance, id): positions ascend with the id inside one
+ * label only, and the K smallest pairs are what the scan of the whole base in ascending id with its
+ * stable insert keeps.  Every output bit therefore equals ggnn_op_bf_query_labeled_in /
+ * ggnn_op_bf_query_labeled_range on the same column, sets / ranges and table (ids, distance bits,
+ * unfilled slots (-1, +inf)).  Every element type -- for int8 rows, which those two refuse, this is
+ * the only way to search by a label set or a label range --, both measures, 1 <= k_query <= 6000
+ * (GGNN_INVALID_ARGUMENT), N_base <= 2^30 (GGNN_UNSUPPORTED); always scan kernels.  A denied row costs
+ * its id and its bitset word, not a base row.  span_limit: the cutoff the caller classified with, or
+ * 0 for "unknown": it only sizes the slices a query's positions are cut into when the batch is small
+ * (hook LABEL_INDEX_SLICES forces the count); a query with more rows is still answered in full.
+ * Label masks have no such form: tag bits are not a sort key.
+ *
+ * ggnn_op_label_spans_classify is ggnn_op_label_index_classify by totals: routed iff totals[n] <=
+ * cutoff (a wildcard set has total N_base, so it is routed only when cutoff >= N_base).  Nq == 0
+ * launches nothing in all three (classify then zeroes counts). */
+ggnn_status ggnn_op_label_spans_resolve(const int32_t* keys, uint32_t n_keys,
+                                        const uint32_t* offsets, int mode, const int32_t* sel,
+                                        uint32_t n_sel, uint32_t Nq, uint32_t* spans,
+                                        uint32_t* totals, void* stream);
+ggnn_status ggnn_op_bf_query_label_spans(const void* base, ggnn_dtype dtype, uint32_t N_base,
+                                         uint32_t D, const void* query, uint32_t Nq,
+                                         uint32_t k_query, ggnn_measure measure,
+                                         const int32_t* rows, const uint32_t* spans,
+                                         uint32_t span_limit, const uint32_t* filter_table,
+                                         uint32_t num_filters, uint64_t n_bits,
+                                         const int32_t* filter_ids, int32_t* ids, float* dists,
+                                         void* stream);
+ggnn_status ggnn_op_label_spans_classify(const uint32_t* totals, uint32_t Nq, uint32_t cutoff,
+                                         uint32_t* routed_list, uint32_t* rest_list,
+                                         uint32_t* counts, void* stream);
 /* ggnn_op_query_labeled / ggnn_op_bf_query_labeled with a label SET per query and an optional
  * filter table (all device memory): query_label_sets is int32 [Nq x set_width], 1 <= set_width <=
  * GGNN_MAX_LABEL_SET; local id i may be given to query n iff labels[i + filter_bit_offset] equals
