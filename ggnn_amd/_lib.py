@@ -231,6 +231,23 @@ SIGNATURES = {
     "ggnn_op_bf_query_labeled_certified": (_int, [_vp, _int, _u32, _u32, _vp, _u32, _u32, _int,
                                                   _vp, _vp, _vp, _u64, _vp, _u32, _vp,
                                                   C.POINTER(C.c_int), _vp]),
+    # range search: ..., radii, measure, capacity, lims, ids, dists, ...
+    "ggnn_bf_range_query": (_int, [_vp, _vp, _u64, _u32, _int, _int, _int, _vp, _int, _u64, _vp, _vp,
+                                   _vp, _int]),
+    "ggnn_bf_range_query_filtered": (_int, [_vp, _vp, _u64, _u32, _int, _int, _int, _vp, _int, _u64,
+                                            _vp, _vp, _vp, _int, _vp, _u64, _int, _int]),
+    "ggnn_bf_range_query_filtered_by": (_int, [_vp, _vp, _u64, _u32, _int, _int, _int, _vp, _int,
+                                               _u64, _vp, _vp, _vp, _int, _vp, _int, _int]),
+    "ggnn_bf_range_query_labeled": (_int, [_vp, _vp, _u64, _u32, _int, _int, _int, _vp, _int, _u64,
+                                           _vp, _vp, _vp, _int, _vp, _int, _int]),
+    "ggnn_op_bf_range_query": (_int, [_vp, _int, _u32, _u32, _vp, _u32, _vp, _int, _u64, _vp, _vp,
+                                      _vp, _vp]),
+    "ggnn_op_bf_range_query_filtered": (_int, [_vp, _int, _u32, _u32, _vp, _u32, _vp, _int, _u64,
+                                               _vp, _vp, _vp, _vp, _u32, _vp]),
+    "ggnn_op_bf_range_query_filtered_by": (_int, [_vp, _int, _u32, _u32, _vp, _u32, _vp, _int, _u64,
+                                                  _vp, _vp, _vp, _vp, _u32, _u64, _vp, _u32, _vp]),
+    "ggnn_op_bf_range_query_labeled": (_int, [_vp, _int, _u32, _u32, _vp, _u32, _vp, _int, _u64,
+                                              _vp, _vp, _vp, _vp, _u64, _vp, _u32, _vp]),
     "ggnn_last_exchange": (C.c_char_p, [_vp]),
     "ggnn_op_top": (_int, [_vp, _int, _u32, _int, _u32, _vp, _u32, _u32, _u32, _u32, _vp, _vp,
                            _vp]),

@@ -1077,6 +1077,130 @@ class GGNN:
         return self._blocking(lib().ggnn_bf_query, _as_tensor(query, what="query"),
                               (int(k_gt), int(measure)))
 
+    def _range(self, call, query, radius, measure, max_results, sort, tail=()):
+        """one exact range search through the C-ABI: (lims int64 [Nq + 1], ids int32, dists float32)"""
+        from .ops import range_radii, sort_segments
+        t = _as_tensor(query, what="query")
+        Nq = t.shape[0]
+        radii = range_radii(radius, Nq, "cpu")
+        loc, dev = _loc(t)
+        on_gpu = self._return_results_on_gpu
+        out_dev = self._result_device(t) if on_gpu else "cpu"
+        lims = torch.zeros(Nq + 1, dtype=torch.int64)
+
+        def run(capacity, ids, dists):
+            self._check(call(self._h, t.data_ptr(), Nq, t.shape[1], _dtype_code(t), loc, dev,
+                             radii.data_ptr(), int(measure), capacity, lims.data_ptr(),
+                             ids.data_ptr() if capacity else None,
+                             dists.data_ptr() if capacity else None,
+                             _lib.GPU if on_gpu else _lib.CPU, *tail))
+            return int(lims[-1])
+
+        def buffers(capacity):
+            ids = torch.empty(capacity, dtype=torch.int32, device=out_dev)
+            dists = torch.empty(capacity, dtype=torch.float32, device=out_dev)
+            if on_gpu:
+                torch.cuda.current_stream(out_dev).synchronize()  # (see _out)
+            return ids, dists
+
+        if max_results is None:
+            total = run(0, None, None)
+            ids, dists = buffers(total)
+            if total:
+                run(total, ids, dists)
+        else:
+            max_results = int(max_results)
+            ids, dists = buffers(max_results)
+            total = run(max_results, ids, dists)
+            if total > max_results:
+                raise RuntimeError(f"range query: {total} results do not fit max_results="
+                                   f"{max_results}; call again with max_results >= {total}")
+            ids, dists = ids[:total], dists[:total]
+        if sort:
+            ids, dists = sort_segments(lims, ids, dists)
+        return lims, ids, dists
+
+    def bf_range_query(self, query, radius, measure=DistanceMeasure.Euclidean, max_results=None,
+                       sort=True):
+        """Extension: exact range search -- EVERY base vector within `radius` of each query, where
+        `bf_query` returns the k best.  Returns (lims, ids, dists): lims is int64 [Nq + 1] on the
+        CPU, and the results of query n are ids[lims[n]:lims[n + 1]] / dists[...] (on the GPU with
+        `set_return_results_on_gpu`).
+
+        **Under the Euclidean measure distances are SQUARED L2 distances, and so is the radius**:
+        pass r * r to get everything within Euclidean distance r.  Under Cosine it is |1 - cos|.  A
+        vector belongs to the answer iff distance <= radius in float32, with exactly the distance
+        `bf_query` reports.  `radius`: a scalar for all queries, or one value per query; +inf
+        admits everything, a negative radius nothing, NaN is an error.
+
+        `max_results=None` counts first (one distance pass), allocates exactly and calls again (two
+        more passes: three in all).  An integer `max_results` makes one call (two passes) into
+        buffers of that many entries and raises RuntimeError, naming the needed total, if they are
+        too small.  `sort=True` orders each query's results by (distance, id), as `bf_query` would
+        list them; `sort=False` keeps the engine's order, ascending id."""
+        return self._range(lib().ggnn_bf_range_query, query, radius, measure, max_results, sort)
+
+    def bf_range_query_filtered(self, query, radius, measure=DistanceMeasure.Euclidean,
+                                max_results=None, sort=True, filter=None):
+        """Extension: `bf_range_query` among the base vectors `filter` allows (see
+        `query_filtered`).  `filter=None` is `bf_range_query`."""
+        return self.bf_range_query_filtered_by(query, radius, measure, max_results, sort,
+                                               filter=filter)
+
+    def bf_range_query_filtered_by(self, query, radius, measure=DistanceMeasure.Euclidean,
+                                   max_results=None, sort=True, filter_ids=None, filter=None):
+        """Extension: `bf_range_query` with a filter per query (`filter_ids`, `filter`: see
+        `query_filtered_by`)."""
+        if filter is not None and filter_ids is not None:
+            raise ValueError("give either filter or filter_ids, not both")
+        if filter_ids is not None:
+            fi = _filter_ids(filter_ids, _as_tensor(query, what="query").shape[0])
+            return self._range(lib().ggnn_bf_range_query_filtered_by, query, radius, measure,
+                               max_results, sort, self._where(fi))
+        if filter is not None:
+            f = _filter_words(filter, self._N)
+            ptr, floc, fdev = self._where(f)
+            return self._range(lib().ggnn_bf_range_query_filtered, query, radius, measure,
+                               max_results, sort, (ptr, self._N, floc, fdev))
+        return self.bf_range_query(query, radius, measure, max_results, sort)
+
+    def bf_range_query_labeled(self, query, radius, measure=DistanceMeasure.Euclidean,
+                               max_results=None, sort=True, labels=None):
+        """Extension: `bf_range_query` among the base vectors that carry the query's label
+        (`labels`: see `query_labeled`; -1 admits every vector).  `labels=None` is
+        `bf_range_query`."""
+        if labels is None:
+            return self.bf_range_query(query, radius, measure, max_results, sort)
+        ql = _labels(labels, _as_tensor(query, what="query").shape[0], per="query")
+        return self._range(lib().ggnn_bf_range_query_labeled, query, radius, measure, max_results,
+                           sort, self._where(ql))
+
+    def range_query(self, query, radius, k_query, tau_query, max_iterations=400,
+                    measure=DistanceMeasure.Euclidean):
+        """Extension: the APPROXIMATE counterpart of `bf_range_query`: the graph search `query`,
+        cut at the radius.  Returns the same (lims, ids, dists) triple, each query's results in
+        ascending distance: the prefix of its `query` row with distance <= radius (squared units
+        under Euclidean), unfilled slots (id -1) dropped.
+
+        It can return AT MOST `k_query` vectors per query.  A query whose count lims[n + 1] -
+        lims[n] equals `k_query` was cut by the list length, not by the radius: raise `k_query`
+        (or use `bf_range_query`) for those."""
+        from .ops import range_radii
+        ids, dists = self.query(query, k_query, tau_query, max_iterations, measure)
+        Nq = ids.shape[0]
+        k = int(k_query)
+        if ids.shape[1] != k:
+            raise RuntimeError("range_query needs merged results: one shard per GPU, or results "
+                               "returned on the host")
+        r = range_radii(radius, Nq, dists.device)
+        if bool(torch.isnan(r).any()):
+            raise ValueError("a radius is NaN")
+        ok = (dists <= r[:, None]) & (ids >= 0)
+        keep = torch.cumprod(ok.to(torch.int32), dim=1).bool()   # the prefix only
+        lims = torch.zeros(Nq + 1, dtype=torch.int64)
+        lims[1:] = torch.cumsum(keep.sum(dim=1), dim=0).cpu()
+        return lims, ids[keep], dists[keep]
+
     def get_graph(self, on_gpu_shard_id=0):
         """Access the GGNN graph."""
         view = _lib.GraphView()

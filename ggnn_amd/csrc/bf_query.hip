@@ -15,113 +15,11 @@
 // re-scanned query is chosen by its real index n = qlist[...], not by its position in the list.
 #include <cstdlib>
 
+#include "bf_common.hpp"  // BfArgs and the filter verdicts, shared with bf_range.hip
 #include "hooks.hpp"
 #include "traversal.hpp"
 
 namespace ggnn_amd {
-
-struct BfArgs {
-  const void* base;
-  const void* query;
-  int32_t* ids;    // [slices x Nq x K] partial results (or final when slices == 1)
-  float* dists;
-  uint32_t D, Nq, N_base, K, slices, rows_per_slice;
-  // optional subset: only the queries qlist[0, *qcount) are scanned (device memory; the grid is
-  // sized for all Nq queries and the surplus blocks leave at once)
-  const uint32_t* qlist;
-  const uint32_t* qcount;
-  // filtered scan (FILT kernels): allowed-id bitset, row i is allowed iff bit i + filter_bit_offset
-  const uint32_t* filter_bits;
-  uint32_t filter_bit_offset;
-};
-
-// Arguments of the FILT kernels: per-query filters make filter_bits a table and add the id array
-// (FilterTable, common.hpp).  A struct of its own: the unfiltered kernels keep their argument block.
-struct BfFilteredArgs : BfArgs {
-  FilterTable filter_table;
-};
-template <bool FILT>
-using BfArgsOf = std::conditional_t<FILT, BfFilteredArgs, BfArgs>;
-
-// FILT: the bitset of this (query, slice) wave -- the call's, or the table row that the filter id
-// of query n names (scalar, once per wave)
-template <bool FILT>
-GGNN_DEV const uint32_t* bf_wave_filter(const BfArgsOf<FILT>& a, uint32_t n)
-{
-  if constexpr (FILT)
-    return wave_filter_bits(a.filter_bits, a.filter_table, n);
-  else
-    return nullptr;
-}
-
-// FILT: this lane's word of the bitset for the 64 (or fewer) rows of a batch starting at i0 -- one
-// coalesced load per batch, issued in front of the rows -- and the verdict for row i0 + lane
-template <bool FILT>
-GGNN_DEV uint32_t bf_filter_word(const BfArgs& a, const uint32_t* bits, uint32_t i0, uint32_t end)
-{
-  if constexpr (FILT) {
-    const uint32_t row = i0 + threadIdx.x;
-    return row < end ? bits[(row + a.filter_bit_offset) >> 5] : 0u;
-  }
-  return 0u;
-}
-template <bool FILT>
-GGNN_DEV bool bf_row_allowed(const BfArgs& a, uint32_t word, uint32_t i0)
-{
-  if constexpr (FILT)
-    return (word >> ((i0 + threadIdx.x + a.filter_bit_offset) & 31u)) & 1u;
-  return true;
-}
-
-// LAB (label filters, with FILT): the rows whose int32 label equals the label of query n; label -1
-// admits every row.  Kernels of their own (the trailing template argument), so that the bitset
-// kernels keep their code: a read parametrised over both forms costs them registers (DESIGN.md
-// 4.9).  One coalesced dword per row of the batch, issued in front of the rows like the bit words;
-// the shard offset is folded into the wave-uniform pointer and the label addressed as a 32-bit
-// byte offset from it (at most 2^30 rows per scan: kMaxLabeledShardRows, traversal.hpp).
-//   allowed = (label & vmask) == want      label L: vmask ~0u, want L;  label -1: vmask 0, want 0
-struct BfLabelFilter {
-  const uint32_t* labels;  // the column at the first global id of this base
-  uint32_t vmask, want;
-};
-template <bool LAB, class Args>
-GGNN_DEV BfLabelFilter bf_wave_labels(const Args& a, uint32_t n)
-{
-  if constexpr (LAB) {
-    const int32_t L = __builtin_amdgcn_readfirstlane(a.filter_table.query_labels[n]);
-    const uint32_t vmask = (L == -1) ? 0u : ~0u;
-    return BfLabelFilter{a.filter_bits + a.filter_bit_offset, vmask, static_cast<uint32_t>(L) & vmask};
-  }
-  else
-    return BfLabelFilter{nullptr, 0u, 0u};
-}
-GGNN_DEV uint32_t bf_label_word(const BfLabelFilter& f, uint32_t i0, uint32_t end)
-{
-  const uint32_t row = i0 + threadIdx.x;
-  return row < end ? filter_word_at(f.labels, row << 2) : 0u;
-}
-GGNN_DEV bool bf_label_allowed(const BfLabelFilter& f, uint32_t word)
-{
-  return (word & f.vmask) == f.want;
-}
-// the filter word and the verdict of a kernel: the bitset's, or the label's
-template <bool FILT, bool LAB>
-GGNN_DEV uint32_t bf_word(const BfArgs& a, const uint32_t* bits, const BfLabelFilter& f,
-                          uint32_t i0, uint32_t end)
-{
-  if constexpr (LAB)
-    return bf_label_word(f, i0, end);
-  else
-    return bf_filter_word<FILT>(a, bits, i0, end);
-}
-template <bool FILT, bool LAB>
-GGNN_DEV bool bf_allowed(const BfArgs& a, const BfLabelFilter& f, uint32_t word, uint32_t i0)
-{
-  if constexpr (LAB)
-    return bf_label_allowed(f, word);
-  else
-    return bf_row_allowed<FILT>(a, word, i0);
-}
 
 template <typename BaseT, int LPR, int NCH, int R, int MODE, bool FILT = false, bool LAB = false>
 __global__ void __launch_bounds__(kWave) bf_query_kernel(const BfArgsOf<FILT> a)
@@ -481,7 +379,7 @@ static void launch_bf_scan(const BfLaunch& a, uint32_t slices, uint32_t rows_per
                                 a.dists, qlist, qcount, stream);
 }
 
-// (shared with bf_query_labelset.hip, bf_query_labelrange.hip and bf_query_labelmask.hip)
+// (shared with bf_query_labelset.hip, bf_query_labelrange.hip, bf_query_labelmask.hip, bf_range.hip)
 void bf_slice_rows(uint32_t N_base, uint32_t& slices, uint32_t& rows_per_slice)
 {
   const uint32_t row_quant = 64;  // multiple of ROWS*STEPS for every configuration

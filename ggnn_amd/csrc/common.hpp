@@ -282,6 +282,31 @@ struct BfLaunch {
 };
 void launch_bf_query(const BfLaunch& a, hipStream_t stream);
 
+// Exact range search (bf_range.hip): every base row i that the filter admits and whose distance to
+// query n -- the float32 value launch_bf_query's scan kernel reports for the pair: squared L2 or
+// |1 - cos| -- is <= radii[n].  CSR result: lims[Nq + 1] (lims[0] = 0, lims[Nq] the total), and the
+// rows of query n at ids / dists [lims[n], lims[n + 1]) in ascending id.  lims is always written; ids /
+// dists only if the total fits `capacity` entries (they may be null with capacity 0: count only).
+// A NaN radius and a negative one admit nothing.  All device memory, nothing waits for the host.
+// Filters: none, a bitset (filter_bits), a filter table (filter_table.ids) or one label per query
+// (filter_table.query_labels) -- BfLaunch's rules.
+struct BfRangeLaunch {
+  const void* base;
+  const void* query;
+  ggnn_dtype dtype;
+  uint32_t N_base, D, Nq;
+  ggnn_measure measure;
+  const float* radii;  // [Nq]
+  uint64_t capacity;
+  uint64_t* lims;  // [Nq + 1]
+  int32_t* ids;    // [capacity] or null
+  float* dists;    // [capacity] or null
+  const uint32_t* filter_bits{nullptr};
+  uint32_t filter_bit_offset{0};
+  FilterTable filter_table{};
+};
+void launch_bf_range_query(const BfRangeLaunch& a, hipStream_t stream);
+
 // Label index (label_index.hip): the label column in CSR form over the global base ids -- keys[n_keys]
 // the distinct labels ascending, offsets[n_keys + 1] uint32 positions (offsets[0] = 0, offsets[n_keys]
 // = N), rows[N] the base ids sorted by (label, id).  label_index_build is a host function (n in

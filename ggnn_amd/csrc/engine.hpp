@@ -762,6 +762,13 @@ struct ggnn_handle {
   void synchronize();
 
   void bf_query(const QueryRequest& r, const QueryFilter& filter);
+  // r.k is not used; radii[Nq] and lims_out[Nq + 1] are host memory, r.ids_out / r.dists_out hold
+  // `capacity` entries at r.out_loc
+  void bf_range_query(const QueryRequest& r, const float* radii, uint64_t capacity,
+                      uint64_t* lims_out, const QueryFilter& filter);
+  // the staging of the exhaustive calls (engine_query.cpp)
+  DeviceCtx& bf_context(uint64_t Nq, uint32_t D, ggnn_dtype dtype, const void* q);
+  const void* bf_whole_base(DeviceCtx& ctx, DeviceBuffer& whole_base);
 
   std::filesystem::path part_file(uint32_t shard) const;
 

@@ -657,6 +657,67 @@ ggnn_status ggnn_bf_query_labeled(ggnn_t* h, const void* query, uint64_t Nq, uin
   });
 }
 
+// Exact range search (bf_range.hip): the bf_query calls with a radius per query and a CSR result.
+#define GGNN_RANGE_REQUEST \
+  QueryRequest{query, Nq, D, dtype, location, gpu_id, 0u, measure, ids_out, dists_out, out_location}
+ggnn_status ggnn_bf_range_query(ggnn_t* h, const void* query, uint64_t Nq, uint32_t D,
+                                ggnn_dtype dtype, ggnn_location location, int gpu_id,
+                                const float* radii, ggnn_measure measure, uint64_t capacity,
+                                uint64_t* lims_out, int32_t* ids_out, float* dists_out,
+                                ggnn_location out_location)
+{
+  GGNN_NEED_HANDLE(h);
+  return guarded(h, [&] {
+    h->bf_range_query(GGNN_RANGE_REQUEST, radii, capacity, lims_out, QueryFilter{});
+  });
+}
+
+ggnn_status ggnn_bf_range_query_filtered(ggnn_t* h, const void* query, uint64_t Nq, uint32_t D,
+                                         ggnn_dtype dtype, ggnn_location location, int gpu_id,
+                                         const float* radii, ggnn_measure measure,
+                                         uint64_t capacity, uint64_t* lims_out, int32_t* ids_out,
+                                         float* dists_out, ggnn_location out_location,
+                                         const uint32_t* allowed_bits, uint64_t n_bits,
+                                         ggnn_location filter_location, int filter_gpu_id)
+{
+  GGNN_NEED_HANDLE(h);
+  return guarded(h, [&] {
+    h->bf_range_query(GGNN_RANGE_REQUEST, radii, capacity, lims_out,
+                      QueryFilter::bitset(*h, allowed_bits, n_bits, filter_location, filter_gpu_id));
+  });
+}
+
+ggnn_status ggnn_bf_range_query_filtered_by(ggnn_t* h, const void* query, uint64_t Nq, uint32_t D,
+                                            ggnn_dtype dtype, ggnn_location location, int gpu_id,
+                                            const float* radii, ggnn_measure measure,
+                                            uint64_t capacity, uint64_t* lims_out,
+                                            int32_t* ids_out, float* dists_out,
+                                            ggnn_location out_location, const int32_t* filter_ids,
+                                            ggnn_location ids_location, int ids_gpu_id)
+{
+  GGNN_NEED_HANDLE(h);
+  return guarded(h, [&] {
+    h->bf_range_query(GGNN_RANGE_REQUEST, radii, capacity, lims_out,
+                      QueryFilter::table_ids(*h, filter_ids, Nq, ids_location, ids_gpu_id));
+  });
+}
+
+ggnn_status ggnn_bf_range_query_labeled(ggnn_t* h, const void* query, uint64_t Nq, uint32_t D,
+                                        ggnn_dtype dtype, ggnn_location location, int gpu_id,
+                                        const float* radii, ggnn_measure measure,
+                                        uint64_t capacity, uint64_t* lims_out, int32_t* ids_out,
+                                        float* dists_out, ggnn_location out_location,
+                                        const int32_t* query_labels, ggnn_location labels_location,
+                                        int labels_gpu_id)
+{
+  GGNN_NEED_HANDLE(h);
+  return guarded(h, [&] {
+    h->bf_range_query(GGNN_RANGE_REQUEST, radii, capacity, lims_out,
+                      QueryFilter::labels(*h, query_labels, Nq, labels_location, labels_gpu_id));
+  });
+}
+#undef GGNN_RANGE_REQUEST
+
 ggnn_status ggnn_query_async_labeled(ggnn_t* h, const void* query, uint64_t Nq, uint32_t D,
                                      ggnn_dtype dtype, int gpu_id, uint32_t k_query,
                                      float tau_query, uint32_t max_iterations,
@@ -1427,6 +1488,72 @@ ggnn_status ggnn_op_bf_query_certified(const void* base, ggnn_dtype dtype, uint3
     launch_bf_query(b, static_cast<hipStream_t>(stream));
   });
 }
+
+// the range-search seam calls: lims [Nq + 1] uint64, ids / dists [capacity] (all device memory)
+#define GGNN_RANGE_LAUNCH \
+  BfRangeLaunch{base, query, dtype, N_base, D, Nq, measure, radii, capacity, lims, ids, dists}
+ggnn_status ggnn_op_bf_range_query(const void* base, ggnn_dtype dtype, uint32_t N_base, uint32_t D,
+                                   const void* query, uint32_t Nq, const float* radii,
+                                   ggnn_measure measure, uint64_t capacity, uint64_t* lims,
+                                   int32_t* ids, float* dists, void* stream)
+{
+  return guarded(nullptr, [&] {
+    launch_bf_range_query(GGNN_RANGE_LAUNCH, static_cast<hipStream_t>(stream));
+  });
+}
+
+ggnn_status ggnn_op_bf_range_query_filtered(const void* base, ggnn_dtype dtype, uint32_t N_base,
+                                            uint32_t D, const void* query, uint32_t Nq,
+                                            const float* radii, ggnn_measure measure,
+                                            uint64_t capacity, uint64_t* lims, int32_t* ids,
+                                            float* dists, const uint32_t* filter_bits,
+                                            uint32_t filter_bit_offset, void* stream)
+{
+  return guarded(nullptr, [&] {
+    GGNN_REQUIRE(filter_bits != nullptr, GGNN_INVALID_ARGUMENT, "the filter bitset is null");
+    BfRangeLaunch b = GGNN_RANGE_LAUNCH;
+    b.filter_bits = filter_bits;
+    b.filter_bit_offset = filter_bit_offset;
+    launch_bf_range_query(b, static_cast<hipStream_t>(stream));
+  });
+}
+
+ggnn_status ggnn_op_bf_range_query_filtered_by(const void* base, ggnn_dtype dtype, uint32_t N_base,
+                                               uint32_t D, const void* query, uint32_t Nq,
+                                               const float* radii, ggnn_measure measure,
+                                               uint64_t capacity, uint64_t* lims, int32_t* ids,
+                                               float* dists, const uint32_t* filter_table,
+                                               uint32_t num_filters, uint64_t n_bits,
+                                               const int32_t* filter_ids,
+                                               uint32_t filter_bit_offset, void* stream)
+{
+  return guarded(nullptr, [&] {
+    BfRangeLaunch b = GGNN_RANGE_LAUNCH;
+    b.filter_table =
+        seam_filter_table(filter_table, num_filters, n_bits, filter_ids, filter_bit_offset, N_base);
+    b.filter_bits = filter_table;
+    b.filter_bit_offset = filter_bit_offset;
+    launch_bf_range_query(b, static_cast<hipStream_t>(stream));
+  });
+}
+
+ggnn_status ggnn_op_bf_range_query_labeled(const void* base, ggnn_dtype dtype, uint32_t N_base,
+                                           uint32_t D, const void* query, uint32_t Nq,
+                                           const float* radii, ggnn_measure measure,
+                                           uint64_t capacity, uint64_t* lims, int32_t* ids,
+                                           float* dists, const int32_t* labels, uint64_t n_labels,
+                                           const int32_t* query_labels, uint32_t filter_bit_offset,
+                                           void* stream)
+{
+  return guarded(nullptr, [&] {
+    BfRangeLaunch b = GGNN_RANGE_LAUNCH;
+    b.filter_table = seam_labels(labels, n_labels, query_labels, filter_bit_offset, N_base);
+    b.filter_bits = reinterpret_cast<const uint32_t*>(labels);
+    b.filter_bit_offset = filter_bit_offset;
+    launch_bf_range_query(b, static_cast<hipStream_t>(stream));
+  });
+}
+#undef GGNN_RANGE_LAUNCH
 
 ggnn_status ggnn_op_top(const void* base, ggnn_dtype dtype, uint32_t D, ggnn_measure measure,
                         uint32_t KBuild, const int32_t* translation_layer, uint32_t N_layer,

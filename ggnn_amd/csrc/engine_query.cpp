@@ -465,18 +465,15 @@ void ggnn_handle::synchronize()
   }
 }
 
-// GGNNImpl::bfQueryImpl, ggnn.cu:332-390
-void ggnn_handle::bf_query(const QueryRequest& r, const QueryFilter& filter)
+// The whole base on the one GPU of an exhaustive call (bf_query, bf_range_query): the resident base,
+// or -- no graph yet -- the base made resident on the (first) selected GPU.
+DeviceCtx& ggnn_handle::bf_context(uint64_t Nq, uint32_t D, ggnn_dtype dtype, const void* q)
 {
-  const uint64_t Nq = r.Nq;
-  const uint32_t k_gt = r.k;
-  int32_t* const ids_out = r.ids_out;
-  float* const dists_out = r.dists_out;
   GGNN_REQUIRE(base_set, GGNN_INVALID_STATE,
                "There is no base dataset loaded which could be queried.");
   GGNN_REQUIRE(devs.size() <= 1, GGNN_INVALID_STATE,
                "The brute-force query only supports a single GPU.");
-  check_query(Nq, r.D, r.dtype, r.q);
+  check_query(Nq, D, dtype, q);
   if (devs.empty()) {
     // no graph yet: make the whole base resident on the (first) selected GPU
     const std::vector<int> gpus = resolve_gpus();
@@ -484,29 +481,44 @@ void ggnn_handle::bf_query(const QueryRequest& r, const QueryFilter& filter)
     devs[0].device = gpus[0];
     stage_base_slice(devs[0], 0, base_N);
   }
-  DeviceCtx& ctx = devs[0];
-  ctx.activate();
+  devs[0].activate();
+  return devs[0];
+}
+
+// ... and with out-of-core shards whose rows are on the host: the exhaustive scan needs the whole
+// base on the GPU for the duration of the call (fails with GGNN_OUT_OF_MEMORY if that is too much);
+// `whole_base` owns that copy
+const void* ggnn_handle::bf_whole_base(DeviceCtx& ctx, DeviceBuffer& whole_base)
+{
+  if (!(ctx.swap && !ctx.swap->base_borrowed))
+    return ctx.d_base;
+  const size_t es = dtype_size(base_dtype);
+  whole_base.alloc(base_N * pad_D * es);
+  const hipMemcpyKind kind = base_loc == GGNN_GPU ? hipMemcpyDefault : hipMemcpyHostToDevice;
+  if (pad_D != base_D) {
+    GGNN_HIP_CHECK(hipMemsetAsync(whole_base.p, 0, whole_base.bytes, ctx.stream));
+    GGNN_HIP_CHECK(hipMemcpy2DAsync(whole_base.p, pad_D * es, base_src, base_D * es, base_D * es,
+                                    base_N, kind, ctx.stream));
+  }
+  else
+    GGNN_HIP_CHECK(hipMemcpyAsync(whole_base.p, base_src, whole_base.bytes, kind, ctx.stream));
+  return whole_base.p;
+}
+
+// GGNNImpl::bfQueryImpl, ggnn.cu:332-390
+void ggnn_handle::bf_query(const QueryRequest& r, const QueryFilter& filter)
+{
+  const uint64_t Nq = r.Nq;
+  const uint32_t k_gt = r.k;
+  int32_t* const ids_out = r.ids_out;
+  float* const dists_out = r.dists_out;
+  DeviceCtx& ctx = bf_context(Nq, r.D, r.dtype, r.q);
   bf_ms = 0.f;
   last_bf_matrix_path = 0;
   if (!Nq)
     return;
-  // out-of-core shards with the rows on the host: the exhaustive scan needs the whole base on
-  // the GPU for the duration of the call (fails with GGNN_OUT_OF_MEMORY if that is too much)
   DeviceBuffer whole_base;
-  const void* bf_base = ctx.d_base;
-  if (ctx.swap && !ctx.swap->base_borrowed) {
-    const size_t es = dtype_size(base_dtype);
-    whole_base.alloc(base_N * pad_D * es);
-    const hipMemcpyKind kind = base_loc == GGNN_GPU ? hipMemcpyDefault : hipMemcpyHostToDevice;
-    if (pad_D != base_D) {
-      GGNN_HIP_CHECK(hipMemsetAsync(whole_base.p, 0, whole_base.bytes, ctx.stream));
-      GGNN_HIP_CHECK(hipMemcpy2DAsync(whole_base.p, pad_D * es, base_src, base_D * es, base_D * es,
-                                      base_N, kind, ctx.stream));
-    }
-    else
-      GGNN_HIP_CHECK(hipMemcpyAsync(whole_base.p, base_src, whole_base.bytes, kind, ctx.stream));
-    bf_base = whole_base.p;
-  }
+  const void* bf_base = bf_whole_base(ctx, whole_base);
   Staged sq = stage_query(ctx, r.q, Nq, r.D, r.dtype, r.loc, r.gpu);
   const uint32_t nq = static_cast<uint32_t>(Nq);
   const bool direct = (r.out_loc == GGNN_GPU);
@@ -546,6 +558,68 @@ void ggnn_handle::bf_query(const QueryRequest& r, const QueryFilter& filter)
                                   hipMemcpyDeviceToHost, ctx.stream));
   }
   GGNN_HIP_CHECK(hipStreamSynchronize(ctx.stream));
+}
+
+// Exact range search over the whole base (launch_bf_range_query): bf_query's staging, a CSR result.
+// lims is host memory; ids / dists follow r.out_loc and are written only if the total fits.
+void ggnn_handle::bf_range_query(const QueryRequest& r, const float* radii, uint64_t capacity,
+                                 uint64_t* lims_out, const QueryFilter& filter)
+{
+  const uint64_t Nq = r.Nq;
+  GGNN_REQUIRE(lims_out != nullptr, GGNN_INVALID_ARGUMENT, "lims is null");
+  GGNN_REQUIRE(!Nq || radii != nullptr, GGNN_INVALID_ARGUMENT, "the radius array is null");
+  GGNN_REQUIRE(capacity == 0 || (r.ids_out != nullptr && r.dists_out != nullptr),
+               GGNN_INVALID_ARGUMENT, "ids / dists are null with capacity > 0");
+  for (uint64_t i = 0; i < Nq; ++i)
+    GGNN_REQUIRE(radii[i] == radii[i], GGNN_INVALID_ARGUMENT,
+                 "the radius of query " + std::to_string(i) + " is NaN");
+  GGNN_REQUIRE(filter.kind == QueryFilter::None || filter.kind == QueryFilter::Bitset ||
+                   filter.kind == QueryFilter::TableIds || filter.kind == QueryFilter::Labels,
+               GGNN_UNSUPPORTED, "range search takes a bitset, filter ids or one label per query");
+  DeviceCtx& ctx = bf_context(Nq, r.D, r.dtype, r.q);
+  bf_ms = 0.f;
+  lims_out[0] = 0;
+  if (!Nq)
+    return;
+  DeviceBuffer whole_base;
+  const void* bf_base = bf_whole_base(ctx, whole_base);
+  Staged sq = stage_query(ctx, r.q, Nq, r.D, r.dtype, r.loc, r.gpu);
+  const uint32_t nq = static_cast<uint32_t>(Nq);
+  const bool direct = (r.out_loc == GGNN_GPU);
+  DeviceBuffer d_radii, d_lims, r_ids, r_dists;
+  d_radii.alloc(Nq * sizeof(float));
+  d_lims.alloc((Nq + 1) * sizeof(uint64_t));
+  GGNN_HIP_CHECK(hipMemcpyAsync(d_radii.p, radii, Nq * sizeof(float), hipMemcpyHostToDevice,
+                                ctx.stream));
+  int32_t* d_ids = r.ids_out;
+  float* d_dists = r.dists_out;
+  if (!direct && capacity) {
+    r_ids.alloc(capacity * 4);
+    r_dists.alloc(capacity * 4);
+    d_ids = r_ids.as<int32_t>();
+    d_dists = r_dists.as<float>();
+  }
+  BfRangeLaunch bl{bf_base,   sq.ptr,   base_dtype, static_cast<uint32_t>(base_N),
+                   pad_D,     nq,       r.measure,  d_radii.as<float>(),
+                   capacity,  d_lims.as<uint64_t>(), d_ids, d_dists};
+  const DeviceFilter df = resolve_filter(ctx, filter, DeviceCtx::kBlockingLane);
+  bl.filter_bits = df.bits;
+  bl.filter_table = df.table;
+  EventTimer timer(ctx.stream, ctx.ev_a, ctx.ev_b);
+  launch_bf_range_query(bl, ctx.stream);
+  bf_ms = timer.stop();
+  GGNN_HIP_CHECK(hipMemcpyAsync(lims_out, d_lims.p, (Nq + 1) * sizeof(uint64_t),
+                                hipMemcpyDeviceToHost, ctx.stream));
+  GGNN_HIP_CHECK(hipStreamSynchronize(ctx.stream));
+  GGNN_LOG(0, "[GPU: %d] brute-force range query: => ms: %.3f [%u points query, %llu results]",
+           ctx.device, bf_ms, nq, static_cast<unsigned long long>(lims_out[Nq]));
+  const uint64_t total = lims_out[Nq];
+  if (!direct && total && total <= capacity) {
+    GGNN_HIP_CHECK(hipMemcpyAsync(r.ids_out, d_ids, total * 4, hipMemcpyDeviceToHost, ctx.stream));
+    GGNN_HIP_CHECK(hipMemcpyAsync(r.dists_out, d_dists, total * 4, hipMemcpyDeviceToHost,
+                                  ctx.stream));
+    GGNN_HIP_CHECK(hipStreamSynchronize(ctx.stream));
+  }
 }
 
 // ---- the filter of one call: validated as the caller gave it, then resolved per GPU -------------

@@ -21,6 +21,7 @@ constexpr Entry kTable[kHookCount] = {
     {"QUERY_EARLY", 1},   {"MERGE_EARLY", 1},   {"QUERY_LDS_PAD", 0},
     {"QUERY_GLOBAL_RING", 1}, {"BF_I8_REFRESH", 64}, {"BF_I8_SEED", 0},
     {"MERGE_COUNTING", 0}, {"PS_EXACT", 1}, {"LABEL_INDEX_SLICES", 0},
+    {"BF_RANGE_SLICES", 0},
 };
 std::atomic<bool> g_set[kHookCount];
 std::atomic<int64_t> g_value[kHookCount];

@@ -40,6 +40,7 @@ enum Hook {
   kHookMergeCounting,   // MERGE_COUNTING   1 = merge launches without counters use the counting kernel too
   kHookPsExact,         // PS_EXACT         0 = query kernels always run the float phase, also on a lossless-grid base
   kHookLabelIndexSlices, // LABEL_INDEX_SLICES 0 auto | slices a label's rows are cut into by the index scan
+  kHookBfRangeSlices,   // BF_RANGE_SLICES  0 auto | base slices per query of the range search (bf_range.hip)
   kHookCount
 };
 

@@ -346,6 +346,99 @@ def bf_query_labeled(base, query, k_query, labels, query_labels, measure=EUCLIDE
     return ids, dists
 
 
+def range_radii(radius, Nq, device=None):
+    """`radius` of a range search as the float32 [Nq] tensor the kernels take: a scalar is broadcast
+    to every query, a sequence / tensor must have one entry per query."""
+    r = torch.as_tensor(radius, dtype=torch.float32)
+    if r.dim() == 0:
+        r = r.expand(Nq)
+    if r.dim() != 1 or r.numel() != Nq:
+        raise ValueError(f"radius must be a scalar or hold one entry per query ({Nq})")
+    return r.to(device if device is not None else r.device).contiguous()
+
+
+def sort_segments(lims, ids, dists):
+    """Reorder every segment [lims[n], lims[n + 1]) of a range-search result by (distance, id) --
+    what bf_query would list first.  The segments arrive in ascending id, so two stable sorts do it:
+    by distance, then by segment."""
+    lims = lims.to(torch.int64)
+    total = int(ids.numel())
+    if total == 0:
+        return ids, dists
+    seg = torch.repeat_interleave(torch.arange(lims.numel() - 1, device=ids.device),
+                                  (lims[1:] - lims[:-1]).to(ids.device))
+    by_d = torch.sort(dists, stable=True).indices
+    order = by_d[torch.sort(seg[by_d], stable=True).indices]
+    return ids[order], dists[order]
+
+
+def bf_range_query(base, query, radius, measure=EUCLIDEAN, capacity=None, filter_bits=None,
+                   filter_table=None, filter_ids=None, labels=None, query_labels=None,
+                   filter_bit_offset=0, out=None):
+    """Exact range search: every base row i whose filter admits it and whose distance to query n is
+    <= radius[n] (float32).  The distance is the one `bf_query`'s scan reports, bit for bit: under
+    EUCLIDEAN the SQUARED L2 distance -- so the radius is in squared units -- under COSINE |1 - cos|.
+    radius: a scalar or [Nq]; +inf admits every allowed row, a negative or NaN radius none.
+    Returns (lims, ids, dists) on the device, CSR-shaped: lims int64 [Nq + 1], the rows of query n at
+    [lims[n], lims[n + 1]) in ascending id.
+      capacity=None  a count-only call, one read of lims[-1] on the host, an exact allocation and a
+                     second call: three distance passes in all
+      capacity=c     one call into buffers of c entries (two passes; c = 0: count only, one pass),
+                     nothing waits for the host: if lims[-1] > c the buffers are left untouched --
+                     compare before reading them.  out=(ids, dists) gives the buffers to use.
+    Filters (at most one): filter_bits (row i: bit i + filter_bit_offset), filter_table + filter_ids
+    (see bf_query_filtered_by), labels + query_labels (see bf_query_labeled)."""
+    _need(base, name="base"), _need(query, base.dtype, "query")
+    Nq, N = query.shape[0], base.shape[0]
+    radii = range_radii(radius, Nq, base.device)
+    kinds = (filter_bits is not None) + (filter_ids is not None) + (query_labels is not None)
+    if kinds > 1:
+        raise ValueError("give at most one of filter_bits, filter_ids, query_labels")
+    if filter_bits is not None:
+        _need(filter_bits, torch.int32, "filter_bits")
+        if filter_bits.numel() * 32 < filter_bit_offset + N:
+            raise ValueError("filter_bits is shorter than filter_bit_offset + N bits")
+        fn = lib().ggnn_op_bf_range_query_filtered
+        tail = (_ptr(filter_bits), filter_bit_offset)
+    elif filter_ids is not None:
+        _need_filter_table(filter_table, filter_ids, Nq, filter_bit_offset + N)
+        fn = lib().ggnn_op_bf_range_query_filtered_by
+        tail = (_ptr(filter_table), filter_table.shape[0], filter_table.shape[1] * 32,
+                _ptr(filter_ids), filter_bit_offset)
+    elif query_labels is not None:
+        _need_labels(labels, query_labels, Nq, filter_bit_offset + N)
+        fn = lib().ggnn_op_bf_range_query_labeled
+        tail = (_ptr(labels), labels.numel(), _ptr(query_labels), filter_bit_offset)
+    else:
+        fn, tail = lib().ggnn_op_bf_range_query, ()
+    lims = torch.empty(Nq + 1, dtype=torch.int64, device=base.device)
+
+    def call(cap, ids, dists):
+        check(fn(_ptr(base), _dtype_code(base), N, base.shape[1], _ptr(query), Nq, _ptr(radii),
+                 measure, cap, _ptr(lims), _ptr(ids), _ptr(dists), *tail, _stream()))
+
+    if out is not None:
+        ids, dists = out
+        _need(ids, torch.int32, "ids"), _need(dists, torch.float32, "dists")
+        cap = min(ids.numel(), dists.numel()) if capacity is None else int(capacity)
+        if cap > min(ids.numel(), dists.numel()):
+            raise ValueError("capacity exceeds the buffers of `out`")
+        call(cap, ids, dists)
+        return lims, ids, dists
+    counted = capacity is None
+    if counted:
+        call(0, None, None)
+        capacity = int(lims[-1].item())
+    capacity = int(capacity)
+    ids = torch.empty(capacity, dtype=torch.int32, device=base.device)
+    dists = torch.empty(capacity, dtype=torch.float32, device=base.device)
+    if capacity:
+        call(capacity, ids, dists)
+    elif not counted:
+        call(0, None, None)
+    return lims, ids, dists
+
+
 def label_index_build(labels):
     """The index of an int32 label column (host; any CPU tensor or array of n labels, 1 <= n <= 2^30):
     (keys [L], offsets [L + 1], rows [n]) as int32 CPU tensors -- the distinct labels ascending, the

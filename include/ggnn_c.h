@@ -269,6 +269,52 @@ ggnn_status ggnn_query_async_labeled(ggnn_t* h, const void* query, uint64_t Nq, 
                                      ggnn_measure measure, int32_t* ids_out, float* dists_out,
                                      uint32_t slot, const int32_t* query_labels);
 
+/* Exact range search (an extension): EVERY base vector within a radius of each query, where
+ * ggnn_bf_query returns the k_gt best.  Base row i belongs to the answer of query n iff the call's
+ * filter admits it and d(n, i) <= radii[n], compared in float32; d is the float32 value the scan
+ * kernels of ggnn_bf_query report for the pair, bit for bit.
+ *   *** A Euclidean radius is in SQUARED units: d is the squared L2 distance (no square root). ***
+ *   Cosine: d = |1 - cos|; a zero row or a zero query gives 1.0.
+ * radii[Nq] is HOST memory, one radius per query: +inf admits every allowed row whose distance is not
+ * NaN, a negative radius admits nothing, a NaN radius is GGNN_INVALID_ARGUMENT.
+ * The result is CSR-shaped: lims_out[Nq + 1] (HOST memory, always written: lims_out[0] = 0,
+ * lims_out[Nq] the total), and the rows of query n at ids_out / dists_out [lims_out[n], lims_out[n + 1])
+ * in ASCENDING ID.  ids_out / dists_out hold `capacity` entries at out_location.  If lims_out[Nq] >
+ * capacity they are left untouched and the call still returns GGNN_OK: compare lims_out[Nq] with the
+ * capacity, and call again with enough room.  ids_out == dists_out == NULL with capacity == 0 is the
+ * count-only call.  Every call evaluates all distances twice (a counting pass and a filling pass;
+ * once when capacity == 0); no atomics decide a position, so results do not vary from run to run.
+ * The *_filtered, *_filtered_by and *_labeled forms take the filter of the ggnn_bf_query call of the
+ * same name, with the same rules (label -1 / filter id -1: every row).  Label sets, label ranges and
+ * label masks have no range form.  Single GPU, any state of the handle after ggnn_set_base, exactly
+ * as ggnn_bf_query; always scan kernels (hook BF_RANGE_SLICES forces their slice count). */
+ggnn_status ggnn_bf_range_query(ggnn_t* h, const void* query, uint64_t Nq, uint32_t D,
+                                ggnn_dtype dtype, ggnn_location location, int gpu_id,
+                                const float* radii, ggnn_measure measure, uint64_t capacity,
+                                uint64_t* lims_out, int32_t* ids_out, float* dists_out,
+                                ggnn_location out_location);
+ggnn_status ggnn_bf_range_query_filtered(ggnn_t* h, const void* query, uint64_t Nq, uint32_t D,
+                                         ggnn_dtype dtype, ggnn_location location, int gpu_id,
+                                         const float* radii, ggnn_measure measure,
+                                         uint64_t capacity, uint64_t* lims_out, int32_t* ids_out,
+                                         float* dists_out, ggnn_location out_location,
+                                         const uint32_t* allowed_bits, uint64_t n_bits,
+                                         ggnn_location filter_location, int filter_gpu_id);
+ggnn_status ggnn_bf_range_query_filtered_by(ggnn_t* h, const void* query, uint64_t Nq, uint32_t D,
+                                            ggnn_dtype dtype, ggnn_location location, int gpu_id,
+                                            const float* radii, ggnn_measure measure,
+                                            uint64_t capacity, uint64_t* lims_out,
+                                            int32_t* ids_out, float* dists_out,
+                                            ggnn_location out_location, const int32_t* filter_ids,
+                                            ggnn_location ids_location, int ids_gpu_id);
+ggnn_status ggnn_bf_range_query_labeled(ggnn_t* h, const void* query, uint64_t Nq, uint32_t D,
+                                        ggnn_dtype dtype, ggnn_location location, int gpu_id,
+                                        const float* radii, ggnn_measure measure,
+                                        uint64_t capacity, uint64_t* lims_out, int32_t* ids_out,
+                                        float* dists_out, ggnn_location out_location,
+                                        const int32_t* query_labels, ggnn_location labels_location,
+                                        int labels_gpu_id);
+
 /* Label index: a label's rows found without reading the label column.
  * The index is the label column grouped by label (CSR over the global base ids: the distinct labels
  * ascending, and the ids of every label ascending), 4 * N + 8 * L + 4 bytes for L distinct labels.
@@ -622,7 +668,10 @@ void ggnn_set_log_level(int level);
  *   LABEL_INDEX_SLICES  0     slices the index scans (one label, label spans) cut a query's rows into
  *                             (1..64): 0 = chosen from the longest segment the call can touch -- for
  *                             spans, span_limit -- and the number of queries (same results for every
- *                             count; test hook) */
+ *                             count; test hook)
+ *   BF_RANGE_SLICES     0     slices the range search cuts the base into per query (1..64): 0 = chosen
+ *                             like the scan's, from the number of queries and rows (same results
+ *                             for every count; test hook) */
 ggnn_status ggnn_set_hook(const char* name, int64_t value);
 /* back to environment / default */
 ggnn_status ggnn_reset_hook(const char* name);
@@ -763,6 +812,39 @@ ggnn_status ggnn_op_bf_query_labeled(const void* base, ggnn_dtype dtype, uint32_
                                      const int32_t* labels, uint64_t n_labels,
                                      const int32_t* query_labels, uint32_t filter_bit_offset,
                                      void* stream);
+/* Range search at the seam (all device memory, stream-ordered: a counting launch, a prefix launch and
+ * a filling launch on `stream`, nothing waits for the host): ggnn_bf_range_query's semantics with
+ * radii[Nq], lims[Nq + 1] (uint64) and ids / dists [capacity] in device memory.  lims is always
+ * written; ids / dists only if lims[Nq] <= capacity (they may be null with capacity 0), rows in
+ * ascending id whatever the number of slices.  A Euclidean radius is in SQUARED units.  A NaN radius
+ * admits nothing here (the handle refuses it).  The filter arguments are those of
+ * ggnn_op_bf_query_filtered / _filtered_by / _labeled; any filter_bit_offset (there is no matrix-core
+ * path), 8-bit rows need D % 16 == 0, labels at most 2^30 rows. */
+ggnn_status ggnn_op_bf_range_query(const void* base, ggnn_dtype dtype, uint32_t N_base, uint32_t D,
+                                   const void* query, uint32_t Nq, const float* radii,
+                                   ggnn_measure measure, uint64_t capacity, uint64_t* lims,
+                                   int32_t* ids, float* dists, void* stream);
+ggnn_status ggnn_op_bf_range_query_filtered(const void* base, ggnn_dtype dtype, uint32_t N_base,
+                                            uint32_t D, const void* query, uint32_t Nq,
+                                            const float* radii, ggnn_measure measure,
+                                            uint64_t capacity, uint64_t* lims, int32_t* ids,
+                                            float* dists, const uint32_t* filter_bits,
+                                            uint32_t filter_bit_offset, void* stream);
+ggnn_status ggnn_op_bf_range_query_filtered_by(const void* base, ggnn_dtype dtype, uint32_t N_base,
+                                               uint32_t D, const void* query, uint32_t Nq,
+                                               const float* radii, ggnn_measure measure,
+                                               uint64_t capacity, uint64_t* lims, int32_t* ids,
+                                               float* dists, const uint32_t* filter_table,
+                                               uint32_t num_filters, uint64_t n_bits,
+                                               const int32_t* filter_ids,
+                                               uint32_t filter_bit_offset, void* stream);
+ggnn_status ggnn_op_bf_range_query_labeled(const void* base, ggnn_dtype dtype, uint32_t N_base,
+                                           uint32_t D, const void* query, uint32_t Nq,
+                                           const float* radii, ggnn_measure measure,
+                                           uint64_t capacity, uint64_t* lims, int32_t* ids,
+                                           float* dists, const int32_t* labels, uint64_t n_labels,
+                                           const int32_t* query_labels, uint32_t filter_bit_offset,
+                                           void* stream);
 /* ggnn_op_bf_query_labeled through a label index (ggnn_label_index_build of the column, copied to
  * the device: keys[n_keys], offsets[n_keys + 1], rows[N_base]): every query reads only the rows of its
  * label.  Every output bit equals what ggnn_op_bf_query_labeled gives for the same base, labels and
