@@ -27,6 +27,8 @@ g.set_base(base)                       # no graph needed: the exact search scans
 r = 0.2
 query = base[:2000]
 lims, ids, dists = g.bf_range_query(query, r * r)            # squared units
+# (1: pre-selected on the matrix cores, every hit decided exactly; 0: the scan -- the same bits)
+print("tile kernels:", g.last_bf_range_matrix_path())
 counts = np.diff(lims.numpy())
 # every row matches itself at distance 0 and comes first (sorted by distance, then id)
 assert (ids.numpy()[lims.numpy()[:-1]] == np.arange(len(query))).all()

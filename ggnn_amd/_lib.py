@@ -248,6 +248,14 @@ SIGNATURES = {
                                                   _vp, _vp, _vp, _vp, _u32, _u64, _vp, _u32, _vp]),
     "ggnn_op_bf_range_query_labeled": (_int, [_vp, _int, _u32, _u32, _vp, _u32, _vp, _int, _u64,
                                               _vp, _vp, _vp, _vp, _u64, _vp, _u32, _vp]),
+    # ..., dists, filter_bits, filter_table, F, n_bits, filter_ids, labels, n_labels, query_labels,
+    # bit offset, fell_back (device), matrix_path (host int), stream
+    "ggnn_op_bf_range_query_routed": (_int, [_vp, _int, _u32, _u32, _vp, _u32, _vp, _int, _u64, _vp,
+                                             _vp, _vp, _vp, _vp, _u32, _u64, _vp, _vp, _u64, _vp,
+                                             _u32, _vp, C.POINTER(C.c_int), _vp]),
+    "ggnn_last_bf_range_matrix_path": (_int, [_vp, C.POINTER(C.c_int)]),
+    "ggnn_debug_bf_range_route": (_int, [_int, _u32, _u32, _u32, _u64, _int, _u32,
+                                         C.POINTER(_u64)]),
     "ggnn_last_exchange": (C.c_char_p, [_vp]),
     "ggnn_op_top": (_int, [_vp, _int, _u32, _int, _u32, _vp, _u32, _u32, _u32, _u32, _vp, _vp,
                            _vp]),

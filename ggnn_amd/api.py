@@ -1302,6 +1302,13 @@ class GGNN:
         self._check(lib().ggnn_last_bf_query_matrix_path(self._h, C.byref(n)))
         return int(n.value)
 
+    def last_bf_range_matrix_path(self):
+        """1 if the last bf_range_query* call chose the matrix-core tile kernels (pre-selection,
+        every hit decided exactly), else 0 (the scan kernels); the same bits on either path"""
+        n = C.c_int()
+        self._check(lib().ggnn_last_bf_range_matrix_path(self._h, C.byref(n)))
+        return int(n.value)
+
     def last_query_counters(self):
         d, p = C.c_uint64(), C.c_uint64()
         self._check(lib().ggnn_last_query_counters(self._h, C.byref(d), C.byref(p)))

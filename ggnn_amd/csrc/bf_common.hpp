@@ -76,6 +76,12 @@ constexpr bool bf_filtered_runs_chunked(uint32_t D, uint32_t k_query)
 const void* bf_mfma_bits_kernel(ggnn_dtype dtype, ggnn_measure measure, int T, int NU, int KPC);
 const void* bf_mfma_labels_kernel(ggnn_dtype dtype, ggnn_measure measure, int T, int NU, int KPC);
 
+// bf_mfma.hip: the shift of float32 squared L2 -- mean[D] = column mean of (a sample of) the base,
+// q_shifted = fl(query - mean); partial is kBfMeanBlocks x D floats of scratch
+constexpr uint32_t kBfMeanBlocks = 256;
+void bf_center_rows(const float* base, uint32_t N_base, uint32_t D, const float* query, uint32_t Nq,
+                    float* mean, float* partial, float* q_shifted, hipStream_t stream);
+
 typedef int i32x16 __attribute__((ext_vector_type(16)));
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 constexpr uint32_t kBfI8RowStride = 144;
@@ -198,5 +204,17 @@ GGNN_DEV bool bf_allowed(const BfArgs& a, const BfLabelFilter& f, uint32_t word,
 
 // (bf_query.hip; shared with the label-family scans and bf_range.hip)
 void bf_slice_rows(uint32_t N_base, uint32_t& slices, uint32_t& rows_per_slice);
+
+// ---- range search (bf_range.hip: the scan; bf_range_mfma.hip: tile pre-selection, exact hits) -----
+// dtype / D / filter of a launch suit the tile kernels, and (hook BF_RANGE_PATH = 0) Nq and N_base
+// reach their minima; BF_RANGE_PATH = 1 says no to everything, 2 waives the minima
+void launch_bf_range_query_mfma(const BfRangeLaunch& a, hipStream_t stream);
+// The scan passes (count, prefix, fill) of a validated launch.  gate (device, or null: the plain scan):
+// with *gate == 0 every wave of the count and fill passes returns before it touches the base, and
+// what the prefix pass then writes to a.lims means nothing -- the caller gives it lims of its own.
+void launch_bf_range_scan(const BfRangeLaunch& a, const uint32_t* gate, hipStream_t stream);
+// bf_range_prefix_kernel: counts [Nq x slices] -> exclusive offsets [Nq x slices] and lims [Nq + 1]
+void launch_bf_range_prefix(const uint32_t* counts, uint32_t Nq, uint32_t slices, uint64_t* offsets,
+                            uint64_t* lims, hipStream_t stream);
 
 }  // namespace ggnn_amd

@@ -144,7 +144,17 @@ __global__ void __launch_bounds__(256) row_norms_kernel(const BaseT* data, uint3
   }
 }
 
-#ifndef GGNN_BF_FILTER_TU  // (kernels and host code that exist once: not in the filtered units)
+inline uint32_t norm_grid(uint32_t rows)
+{
+  // (2048 workgroups: enough to fill the chip with four rows in flight per lane group, and a
+  // quarter of the per-wave atomics on the one norm-maximum word, which is what a launch of 8192
+  // spent most of its 0.37 ms on)
+  return std::max(1u, std::min((rows + 15u) / 16u, 2048u));
+}
+
+// (kernels and host code that exist once: not in the filtered units, nor in bf_range_mfma.hip,
+// which takes the shared device code of this file only: GGNN_BF_SHARED_ONLY)
+#if !defined(GGNN_BF_FILTER_TU) && !defined(GGNN_BF_SHARED_ONLY)
 // out = fl(in - mean), row by row: the query set is shifted once, up front (it is small), so that
 // the tile kernels load their A operand without touching the mean
 __global__ void __launch_bounds__(256) shift_rows_kernel(const float* in, uint64_t n4, uint32_t D,
@@ -159,19 +169,10 @@ __global__ void __launch_bounds__(256) shift_rows_kernel(const float* in, uint64
   }
 }
 
-inline uint32_t norm_grid(uint32_t rows)
-{
-  // (2048 workgroups: enough to fill the chip with four rows in flight per lane group, and a
-  // quarter of the per-wave atomics on the one norm-maximum word, which is what a launch of 8192
-  // spent most of its 0.37 ms on)
-  return std::max(1u, std::min((rows + 15u) / 16u, 2048u));
-}
-
 // Column means of (a sample of) the base: partial[p][c] = sum over rows p, p+P, ... of the
 // sampled rows; finalised in a fixed order, so the shift -- and with it every intermediate of the
 // tile kernel -- is the same from run to run.  The shift only has to be close to the data: any
 // vector gives exact results (see the certificate above).
-constexpr uint32_t kBfMeanBlocks = 256;
 __global__ void __launch_bounds__(256) col_mean_partial_kernel(const float* data, uint32_t N,
                                                               uint32_t D, uint32_t stride,
                                                               uint32_t rows, float* partial)
@@ -773,6 +774,9 @@ GGNN_DEV bool bf_label_denied(int32_t ql, int32_t row_label)
   return ql != -1 && ql != row_label;
 }
 
+#ifdef GGNN_BF_SHARED_ONLY
+}  // namespace ggnn_amd
+#else
 // T = base tiles per group whose accumulators stay in registers while the K chunks stream by
 // (T = 1 for D <= 128: a single chunk, the query tile is loaded once per workgroup).
 // NU (T = 1 only): float4 steps per half row, Dh = 4*NU -- a compile-time trip count keeps the
@@ -1512,6 +1516,24 @@ size_t bf_rescan_tmp_entries(const BfLaunch& a, uint32_t* slices_out);
 void launch_bf_rescan(const BfLaunch& a, const uint32_t* qlist, const uint32_t* qcount,
                       int32_t* tmp_ids, float* tmp_dists, hipStream_t stream);
 
+// mean[D] = column mean of (a sample of) the float32 base, q_shifted = fl(query - mean)
+// (partial: kBfMeanBlocks x D floats of scratch)
+void bf_center_rows(const float* base, uint32_t N_base, uint32_t D, const float* query, uint32_t Nq,
+                    float* mean, float* partial, float* q_shifted, hipStream_t stream)
+{
+  // at most ~32k evenly spaced rows: plenty for a shift, negligible next to the scan itself
+  const uint32_t stride = std::max(1u, N_base / 16384u);
+  const uint32_t rows = (N_base + stride - 1) / stride;
+  hipLaunchKernelGGL(col_mean_partial_kernel, dim3(kBfMeanBlocks), dim3(256), 0, stream, base, N_base,
+                     D, stride, rows, partial);
+  hipLaunchKernelGGL(col_mean_final_kernel, dim3((D + 255) / 256), dim3(256), 0, stream, partial, D,
+                     rows, mean);
+  const uint64_t n4 = static_cast<uint64_t>(Nq) * D / 4;
+  hipLaunchKernelGGL(shift_rows_kernel,
+                     dim3(static_cast<uint32_t>(std::min<uint64_t>((n4 + 255) / 256, 4096))),
+                     dim3(256), 0, stream, query, n4, D, mean, q_shifted);
+}
+
 void launch_bf_query_mfma(const BfLaunch& a, hipStream_t stream)
 {
   check_vector_layout(a.base, a.D, a.dtype);
@@ -1635,20 +1657,9 @@ void launch_bf_query_mfma(const BfLaunch& a, hipStream_t stream)
                                      parts, stream));
   }
 
-  if (center) {
-    // at most ~32k evenly spaced rows: plenty for a shift, negligible next to the scan itself
-    const uint32_t stride = std::max(1u, a.N_base / 16384u);
-    const uint32_t rows = (a.N_base + stride - 1) / stride;
-    hipLaunchKernelGGL(col_mean_partial_kernel, dim3(kBfMeanBlocks), dim3(256), 0, stream,
-                       static_cast<const float*>(a.base), a.N_base, a.D, stride, rows, partial);
-    hipLaunchKernelGGL(col_mean_final_kernel, dim3((a.D + 255) / 256), dim3(256), 0, stream, partial,
-                       a.D, rows, mean);
-    const uint64_t n4 = static_cast<uint64_t>(a.Nq) * a.D / 4;
-    hipLaunchKernelGGL(shift_rows_kernel,
-                       dim3(static_cast<uint32_t>(std::min<uint64_t>((n4 + 255) / 256, 4096))),
-                       dim3(256), 0, stream, static_cast<const float*>(a.query), n4, a.D, mean,
-                       q_shifted);
-  }
+  if (center)
+    bf_center_rows(static_cast<const float*>(a.base), a.N_base, a.D,
+                   static_cast<const float*>(a.query), a.Nq, mean, partial, q_shifted, stream);
   const float* d_mean = center ? mean : nullptr;
   // what the tile and norm kernels see as the query set (the re-rank works on the original rows)
   const void* tile_query = center ? static_cast<const void*>(q_shifted) : a.query;
@@ -1908,3 +1919,4 @@ extern "C" int ggnn_debug_bf_phase(unsigned long long* out8, int reset)
   return 0;
 }
 #endif
+#endif  // GGNN_BF_SHARED_ONLY

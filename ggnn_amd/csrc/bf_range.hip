@@ -11,6 +11,8 @@
 //           offset + popcount(hits below j), so a query's rows stand in ascending id without a sort.
 //           A wave leaves at once when lims[Nq] exceeds the capacity: ids / dists stay untouched.
 // Count and fill are one kernel body with one `if constexpr`: they cannot disagree.
+// Calls that suit the tile kernels go to bf_range_mfma.hip (launch_bf_range_query routes); that path
+// enqueues these passes behind itself with a gate word, as its fallback (launch_bf_range_scan).
 #include <algorithm>
 
 #include "bf_common.hpp"
@@ -26,6 +28,9 @@ struct BfRangeArgs : BfFilteredArgs {
   const uint64_t* offsets;  // [Nq x slices] exclusive, read by the fill pass
   const uint64_t* lims;     // [Nq + 1], read by the fill pass
   uint64_t capacity;
+  // null on the plain scan path.  Behind the tile path (bf_range_mfma.hip) the scan passes are
+  // always enqueued; their waves leave at once unless the candidate budget overflowed (*gate != 0)
+  const uint32_t* gate;
 };
 
 template <typename BaseT, int LPR, int NCH, int MODE, bool FILT, bool LAB, bool FILL>
@@ -41,6 +46,8 @@ __global__ void __launch_bounds__(kWave) bf_range_kernel(const BfRangeArgs a)
   const int lane = threadIdx.x;
   const uint32_t bid = block_linear_index();
   if (bid >= a.Nq * a.slices)
+    return;
+  if (a.gate && *a.gate == 0)  // (wave-uniform)
     return;
   const uint32_t n = bid / a.slices;
   const uint32_t slice = bid % a.slices;
@@ -200,11 +207,23 @@ static void launch_bf_range_pass(const BfRangeLaunch& a, const BfRangeArgs& args
   GGNN_HIP_CHECK(hipGetLastError());
 }
 
+void launch_bf_range_prefix(const uint32_t* counts, uint32_t Nq, uint32_t slices, uint64_t* offsets,
+                            uint64_t* lims, hipStream_t stream)
+{
+  hipLaunchKernelGGL(bf_range_prefix_kernel, dim3(1), dim3(kPrefixThreads), 0, stream, counts, Nq,
+                     slices, offsets, lims);
+  GGNN_HIP_CHECK(hipGetLastError());
+}
+
 void launch_bf_range_query(const BfRangeLaunch& a_in, hipStream_t stream)
 {
   GGNN_REQUIRE(a_in.lims != nullptr, GGNN_INVALID_ARGUMENT, "range query: lims is null");
   GGNN_REQUIRE(a_in.capacity == 0 || (a_in.ids != nullptr && a_in.dists != nullptr),
                GGNN_INVALID_ARGUMENT, "range query: ids / dists are null with capacity > 0");
+  if (a_in.matrix_path)
+    *a_in.matrix_path = 0;
+  if (a_in.fell_back)
+    GGNN_HIP_CHECK(hipMemsetAsync(a_in.fell_back, 0, sizeof(uint32_t), stream));
   if (a_in.Nq == 0) {
     GGNN_HIP_CHECK(hipMemsetAsync(a_in.lims, 0, sizeof(uint64_t), stream));
     return;
@@ -231,6 +250,18 @@ void launch_bf_range_query(const BfRangeLaunch& a_in, hipStream_t stream)
   if (consts.p)
     a.filter_table.consts = static_cast<const uint32_t*>(consts.p);
 
+  // tile pre-selection on the matrix cores with exact hits (bf_range_mfma.hip), or the scan
+  if (bf_range_mfma_supported(a)) {
+    if (a.matrix_path)
+      *a.matrix_path = 1;
+    launch_bf_range_query_mfma(a, stream);
+  }
+  else
+    launch_bf_range_scan(a, nullptr, stream);
+}
+
+void launch_bf_range_scan(const BfRangeLaunch& a, const uint32_t* gate, hipStream_t stream)
+{
   // slices as launch_bf_query chooses them; hook BF_RANGE_SLICES forces the count
   uint32_t slices = 1;
   const int64_t forced = hook(kHookBfRangeSlices);
@@ -268,11 +299,10 @@ void launch_bf_range_query(const BfRangeLaunch& a_in, hipStream_t stream)
   args.offsets = offsets;
   args.lims = a.lims;
   args.capacity = a.capacity;
+  args.gate = gate;
 
   launch_bf_range_pass(a, args, /*fill=*/false, stream);
-  hipLaunchKernelGGL(bf_range_prefix_kernel, dim3(1), dim3(kPrefixThreads), 0, stream, counts, a.Nq,
-                     slices, offsets, a.lims);
-  GGNN_HIP_CHECK(hipGetLastError());
+  launch_bf_range_prefix(counts, a.Nq, slices, offsets, a.lims, stream);
   // (capacity 0: the count-only call, and a total of 0 needs no fill)
   if (a.capacity != 0)
     launch_bf_range_pass(a, args, /*fill=*/true, stream);

@@ -290,6 +290,8 @@ void launch_bf_query(const BfLaunch& a, hipStream_t stream);
 // A NaN radius and a negative one admit nothing.  All device memory, nothing waits for the host.
 // Filters: none, a bitset (filter_bits), a filter table (filter_table.ids) or one label per query
 // (filter_table.query_labels) -- BfLaunch's rules.
+// Float rows in large batches are pre-selected on the matrix cores and every hit decided exactly
+// (bf_range_mfma.hip, bf_range_mfma_supported); the scan kernels answer the rest.  Same bits.
 struct BfRangeLaunch {
   const void* base;
   const void* query;
@@ -304,8 +306,17 @@ struct BfRangeLaunch {
   const uint32_t* filter_bits{nullptr};
   uint32_t filter_bit_offset{0};
   FilterTable filter_table{};
+  // tile path (bf_range_mfma.hip): 1 if the candidate budget overflowed and the scan answered the
+  // call, else 0 (device, optional); *matrix_path (host, optional) = the tile path was chosen
+  uint32_t* fell_back{nullptr};
+  int* matrix_path{nullptr};
 };
 void launch_bf_range_query(const BfRangeLaunch& a, hipStream_t stream);
+// host side of the tile path (bf_range_mfma.hip): the routing predicate -- decided before anything is
+// enqueued, from dtype, D, Nq, N_base, capacity, the filter form and hook BF_RANGE_PATH -- and the
+// dynamic LDS of a tile workgroup (fm: 0 none, 1 bitset / table, 2 labels)
+bool bf_range_mfma_supported(const BfRangeLaunch& a);
+size_t bf_range_tile_lds_bytes(uint32_t D, int fm);
 
 // Label index (label_index.hip): the label column in CSR form over the global base ids -- keys[n_keys]
 // the distinct labels ascending, offsets[n_keys + 1] uint32 positions (offsets[0] = 0, offsets[n_keys]

@@ -964,6 +964,32 @@ ggnn_status ggnn_last_bf_query_rescanned(const ggnn_t* h, uint32_t* n_rescanned)
   return GGNN_OK;
 }
 
+// tests: the host side of the range tile path, no device touched.  filter: 0 none, 1 bitset / table,
+// 2 labels (the pointers only say which form the launch has)
+int ggnn_debug_bf_range_route(ggnn_dtype dtype, uint32_t D, uint32_t Nq, uint32_t N_base,
+                              uint64_t capacity, int filter, uint32_t filter_bit_offset,
+                              uint64_t* tile_lds_bytes)
+{
+  static const uint32_t word = 0;
+  static const int32_t label = 0;
+  BfRangeLaunch b{};
+  b.dtype = dtype, b.D = D, b.Nq = Nq, b.N_base = N_base, b.capacity = capacity;
+  b.filter_bits = filter ? &word : nullptr;
+  b.filter_bit_offset = filter_bit_offset;
+  b.filter_table.query_labels = filter == 2 ? &label : nullptr;
+  if (tile_lds_bytes)
+    *tile_lds_bytes = bf_range_tile_lds_bytes(D, filter);
+  return bf_range_mfma_supported(b) ? 1 : 0;
+}
+
+ggnn_status ggnn_last_bf_range_matrix_path(const ggnn_t* h, int* out)
+{
+  if (!h || !out)
+    return GGNN_INVALID_ARGUMENT;
+  *out = h->last_bf_range_matrix_path;
+  return GGNN_OK;
+}
+
 ggnn_status ggnn_last_bf_query_matrix_path(const ggnn_t* h, int* out)
 {
   GGNN_NEED_HANDLE(h);
@@ -1550,6 +1576,39 @@ ggnn_status ggnn_op_bf_range_query_labeled(const void* base, ggnn_dtype dtype, u
     b.filter_table = seam_labels(labels, n_labels, query_labels, filter_bit_offset, N_base);
     b.filter_bits = reinterpret_cast<const uint32_t*>(labels);
     b.filter_bit_offset = filter_bit_offset;
+    launch_bf_range_query(b, static_cast<hipStream_t>(stream));
+  });
+}
+
+ggnn_status ggnn_op_bf_range_query_routed(const void* base, ggnn_dtype dtype, uint32_t N_base,
+                                          uint32_t D, const void* query, uint32_t Nq,
+                                          const float* radii, ggnn_measure measure,
+                                          uint64_t capacity, uint64_t* lims, int32_t* ids,
+                                          float* dists, const uint32_t* filter_bits,
+                                          const uint32_t* filter_table, uint32_t num_filters,
+                                          uint64_t n_bits, const int32_t* filter_ids,
+                                          const int32_t* labels, uint64_t n_labels,
+                                          const int32_t* query_labels, uint32_t filter_bit_offset,
+                                          uint32_t* fell_back, int* matrix_path, void* stream)
+{
+  return guarded(nullptr, [&] {
+    GGNN_REQUIRE((filter_bits != nullptr) + (filter_ids != nullptr) + (query_labels != nullptr) <= 1,
+                 GGNN_INVALID_ARGUMENT, "give at most one of filter_bits, filter_ids, query_labels");
+    BfRangeLaunch b = GGNN_RANGE_LAUNCH;
+    b.filter_bit_offset = filter_bit_offset;
+    if (filter_bits)
+      b.filter_bits = filter_bits;
+    else if (filter_ids) {
+      b.filter_table =
+          seam_filter_table(filter_table, num_filters, n_bits, filter_ids, filter_bit_offset, N_base);
+      b.filter_bits = filter_table;
+    }
+    else if (query_labels) {
+      b.filter_table = seam_labels(labels, n_labels, query_labels, filter_bit_offset, N_base);
+      b.filter_bits = reinterpret_cast<const uint32_t*>(labels);
+    }
+    b.fell_back = fell_back;
+    b.matrix_path = matrix_path;
     launch_bf_range_query(b, static_cast<hipStream_t>(stream));
   });
 }

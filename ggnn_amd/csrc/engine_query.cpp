@@ -605,6 +605,8 @@ void ggnn_handle::bf_range_query(const QueryRequest& r, const float* radii, uint
   const DeviceFilter df = resolve_filter(ctx, filter, DeviceCtx::kBlockingLane);
   bl.filter_bits = df.bits;
   bl.filter_table = df.table;
+  last_bf_range_matrix_path = 0;
+  bl.matrix_path = &last_bf_range_matrix_path;
   EventTimer timer(ctx.stream, ctx.ev_a, ctx.ev_b);
   launch_bf_range_query(bl, ctx.stream);
   bf_ms = timer.stop();

@@ -41,6 +41,8 @@ enum Hook {
   kHookPsExact,         // PS_EXACT         0 = query kernels always run the float phase, also on a lossless-grid base
   kHookLabelIndexSlices, // LABEL_INDEX_SLICES 0 auto | slices a label's rows are cut into by the index scan
   kHookBfRangeSlices,   // BF_RANGE_SLICES  0 auto | base slices per query of the range search (bf_range.hip)
+  kHookBfRangePath,     // BF_RANGE_PATH    0 auto | 1 scan always | 2 tile kernels whenever dtype / D / filter allow
+  kHookBfRangeCand,     // BF_RANGE_CAND    0 auto | entries of the tile path's candidate buffer (bf_range_mfma.hip)
   kHookCount
 };
 

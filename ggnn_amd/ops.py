@@ -374,7 +374,7 @@ def sort_segments(lims, ids, dists):
 
 def bf_range_query(base, query, radius, measure=EUCLIDEAN, capacity=None, filter_bits=None,
                    filter_table=None, filter_ids=None, labels=None, query_labels=None,
-                   filter_bit_offset=0, out=None):
+                   filter_bit_offset=0, out=None, routed=False):
     """Exact range search: every base row i whose filter admits it and whose distance to query n is
     <= radius[n] (float32).  The distance is the one `bf_query`'s scan reports, bit for bit: under
     EUCLIDEAN the SQUARED L2 distance -- so the radius is in squared units -- under COSINE |1 - cos|.
@@ -387,7 +387,12 @@ def bf_range_query(base, query, radius, measure=EUCLIDEAN, capacity=None, filter
                      nothing waits for the host: if lims[-1] > c the buffers are left untouched --
                      compare before reading them.  out=(ids, dists) gives the buffers to use.
     Filters (at most one): filter_bits (row i: bit i + filter_bit_offset), filter_table + filter_ids
-    (see bf_query_filtered_by), labels + query_labels (see bf_query_labeled)."""
+    (see bf_query_filtered_by), labels + query_labels (see bf_query_labeled).
+    Float32 / float16 / bfloat16 calls with Nq >= 256 and N >= 4096 pre-select on the matrix cores and
+    decide every hit exactly; the scan kernels answer the rest -- the same bits either way.
+    routed=True returns (lims, ids, dists, matrix_path, fell_back) instead: matrix_path 1 if the
+    (last) call chose the tile kernels, fell_back 1 if their candidate buffer overflowed and the scan
+    kernels answered after all (one host read)."""
     _need(base, name="base"), _need(query, base.dtype, "query")
     Nq, N = query.shape[0], base.shape[0]
     radii = range_radii(radius, Nq, base.device)
@@ -412,10 +417,25 @@ def bf_range_query(base, query, radius, measure=EUCLIDEAN, capacity=None, filter
     else:
         fn, tail = lib().ggnn_op_bf_range_query, ()
     lims = torch.empty(Nq + 1, dtype=torch.int64, device=base.device)
+    if routed:
+        import ctypes as C
+        fell, path = torch.zeros(1, dtype=torch.int32, device=base.device), C.c_int(0)
+        fn = lib().ggnn_op_bf_range_query_routed
+        tail = (_ptr(filter_bits),
+                _ptr(filter_table) if filter_ids is not None else None,
+                filter_table.shape[0] if filter_ids is not None else 0,
+                filter_table.shape[1] * 32 if filter_ids is not None else 0, _ptr(filter_ids),
+                _ptr(labels) if query_labels is not None else None,
+                labels.numel() if query_labels is not None else 0, _ptr(query_labels),
+                filter_bit_offset, _ptr(fell), C.byref(path))
 
     def call(cap, ids, dists):
         check(fn(_ptr(base), _dtype_code(base), N, base.shape[1], _ptr(query), Nq, _ptr(radii),
                  measure, cap, _ptr(lims), _ptr(ids), _ptr(dists), *tail, _stream()))
+
+    def where(res):
+        # (one host read of the device flag, after the call(s) it belongs to)
+        return res + (int(path.value), int(fell.item())) if routed else res
 
     if out is not None:
         ids, dists = out
@@ -424,7 +444,7 @@ def bf_range_query(base, query, radius, measure=EUCLIDEAN, capacity=None, filter
         if cap > min(ids.numel(), dists.numel()):
             raise ValueError("capacity exceeds the buffers of `out`")
         call(cap, ids, dists)
-        return lims, ids, dists
+        return where((lims, ids, dists))
     counted = capacity is None
     if counted:
         call(0, None, None)
@@ -436,7 +456,7 @@ def bf_range_query(base, query, radius, measure=EUCLIDEAN, capacity=None, filter
         call(capacity, ids, dists)
     elif not counted:
         call(0, None, None)
-    return lims, ids, dists
+    return where((lims, ids, dists))
 
 
 def label_index_build(labels):

@@ -287,7 +287,9 @@ ggnn_status ggnn_query_async_labeled(ggnn_t* h, const void* query, uint64_t Nq, 
  * The *_filtered, *_filtered_by and *_labeled forms take the filter of the ggnn_bf_query call of the
  * same name, with the same rules (label -1 / filter id -1: every row).  Label sets, label ranges and
  * label masks have no range form.  Single GPU, any state of the handle after ggnn_set_base, exactly
- * as ggnn_bf_query; always scan kernels (hook BF_RANGE_SLICES forces their slice count). */
+ * as ggnn_bf_query.  Float32 / float16 / bfloat16 calls with Nq >= 256 and N >= 4096 pre-select on the
+ * matrix cores and decide every hit exactly (same bits as the scan kernels, which answer every other
+ * call; hooks BF_RANGE_PATH, BF_RANGE_SLICES, BF_RANGE_CAND): ggnn_last_bf_range_matrix_path. */
 ggnn_status ggnn_bf_range_query(ggnn_t* h, const void* query, uint64_t Nq, uint32_t D,
                                 ggnn_dtype dtype, ggnn_location location, int gpu_id,
                                 const float* radii, ggnn_measure measure, uint64_t capacity,
@@ -543,6 +545,14 @@ ggnn_status ggnn_last_bf_query_rescanned(const ggnn_t* h, uint32_t* n_rescanned)
  * or a test tells which one ran.  out == NULL: GGNN_INVALID_ARGUMENT.
  * ggnn_last_bf_query_rescanned covers the filtered calls as well. */
 ggnn_status ggnn_last_bf_query_matrix_path(const ggnn_t* h, int* out);
+/* *out = 1 if the last ggnn_bf_range_query* call chose the tile kernels (matrix-core pre-selection,
+ * exact hits), else 0 (the scan kernels; also before the first call).  Results are the same bits. */
+ggnn_status ggnn_last_bf_range_matrix_path(const ggnn_t* h, int* out);
+/* tests: 1 if a range launch of this shape would take the tile kernels under the current hooks (host
+ * logic only; filter: 0 none, 1 bitset / table, 2 labels), and the LDS bytes of a tile workgroup */
+int ggnn_debug_bf_range_route(ggnn_dtype dtype, uint32_t D, uint32_t Nq, uint32_t N_base,
+                              uint64_t capacity, int filter, uint32_t filter_bit_offset,
+                              uint64_t* tile_lds_bytes);
 ggnn_status ggnn_set_collect_counters(ggnn_t* h, int enable);
 /* rows the last ggnn_query read for those evaluations (needs collect_counters): float rows
  * (4*D bytes each) and, with the pre-screen, 8-bit code rows (prescreen_code_dim(D) bytes each: a power of two up to 64, multiples of 64 above). */
@@ -671,7 +681,13 @@ void ggnn_set_log_level(int level);
  *                             count; test hook)
  *   BF_RANGE_SLICES     0     slices the range search cuts the base into per query (1..64): 0 = chosen
  *                             like the scan's, from the number of queries and rows (same results
- *                             for every count; test hook) */
+ *                             for every count; test hook); also the parts per query of the tile path
+ *   BF_RANGE_PATH       0     range search: 0 = tile kernels when dtype, D and filter allow and Nq >=
+ *                             256, N >= 4096 (count-only calls: Nq >= 1024, N >= 65536) | 1 = scan kernels always | 2 = tile kernels whenever
+ *                             dtype, D and filter allow, whatever Nq and N (same results; test hook)
+ *   BF_RANGE_CAND       0     entries of the tile path's candidate buffer: 0 = max(capacity, 32 Nq)
+ *                             plus one eighth, within 1 GiB; a call whose candidates do not fit is
+ *                             answered by the scan kernels (same results; test hook) */
 ggnn_status ggnn_set_hook(const char* name, int64_t value);
 /* back to environment / default */
 ggnn_status ggnn_reset_hook(const char* name);
@@ -845,6 +861,21 @@ ggnn_status ggnn_op_bf_range_query_labeled(const void* base, ggnn_dtype dtype, u
                                            float* dists, const int32_t* labels, uint64_t n_labels,
                                            const int32_t* query_labels, uint32_t filter_bit_offset,
                                            void* stream);
+/* ggnn_op_bf_range_query with the union of the filter arguments (at most one of filter_bits,
+ * filter_ids, query_labels non-NULL; the others as in the call of that name), and where it ran:
+ * *fell_back (DEVICE memory, may be NULL) receives 1 if the tile path's candidate buffer overflowed
+ * and the scan kernels answered, else 0; *matrix_path (HOST, may be NULL) receives 1 if the call
+ * chose the tile kernels (bf_range_mfma.hip), else 0. */
+ggnn_status ggnn_op_bf_range_query_routed(const void* base, ggnn_dtype dtype, uint32_t N_base,
+                                          uint32_t D, const void* query, uint32_t Nq,
+                                          const float* radii, ggnn_measure measure,
+                                          uint64_t capacity, uint64_t* lims, int32_t* ids,
+                                          float* dists, const uint32_t* filter_bits,
+                                          const uint32_t* filter_table, uint32_t num_filters,
+                                          uint64_t n_bits, const int32_t* filter_ids,
+                                          const int32_t* labels, uint64_t n_labels,
+                                          const int32_t* query_labels, uint32_t filter_bit_offset,
+                                          uint32_t* fell_back, int* matrix_path, void* stream);
 /* ggnn_op_bf_query_labeled through a label index (ggnn_label_index_build of the column, copied to
  * the device: keys[n_keys], offsets[n_keys + 1], rows[N_base]): every query reads only the rows of its
  * label.  Every output bit equals what ggnn_op_bf_query_labeled gives for the same base, labels and

@@ -2,10 +2,13 @@
 
     python scripts/bf_range_bench.py [--reps 5] [--out FILE.json]
 
-Shapes: 10k x 1M x 128 float32 and uint8, 100 x 1M x 128 float32.  Per shape, with the radius of every
+Shapes: 10k x 1M x 128 float32 and uint8, 100 x 1M x 128 float32, 10k x 1M x 960 float32 cosine, and a
+sweep around the routing minima of the tile path (Nq 256 / 1024, N 4096 / 65536).  Per shape, with the radius of every
 query at its 10th and at (about) its 1000th neighbour's distance: the count-only call (one distance pass) and
 the full call into an exactly sized buffer (two passes), in alternating runs with `bf_query` of the
-same shape under hook BF_SCAN = 1, k = 10 (the scan kernels: one pass that also keeps a list).  Prints
+same shape under hook BF_SCAN = 1, k = 10 (the scan kernels: one pass that also keeps a list) and on
+the tile kernels (`mfma_k10`).  The range calls run under BF_RANGE_PATH = 1 (the scan: `count_r*`,
+`full_r*`) and = 2 (tile pre-selection, exact hits: `tile_count_r*`, `tile_full_r*`).  Prints
 one JSON line per shape: median and min / max milliseconds over the repetitions, and results per query.
 No figure here is asserted anywhere: it is the measurement behind DESIGN.md 4.6."""
 import argparse
@@ -17,8 +20,9 @@ import torch
 
 from ggnn_amd import _lib, ops
 
-SHAPES = [("f32", 10_000, 1_000_000, 128), ("u8", 10_000, 1_000_000, 128),
-          ("f32", 100, 1_000_000, 128)]
+SHAPES = [("f32", 10_000, 1_000_000, 128, 0), ("u8", 10_000, 1_000_000, 128, 0),
+          ("f32", 100, 1_000_000, 128, 0), ("f32", 10_000, 1_000_000, 960, 1)] + \
+         [("f32", Nq, N, 128, 0) for Nq in (256, 1024) for N in (4096, 65536)]
 
 
 def timed(fn):
@@ -43,7 +47,7 @@ def main():
     args = ap.parse_args()
     lines = []
     for si in args.shapes:
-        dtype, Nq, N, D = SHAPES[si]
+        dtype, Nq, N, D, measure = SHAPES[si]
         g = torch.Generator(device="cuda").manual_seed(si)
         if dtype == "u8":
             base = torch.randint(0, 256, (N, D), dtype=torch.uint8, device="cuda", generator=g)
@@ -54,25 +58,34 @@ def main():
         # the radii: the exact 10th neighbour's distance, and the 10th neighbour's distance within the
         # first 1 % of the base -- on i.i.d. rows about the 1000th neighbour's of the whole base
         # (results_per_query below says what the radii really admit)
-        d10 = ops.bf_query(base, query, 10)[1]
-        d1000 = ops.bf_query(base[:N // 100], query, 10)[1]
+        d10 = ops.bf_query(base, query, 10, measure)[1]
+        d1000 = ops.bf_query(base[:N // 100], query, 10, measure)[1]
         radii = {10: d10[:, 9].contiguous(), 1000: d1000[:, 9].contiguous()}
-        totals = {k: int(ops.bf_range_query(base, query, r, capacity=0)[0][-1]) for k, r in radii.items()}
+        totals = {k: int(ops.bf_range_query(base, query, r, measure, capacity=0)[0][-1])
+                  for k, r in radii.items()}
         bufs = {k: (torch.empty(t, dtype=torch.int32, device="cuda"),
                     torch.empty(t, dtype=torch.float32, device="cuda")) for k, t in totals.items()}
-        ms = {"scan_k10": []}
+        ms = {"scan_k10": [], "mfma_k10": []}
+        paths = {"": 1} if dtype == "u8" else {"": 1, "tile_": 2}
         for k in radii:
-            ms[f"count_r{k}"], ms[f"full_r{k}"] = [], []
-        with _lib.hooks(BF_SCAN=1):
-            ops.bf_query(base, query, 10)                                        # warm-up
-            for _ in range(args.reps):                                           # alternating runs
-                ms["scan_k10"].append(timed(lambda: ops.bf_query(base, query, 10))[0])
-                for k, r in radii.items():
-                    ms[f"count_r{k}"].append(
-                        timed(lambda: ops.bf_range_query(base, query, r, capacity=0))[0])
-                    ms[f"full_r{k}"].append(
-                        timed(lambda: ops.bf_range_query(base, query, r, out=bufs[k]))[0])
-        line = {"dtype": dtype, "Nq": Nq, "N": N, "D": D, "reps": args.reps,
+            for pre in paths:
+                ms[f"{pre}count_r{k}"], ms[f"{pre}full_r{k}"] = [], []
+        for rep in range(-1, args.reps):                                         # -1: warm-up
+            got = {}
+            with _lib.hooks(BF_SCAN=1):
+                got["scan_k10"] = timed(lambda: ops.bf_query(base, query, 10, measure))[0]
+            got["mfma_k10"] = timed(lambda: ops.bf_query(base, query, 10, measure))[0]
+            for pre, path in paths.items():                                      # alternating runs
+                with _lib.hooks(BF_RANGE_PATH=path):
+                    for k, r in radii.items():
+                        got[f"{pre}count_r{k}"] = timed(
+                            lambda: ops.bf_range_query(base, query, r, measure, capacity=0))[0]
+                        got[f"{pre}full_r{k}"] = timed(
+                            lambda: ops.bf_range_query(base, query, r, measure, out=bufs[k]))[0]
+            if rep >= 0:
+                for k, v in got.items():
+                    ms[k].append(v)
+        line = {"dtype": dtype, "Nq": Nq, "N": N, "D": D, "measure": measure, "reps": args.reps,
                 "results_per_query": {f"r{k}": round(t / Nq, 2) for k, t in totals.items()},
                 **{k: stats(v) for k, v in ms.items()}}
         print(json.dumps(line), flush=True)
