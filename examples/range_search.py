@@ -55,3 +55,10 @@ b = torch.from_numpy(base).cuda()
 lims, _, _ = ops.bf_range_query(b, b[:2000].contiguous(), 100.0, capacity=0)
 print("rows within squared distance 100 of a row: median",
       int(torch.diff(lims).median()), "max", int(torch.diff(lims).max()))
+
+# uint8 rows (SIFT-like): the same call; batches from 256 queries x 65536 rows under squared L2 are
+# decided on the integer matrix cores (last_bf_range_matrix_path() == 2), smaller ones by the scan
+g8 = ggnn.GGNN()
+g8.set_base(np.random.default_rng(1).integers(0, 256, (4096, 128)).astype(np.uint8))
+lims8, _, _ = g8.bf_range_query(np.zeros((4, 128), np.uint8), 128 * 100.0 ** 2, sort=False)
+print("uint8 rows within 100 per dimension of the origin:", np.diff(lims8.numpy()))

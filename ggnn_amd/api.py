@@ -1303,8 +1303,9 @@ class GGNN:
         return int(n.value)
 
     def last_bf_range_matrix_path(self):
-        """1 if the last bf_range_query* call chose the matrix-core tile kernels (pre-selection,
-        every hit decided exactly), else 0 (the scan kernels); the same bits on either path"""
+        """1 if the last bf_range_query* call chose the float tile kernels (matrix-core pre-selection,
+        every hit decided exactly), 2 if it chose the integer tile kernels of uint8 / int8 rows
+        (squared L2, exact verdicts), else 0 (the scan kernels); the same bits on every path"""
         n = C.c_int()
         self._check(lib().ggnn_last_bf_range_matrix_path(self._h, C.byref(n)))
         return int(n.value)

@@ -209,6 +209,9 @@ void bf_slice_rows(uint32_t N_base, uint32_t& slices, uint32_t& rows_per_slice);
 // dtype / D / filter of a launch suit the tile kernels, and (hook BF_RANGE_PATH = 0) Nq and N_base
 // reach their minima; BF_RANGE_PATH = 1 says no to everything, 2 waives the minima
 void launch_bf_range_query_mfma(const BfRangeLaunch& a, hipStream_t stream);
+// bf_range_i8.hip: uint8 / int8 rows under squared L2 on the integer matrix cores, exact verdicts
+// (a launch that bf_range_i8_supported admits)
+void launch_bf_range_query_i8(const BfRangeLaunch& a, hipStream_t stream);
 // The scan passes (count, prefix, fill) of a validated launch.  gate (device, or null: the plain scan):
 // with *gate == 0 every wave of the count and fill passes returns before it touches the base, and
 // what the prefix pass then writes to a.lims means nothing -- the caller gives it lims of its own.

@@ -11,8 +11,9 @@
 //           offset + popcount(hits below j), so a query's rows stand in ascending id without a sort.
 //           A wave leaves at once when lims[Nq] exceeds the capacity: ids / dists stay untouched.
 // Count and fill are one kernel body with one `if constexpr`: they cannot disagree.
-// Calls that suit the tile kernels go to bf_range_mfma.hip (launch_bf_range_query routes); that path
-// enqueues these passes behind itself with a gate word, as its fallback (launch_bf_range_scan).
+// Calls that suit the tile kernels go to bf_range_mfma.hip (float rows) or bf_range_i8.hip (byte rows,
+// squared L2) -- launch_bf_range_query routes; those paths enqueue these passes behind themselves with
+// a gate word, as their fallback (launch_bf_range_scan).
 #include <algorithm>
 
 #include "bf_common.hpp"
@@ -255,6 +256,12 @@ void launch_bf_range_query(const BfRangeLaunch& a_in, hipStream_t stream)
     if (a.matrix_path)
       *a.matrix_path = 1;
     launch_bf_range_query_mfma(a, stream);
+  }
+  // byte rows under squared L2: exact verdicts from the integer matrix cores (bf_range_i8.hip)
+  else if (bf_range_i8_supported(a)) {
+    if (a.matrix_path)
+      *a.matrix_path = 2;
+    launch_bf_range_query_i8(a, stream);
   }
   else
     launch_bf_range_scan(a, nullptr, stream);

@@ -291,7 +291,9 @@ void launch_bf_query(const BfLaunch& a, hipStream_t stream);
 // Filters: none, a bitset (filter_bits), a filter table (filter_table.ids) or one label per query
 // (filter_table.query_labels) -- BfLaunch's rules.
 // Float rows in large batches are pre-selected on the matrix cores and every hit decided exactly
-// (bf_range_mfma.hip, bf_range_mfma_supported); the scan kernels answer the rest.  Same bits.
+// (bf_range_mfma.hip, bf_range_mfma_supported); uint8 / int8 rows under squared L2 in large batches
+// are decided on the integer matrix cores (bf_range_i8.hip, bf_range_i8_supported); the scan kernels
+// answer the rest.  Same bits.
 struct BfRangeLaunch {
   const void* base;
   const void* query;
@@ -307,7 +309,9 @@ struct BfRangeLaunch {
   uint32_t filter_bit_offset{0};
   FilterTable filter_table{};
   // tile path (bf_range_mfma.hip): 1 if the candidate budget overflowed and the scan answered the
-  // call, else 0 (device, optional); *matrix_path (host, optional) = the tile path was chosen
+  // call, else 0 (device, optional); *matrix_path (host, optional): 1 = the float tile path was chosen,
+  // 2 = the integer tile kernels (bf_range_i8.hip; fell_back: a radius >= 2^24 at D > 258 sent the
+  // call to the scan), 0 = the scan
   uint32_t* fell_back{nullptr};
   int* matrix_path{nullptr};
 };
@@ -317,6 +321,11 @@ void launch_bf_range_query(const BfRangeLaunch& a, hipStream_t stream);
 // dynamic LDS of a tile workgroup (fm: 0 none, 1 bitset / table, 2 labels)
 bool bf_range_mfma_supported(const BfRangeLaunch& a);
 size_t bf_range_tile_lds_bytes(uint32_t D, int fm);
+// the same pair for the integer tile kernels (bf_range_i8.hip): uint8 / int8, squared L2, D % 16 == 0,
+// D <= 4096, a bitset's bit offset a multiple of 32; hooks BF_RANGE_PATH (1: no) and BF_RANGE_I8
+// (0: Nq >= 256 and N_base >= 65536, 1: no, 2: minima waived)
+bool bf_range_i8_supported(const BfRangeLaunch& a);
+size_t bf_range_i8_lds_bytes(uint32_t D, int fm);
 
 // Label index (label_index.hip): the label column in CSR form over the global base ids -- keys[n_keys]
 // the distinct labels ascending, offsets[n_keys + 1] uint32 positions (offsets[0] = 0, offsets[n_keys]

@@ -288,8 +288,11 @@ ggnn_status ggnn_query_async_labeled(ggnn_t* h, const void* query, uint64_t Nq, 
  * same name, with the same rules (label -1 / filter id -1: every row).  Label sets, label ranges and
  * label masks have no range form.  Single GPU, any state of the handle after ggnn_set_base, exactly
  * as ggnn_bf_query.  Float32 / float16 / bfloat16 calls with Nq >= 256 and N >= 4096 pre-select on the
- * matrix cores and decide every hit exactly (same bits as the scan kernels, which answer every other
- * call; hooks BF_RANGE_PATH, BF_RANGE_SLICES, BF_RANGE_CAND): ggnn_last_bf_range_matrix_path. */
+ * matrix cores and decide every hit exactly; uint8 / int8 calls with Nq >= 256 and N >= 65536 under
+ * squared L2 (D a multiple of 16) take their verdicts from the integer matrix cores, where a pair's distance is an
+ * exact integer (a radius >= 2^24 at D > 258 sends the whole call to the scan kernels).  Same bits as
+ * the scan kernels, which answer every other call -- byte rows under cosine among them (hooks
+ * BF_RANGE_PATH, BF_RANGE_I8, BF_RANGE_SLICES, BF_RANGE_CAND): ggnn_last_bf_range_matrix_path. */
 ggnn_status ggnn_bf_range_query(ggnn_t* h, const void* query, uint64_t Nq, uint32_t D,
                                 ggnn_dtype dtype, ggnn_location location, int gpu_id,
                                 const float* radii, ggnn_measure measure, uint64_t capacity,
@@ -545,14 +548,19 @@ ggnn_status ggnn_last_bf_query_rescanned(const ggnn_t* h, uint32_t* n_rescanned)
  * or a test tells which one ran.  out == NULL: GGNN_INVALID_ARGUMENT.
  * ggnn_last_bf_query_rescanned covers the filtered calls as well. */
 ggnn_status ggnn_last_bf_query_matrix_path(const ggnn_t* h, int* out);
-/* *out = 1 if the last ggnn_bf_range_query* call chose the tile kernels (matrix-core pre-selection,
- * exact hits), else 0 (the scan kernels; also before the first call).  Results are the same bits. */
+/* *out = 1 if the last ggnn_bf_range_query* call chose the float tile kernels (matrix-core
+ * pre-selection, exact hits), 2 if it chose the integer tile kernels of uint8 / int8 rows, else 0 (the
+ * scan kernels; also before the first call).  Results are the same bits. */
 ggnn_status ggnn_last_bf_range_matrix_path(const ggnn_t* h, int* out);
 /* tests: 1 if a range launch of this shape would take the tile kernels under the current hooks (host
  * logic only; filter: 0 none, 1 bitset / table, 2 labels), and the LDS bytes of a tile workgroup */
 int ggnn_debug_bf_range_route(ggnn_dtype dtype, uint32_t D, uint32_t Nq, uint32_t N_base,
                               uint64_t capacity, int filter, uint32_t filter_bit_offset,
                               uint64_t* tile_lds_bytes);
+/* tests: the same for the integer tile kernels of uint8 / int8 rows (hooks BF_RANGE_PATH, BF_RANGE_I8) */
+int ggnn_debug_bf_range_i8_route(ggnn_dtype dtype, ggnn_measure measure, uint32_t D, uint32_t Nq,
+                                 uint32_t N_base, uint64_t capacity, int filter,
+                                 uint32_t filter_bit_offset, uint64_t* tile_lds_bytes);
 ggnn_status ggnn_set_collect_counters(ggnn_t* h, int enable);
 /* rows the last ggnn_query read for those evaluations (needs collect_counters): float rows
  * (4*D bytes each) and, with the pre-screen, 8-bit code rows (prescreen_code_dim(D) bytes each: a power of two up to 64, multiples of 64 above). */
@@ -687,7 +695,12 @@ void ggnn_set_log_level(int level);
  *                             dtype, D and filter allow, whatever Nq and N (same results; test hook)
  *   BF_RANGE_CAND       0     entries of the tile path's candidate buffer: 0 = max(capacity, 32 Nq)
  *                             plus one eighth, within 1 GiB; a call whose candidates do not fit is
- *                             answered by the scan kernels (same results; test hook) */
+ *                             answered by the scan kernels (same results; test hook)
+ *   BF_RANGE_I8         0     range search on uint8 / int8 rows: 0 = integer tile kernels when the
+ *                             measure is squared L2, D % 16 == 0, D <= 4096, a bitset's bit offset is a
+ *                             multiple of 32 and Nq >= 256, N >= 65536 | 1 = never | 2 = whenever those
+ *                             conditions hold, whatever Nq and N; BF_RANGE_PATH = 1 still means the scan
+ *                             kernels always (same results; test hook) */
 ggnn_status ggnn_set_hook(const char* name, int64_t value);
 /* back to environment / default */
 ggnn_status ggnn_reset_hook(const char* name);
@@ -834,8 +847,8 @@ ggnn_status ggnn_op_bf_query_labeled(const void* base, ggnn_dtype dtype, uint32_
  * written; ids / dists only if lims[Nq] <= capacity (they may be null with capacity 0), rows in
  * ascending id whatever the number of slices.  A Euclidean radius is in SQUARED units.  A NaN radius
  * admits nothing here (the handle refuses it).  The filter arguments are those of
- * ggnn_op_bf_query_filtered / _filtered_by / _labeled; any filter_bit_offset (there is no matrix-core
- * path), 8-bit rows need D % 16 == 0, labels at most 2^30 rows. */
+ * ggnn_op_bf_query_filtered / _filtered_by / _labeled; any filter_bit_offset (a bitset whose offset is
+ * no multiple of 32 keeps the scan kernels), 8-bit rows need D % 16 == 0, labels at most 2^30 rows. */
 ggnn_status ggnn_op_bf_range_query(const void* base, ggnn_dtype dtype, uint32_t N_base, uint32_t D,
                                    const void* query, uint32_t Nq, const float* radii,
                                    ggnn_measure measure, uint64_t capacity, uint64_t* lims,
@@ -864,8 +877,9 @@ ggnn_status ggnn_op_bf_range_query_labeled(const void* base, ggnn_dtype dtype, u
 /* ggnn_op_bf_range_query with the union of the filter arguments (at most one of filter_bits,
  * filter_ids, query_labels non-NULL; the others as in the call of that name), and where it ran:
  * *fell_back (DEVICE memory, may be NULL) receives 1 if the tile path's candidate buffer overflowed
- * and the scan kernels answered, else 0; *matrix_path (HOST, may be NULL) receives 1 if the call
- * chose the tile kernels (bf_range_mfma.hip), else 0. */
+ * (float rows) or a radius >= 2^24 met D > 258 (byte rows) and the scan kernels answered, else 0;
+ * *matrix_path (HOST, may be NULL) receives 1 if the call chose the float tile kernels
+ * (bf_range_mfma.hip), 2 if it chose the integer tile kernels (bf_range_i8.hip), else 0. */
 ggnn_status ggnn_op_bf_range_query_routed(const void* base, ggnn_dtype dtype, uint32_t N_base,
                                           uint32_t D, const void* query, uint32_t Nq,
                                           const float* radii, ggnn_measure measure,

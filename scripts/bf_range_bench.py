@@ -1,6 +1,6 @@
 """Times the exact range search beside the K-best scan of the same shape, on one GPU:
 
-    python scripts/bf_range_bench.py [--reps 5] [--out FILE.json]
+    python scripts/bf_range_bench.py [--reps 5] [--out FILE.json] [--dtype uint8|int8]
 
 Shapes: 10k x 1M x 128 float32 and uint8, 100 x 1M x 128 float32, 10k x 1M x 960 float32 cosine, and a
 sweep around the routing minima of the tile path (Nq 256 / 1024, N 4096 / 65536).  Per shape, with the radius of every
@@ -9,7 +9,10 @@ the full call into an exactly sized buffer (two passes), in alternating runs wit
 same shape under hook BF_SCAN = 1, k = 10 (the scan kernels: one pass that also keeps a list) and on
 the tile kernels (`mfma_k10`).  The range calls run under BF_RANGE_PATH = 1 (the scan: `count_r*`,
 `full_r*`) and = 2 (tile pre-selection, exact hits: `tile_count_r*`, `tile_full_r*`).  Prints
-one JSON line per shape: median and min / max milliseconds over the repetitions, and results per query.
+Byte rows alternate hook BF_RANGE_I8 = 1 (the scan) and = 2 (the integer tile kernels, exact verdicts)
+instead.  --dtype uint8|int8 runs the byte-row sweep: 10k x 1M x 128 and the four shapes around the
+routing minima, integer data over the full value range; the radii are pair distances, so integers.
+Prints one JSON line per shape: median and min / max milliseconds over the repetitions, and results per query.
 No figure here is asserted anywhere: it is the measurement behind DESIGN.md 4.6."""
 import argparse
 import json
@@ -23,6 +26,12 @@ from ggnn_amd import _lib, ops
 SHAPES = [("f32", 10_000, 1_000_000, 128, 0), ("u8", 10_000, 1_000_000, 128, 0),
           ("f32", 100, 1_000_000, 128, 0), ("f32", 10_000, 1_000_000, 960, 1)] + \
          [("f32", Nq, N, 128, 0) for Nq in (256, 1024) for N in (4096, 65536)]
+BYTE = {"uint8": "u8", "int8": "i8"}
+
+
+def byte_shapes(t):
+    return [(t, 10_000, 1_000_000, 128, 0)] + [(t, Nq, N, 128, 0) for Nq in (256, 1024)
+                                                for N in (4096, 65536)]
 
 
 def timed(fn):
@@ -43,15 +52,18 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--out")
-    ap.add_argument("--shapes", type=int, nargs="*", default=list(range(len(SHAPES))))
+    ap.add_argument("--shapes", type=int, nargs="*")
+    ap.add_argument("--dtype", choices=sorted(BYTE))
     args = ap.parse_args()
+    shapes = byte_shapes(BYTE[args.dtype]) if args.dtype else SHAPES
     lines = []
-    for si in args.shapes:
-        dtype, Nq, N, D, measure = SHAPES[si]
+    for si in (args.shapes if args.shapes is not None else range(len(shapes))):
+        dtype, Nq, N, D, measure = shapes[si]
         g = torch.Generator(device="cuda").manual_seed(si)
-        if dtype == "u8":
-            base = torch.randint(0, 256, (N, D), dtype=torch.uint8, device="cuda", generator=g)
-            query = torch.randint(0, 256, (Nq, D), dtype=torch.uint8, device="cuda", generator=g)
+        if dtype in ("u8", "i8"):
+            lo, tt = (0, torch.uint8) if dtype == "u8" else (-128, torch.int8)
+            base = torch.randint(lo, lo + 256, (N, D), dtype=tt, device="cuda", generator=g)
+            query = torch.randint(lo, lo + 256, (Nq, D), dtype=tt, device="cuda", generator=g)
         else:
             base = torch.rand((N, D), device="cuda", generator=g)
             query = torch.rand((Nq, D), device="cuda", generator=g)
@@ -66,7 +78,8 @@ def main():
         bufs = {k: (torch.empty(t, dtype=torch.int32, device="cuda"),
                     torch.empty(t, dtype=torch.float32, device="cuda")) for k, t in totals.items()}
         ms = {"scan_k10": [], "mfma_k10": []}
-        paths = {"": 1} if dtype == "u8" else {"": 1, "tile_": 2}
+        hook = "BF_RANGE_I8" if dtype in ("u8", "i8") and measure == 0 else "BF_RANGE_PATH"
+        paths = {"": 1, "tile_": 2}
         for k in radii:
             for pre in paths:
                 ms[f"{pre}count_r{k}"], ms[f"{pre}full_r{k}"] = [], []
@@ -76,7 +89,7 @@ def main():
                 got["scan_k10"] = timed(lambda: ops.bf_query(base, query, 10, measure))[0]
             got["mfma_k10"] = timed(lambda: ops.bf_query(base, query, 10, measure))[0]
             for pre, path in paths.items():                                      # alternating runs
-                with _lib.hooks(BF_RANGE_PATH=path):
+                with _lib.hooks(**{hook: path}):
                     for k, r in radii.items():
                         got[f"{pre}count_r{k}"] = timed(
                             lambda: ops.bf_range_query(base, query, r, measure, capacity=0))[0]
