@@ -339,6 +339,7 @@ void launch_bf_query_labelset(const BfLaunch& a, hipStream_t stream);  // bf_que
 void launch_bf_query_labelrange(const BfLaunch& a, hipStream_t stream);  // bf_query_labelrange.hip
 void launch_bf_query_labelmask(const BfLaunch& a, hipStream_t stream);  // bf_query_labelmask.hip
 void launch_bf_query_mfma(const BfLaunch& a, hipStream_t stream);
+void launch_bf_query_f16(const BfLaunch& a, hipStream_t stream);  // bf_f16.hip
 
 // scan of all queries (qlist == nullptr) or of the subset qlist[0, *qcount); slices > 1 needs
 // tmp_ids / tmp_dists of [slices x Nq x K] entries
@@ -462,6 +463,13 @@ void launch_bf_query(const BfLaunch& a_in, hipStream_t stream)
     force_scan = force_scan || bf_mfma_uses_i8(a) || a.dtype == GGNN_I8 ||
                  (bits && a.filter_bit_offset % 32 != 0) ||
                  static_cast<uint64_t>(a.filter_bit_offset) + a.N_base > 0xffffffffull;
+  }
+  // float16 / bfloat16 rows, squared L2, no filter: the 16-bit matrix cores (bf_f16.hip; hook BF_F16)
+  if (!force_scan && bf_f16_supported(a)) {
+    launch_bf_query_f16(a, stream);
+    if (a.matrix_path)
+      *a.matrix_path = 2;
+    return;
   }
   if (!force_scan && bf_mfma_supported(a)) {
     launch_bf_query_mfma(a, stream);

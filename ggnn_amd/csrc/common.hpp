@@ -270,8 +270,9 @@ struct BfLaunch {
   uint32_t filter_bit_offset{0};
   // per-query filters: filter_bits is then a table (see FilterTable)
   FilterTable filter_table{};
-  // optional (HOST): 1 if the launch ran the tile kernels of bf_mfma.hip, 0 if it ran the scan --
-  // decided on the host before anything is enqueued; results are bit-identical either way
+  // optional (HOST): 1 if the launch ran the tile kernels of bf_mfma.hip, 2 if it ran the 16-bit tile
+  // kernels of bf_f16.hip, 0 if it ran the scan -- decided on the host before anything is enqueued;
+  // results are bit-identical either way
   int* matrix_path{nullptr};
   // label-set filters (labels != nullptr: see LabelSetSpec); always the scan
   LabelSetSpec label_sets{};
@@ -281,6 +282,15 @@ struct BfLaunch {
   LabelMaskSpec label_masks{};
 };
 void launch_bf_query(const BfLaunch& a, hipStream_t stream);
+// host side of the 16-bit tile path (bf_f16.hip): float16 / bfloat16, squared L2, no filter of any kind,
+// D % 8 == 0, D <= 4096, k + 8 <= 120 and the lists of a workgroup within its LDS (k <= 110 at D <= 32);
+// hook BF_F16 (0: bfloat16 with Nq >= 10000, N_base >= 1000000, D > 64 and lists short enough for two
+// sets per wave, 1: no, 2: type, minima and kernel variant waived).  The ratio sink (scripts/bf_f16_cm.py
+// only; one process-wide pointer, not for concurrent callers): a device word that receives, as float bits,
+// the largest |d_e - d_dir| / ((2D+8) 2^-24 (|q|^2 + |x|^2)) over the candidates of the launches that
+// follow, or null
+bool bf_f16_supported(const BfLaunch& a);
+void bf_f16_set_ratio_sink(uint32_t* device_word);
 
 // Exact range search (bf_range.hip): every base row i that the filter admits and whose distance to
 // query n -- the float32 value launch_bf_query's scan kernel reports for the pair: squared L2 or

@@ -858,7 +858,10 @@ def pack_filters(masks):
 
 
 def bf_query(base, query, k_query, measure=EUCLIDEAN, rescanned=False):
-    """rescanned=True: also return how many queries the matrix-core path handed to the scan"""
+    """rescanned=True: also return how many queries the matrix-core path handed to the scan.
+    (Which path a launch takes -- 0 the scan, 1 the float32-staged tiles, 2 the 16-bit tiles of float16 /
+    bfloat16 rows under squared L2 -- is reported by GGNN.last_bf_query_matrix_path() and, for a
+    shape, by ggnn_debug_bf_f16_route.)"""
     _need(base, name="base"), _need(query, base.dtype, "query")
     Nq = query.shape[0]
     ids = torch.empty((Nq, k_query), dtype=torch.int32, device=base.device)

@@ -543,7 +543,8 @@ ggnn_status ggnn_last_query_parts(const ggnn_t* h, uint32_t* parts);
  * matrix-core pre-selection could not be certified exact (tracing; results are exact either way) */
 ggnn_status ggnn_last_bf_query_rescanned(const ggnn_t* h, uint32_t* n_rescanned);
 /* *out = 1 if the last ggnn_bf_query* call of the handle (filtered or not) ran the matrix-core
- * tile kernel on every shard, else 0 (the scan kernels; also before the first call and after a
+ * tile kernel on every shard, 2 if it ran the 16-bit tile kernels (float16 / bfloat16 rows, squared
+ * L2, no filter: bf_f16.hip, hook BF_F16), else 0 (the scan kernels; also before the first call and after a
  * call without queries).  Results are bit-identical on either path: this getter is how a caller
  * or a test tells which one ran.  out == NULL: GGNN_INVALID_ARGUMENT.
  * ggnn_last_bf_query_rescanned covers the filtered calls as well. */
@@ -561,6 +562,15 @@ int ggnn_debug_bf_range_route(ggnn_dtype dtype, uint32_t D, uint32_t Nq, uint32_
 int ggnn_debug_bf_range_i8_route(ggnn_dtype dtype, ggnn_measure measure, uint32_t D, uint32_t Nq,
                                  uint32_t N_base, uint64_t capacity, int filter,
                                  uint32_t filter_bit_offset, uint64_t* tile_lds_bytes);
+/* tests: 1 if an unfiltered (filtered = 0) or filtered bf_query launch of this shape would take the
+ * 16-bit tile kernels (bf_f16.hip) under the current hooks (BF_F16, BF_SCAN); host logic only */
+int ggnn_debug_bf_f16_route(ggnn_dtype dtype, ggnn_measure measure, uint32_t D, uint32_t Nq,
+                            uint32_t N_base, uint32_t k_query, int filtered);
+/* scripts/bf_f16_cm.py: a DEVICE word that the 16-bit tile path's re-rank raises (atomic max of float
+ * bits) to the largest |d_e - d_dir| / ((2D+8) 2^-24 (|q|^2 + |x|^2)) over the candidates of the
+ * launches that follow -- the evidence behind the certificate's model constant; NULL:
+ * off.  One process-wide pointer: set and clear it with no bf_query of another thread in flight */
+void ggnn_debug_bf_f16_ratio_sink(uint32_t* device_word);
 ggnn_status ggnn_set_collect_counters(ggnn_t* h, int enable);
 /* rows the last ggnn_query read for those evaluations (needs collect_counters): float rows
  * (4*D bytes each) and, with the pre-screen, 8-bit code rows (prescreen_code_dim(D) bytes each: a power of two up to 64, multiples of 64 above). */
@@ -700,7 +710,16 @@ void ggnn_set_log_level(int level);
  *                             measure is squared L2, D % 16 == 0, D <= 4096, a bitset's bit offset is a
  *                             multiple of 32 and Nq >= 256, N >= 65536 | 1 = never | 2 = whenever those
  *                             conditions hold, whatever Nq and N; BF_RANGE_PATH = 1 still means the scan
- *                             kernels always (same results; test hook) */
+ *                             kernels always (same results; test hook)
+ *   BF_F16              0     bf_query on float16 / bfloat16 rows: 0 = 16-bit tile kernels (bf_f16.hip)
+ *                             when the measure is squared L2, the call has no filter of any kind,
+ *                             D % 8 == 0, D <= 4096, k + 8 <= 120 (k <= 110 at D <= 32: the lists of
+ *                             a workgroup must fit its LDS) and the rows are bfloat16 with
+ *                             Nq >= 10000, N >= 1000000, D > 64 and k <= 13: the kernel
+ *                             variants that measured faster; float16: never | 1 = never
+ *                             (the float32-staged tile kernels) | 2 = whenever the conditions before
+ *                             "and the rows" hold; BF_SCAN = 1 still means the scan kernels always
+ *                             (same results; test hook) */
 ggnn_status ggnn_set_hook(const char* name, int64_t value);
 /* back to environment / default */
 ggnn_status ggnn_reset_hook(const char* name);
