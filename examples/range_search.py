@@ -62,3 +62,11 @@ g8 = ggnn.GGNN()
 g8.set_base(np.random.default_rng(1).integers(0, 256, (4096, 128)).astype(np.uint8))
 lims8, _, _ = g8.bf_range_query(np.zeros((4, 128), np.uint8), 128 * 100.0 ** 2, sort=False)
 print("uint8 rows within 100 per dimension of the origin:", np.diff(lims8.numpy()))
+
+# bfloat16 rows: the same call; batches from 10 000 queries x 1M rows under squared L2 are pre-selected
+# on the 16-bit matrix cores (last_bf_range_matrix_path() == 3), smaller ones as float32 rows are
+g16 = ggnn.GGNN()
+g16.set_base_reference(b[:4096].to(torch.bfloat16))
+g16.set_return_results_on_gpu(True)
+lims16, _, _ = g16.bf_range_query(b[:4].to(torch.bfloat16), 100.0, sort=False)
+print("bfloat16 rows within squared distance 100:", torch.diff(lims16).tolist())

@@ -212,6 +212,30 @@ void launch_bf_range_query_mfma(const BfRangeLaunch& a, hipStream_t stream);
 // bf_range_i8.hip: uint8 / int8 rows under squared L2 on the integer matrix cores, exact verdicts
 // (a launch that bf_range_i8_supported admits)
 void launch_bf_range_query_i8(const BfRangeLaunch& a, hipStream_t stream);
+// bf_range_f16.hip: float16 / bfloat16 rows under squared L2 on the 16-bit matrix cores, tile
+// pre-selection and exact hits (a launch that bf_range_f16_supported admits)
+void launch_bf_range_query_f16(const BfRangeLaunch& a, hipStream_t stream);
+// bf_range_mfma.hip's last passes, shared with bf_range_f16.hip.  Compaction: every (query, part) copies
+// its hits (candidates with distance <= radius), in candidate order, to ids / dists -- unless the
+// candidates overflowed their budget or the total exceeds the capacity.  take_lims: lims[0, n) = from[0, n)
+// if *flag != 0 (the scan passes answered the call)
+struct BfRangeCompactArgs {
+  const float* radii;
+  const uint32_t* cand_counts;
+  const uint64_t* cand_offsets;
+  const uint64_t* cand_lims;
+  const int32_t* cand_ids;
+  const float* cand_dists;
+  const uint64_t* hit_offsets;  // [Nq x parts] exclusive
+  const uint64_t* lims;         // [Nq + 1]
+  int32_t* ids;
+  float* dists;
+  uint64_t budget, capacity;
+  uint32_t Nq, parts;
+};
+void launch_bf_range_compact(const BfRangeCompactArgs& cp, hipStream_t stream);
+void launch_bf_range_take_lims(const uint32_t* flag, const uint64_t* from, uint32_t n, uint64_t* lims,
+                               hipStream_t stream);
 // The scan passes (count, prefix, fill) of a validated launch.  gate (device, or null: the plain scan):
 // with *gate == 0 every wave of the count and fill passes returns before it touches the base, and
 // what the prefix pass then writes to a.lims means nothing -- the caller gives it lims of its own.

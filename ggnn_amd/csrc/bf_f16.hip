@@ -151,6 +151,13 @@ __global__ void __launch_bounds__(256) bf_f16_pack_kernel(const uint16_t* query,
   }
 }
 
+constexpr int bf_f16_stage_tiles(int NM, bool CH)
+{
+  return CH ? 2 : 16 / NM;
+}
+
+// (bf_range_f16.hip takes the shared device code above only: GGNN_BF_F16_SHARED_ONLY)
+#ifndef GGNN_BF_F16_SHARED_ONLY
 // ---- tile kernel ------------------------------------------------------------------------------------
 struct BfF16Args {
   const void* base;
@@ -167,10 +174,6 @@ struct BfF16Args {
   uint64_t total_units;      // query blocks * units_per_q
 };
 
-constexpr int bf_f16_stage_tiles(int NM, bool CH)
-{
-  return CH ? 2 : 16 / NM;
-}
 // dynamic LDS of a tile workgroup: two stages, norms and thresholds of its queries, the lists, and 128
 // words that bf_insert_hits may read (never use) past the last list
 constexpr size_t bf_f16_lds_bytes(int NM, int NS, bool CH, uint32_t KP)
@@ -731,5 +734,6 @@ void launch_bf_query_f16(const BfLaunch& a, hipStream_t stream)
   else
     throw Error(GGNN_UNSUPPORTED, "the 16-bit tile kernels take float16 / bfloat16 rows");
 }
+#endif  // GGNN_BF_F16_SHARED_ONLY
 
 }  // namespace ggnn_amd

@@ -11,9 +11,10 @@
 //           offset + popcount(hits below j), so a query's rows stand in ascending id without a sort.
 //           A wave leaves at once when lims[Nq] exceeds the capacity: ids / dists stay untouched.
 // Count and fill are one kernel body with one `if constexpr`: they cannot disagree.
-// Calls that suit the tile kernels go to bf_range_mfma.hip (float rows) or bf_range_i8.hip (byte rows,
-// squared L2) -- launch_bf_range_query routes; those paths enqueue these passes behind themselves with
-// a gate word, as their fallback (launch_bf_range_scan).
+// Calls that suit the tile kernels go to bf_range_mfma.hip (float rows), bf_range_f16.hip (16-bit rows,
+// squared L2, large batches) or bf_range_i8.hip (byte rows, squared L2) -- launch_bf_range_query
+// routes; those paths enqueue these passes behind themselves with a gate word, as their fallback
+// (launch_bf_range_scan).
 #include <algorithm>
 
 #include "bf_common.hpp"
@@ -251,8 +252,15 @@ void launch_bf_range_query(const BfRangeLaunch& a_in, hipStream_t stream)
   if (consts.p)
     a.filter_table.consts = static_cast<const uint32_t*>(consts.p);
 
+  // float16 / bfloat16 rows under squared L2: tile pre-selection on the 16-bit matrix cores
+  // (bf_range_f16.hip; hook BF_RANGE_F16)
+  if (bf_range_f16_supported(a)) {
+    if (a.matrix_path)
+      *a.matrix_path = 3;
+    launch_bf_range_query_f16(a, stream);
+  }
   // tile pre-selection on the matrix cores with exact hits (bf_range_mfma.hip), or the scan
-  if (bf_range_mfma_supported(a)) {
+  else if (bf_range_mfma_supported(a)) {
     if (a.matrix_path)
       *a.matrix_path = 1;
     launch_bf_range_query_mfma(a, stream);

@@ -61,6 +61,7 @@
 #include <algorithm>
 
 #include "bf_common.hpp"
+#include "bf_thread_filter.hpp"
 #include "hooks.hpp"
 
 namespace ggnn_amd {
@@ -241,21 +242,10 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2)))
     if constexpr (FM == kBfLabels)
       filt_l[tid] = static_cast<uint32_t>(my_valid ? a.filter_table.query_labels[my_q] : -1);
   }
-  // kBfBits: the bitset row of this thread's query, chosen as wave_filter_bits() chooses it (that
-  // helper takes a wave-uniform query; here a thread stages the words of one query): the call's bitset
-  // without filter ids, else the table row of an id in [0, num_filters) -- an UNSIGNED compare --, the
-  // all-ones row for -1 and the all-zero row for everything else
+  // kBfBits: the bitset row of this thread's query (padding queries have no hits anyway)
   [[maybe_unused]] const uint32_t* frow = nullptr;
-  if constexpr (FM == kBfBits) {
-    const FilterTable& t = a.filter_table;
-    frow = a.filter_bits;
-    if (t.ids) {
-      const int32_t f = t.ids[min(my_q, a.Nq - 1)];  // (padding queries have no hits anyway)
-      frow = static_cast<uint32_t>(f) < t.num_filters
-                 ? a.filter_bits + static_cast<size_t>(static_cast<uint32_t>(f)) * t.words
-                 : t.consts + (f == -1 ? 0u : t.words);
-    }
-  }
+  if constexpr (FM == kBfBits)
+    frow = bf_thread_filter_row(a.filter_bits, a.filter_table, my_q, a.Nq);
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
 

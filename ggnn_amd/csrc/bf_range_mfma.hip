@@ -366,21 +366,6 @@ __global__ void __launch_bounds__(kWave) bf_range_exact_kernel(const BfRangeExac
     a.hit_counts[bid] = hits;
 }
 
-struct BfRangeCompactArgs {
-  const float* radii;
-  const uint32_t* cand_counts;
-  const uint64_t* cand_offsets;
-  const uint64_t* cand_lims;
-  const int32_t* cand_ids;
-  const float* cand_dists;
-  const uint64_t* hit_offsets;  // [Nq x parts] exclusive
-  const uint64_t* lims;         // [Nq + 1]
-  int32_t* ids;
-  float* dists;
-  uint64_t budget, capacity;
-  uint32_t Nq, parts;
-};
-
 // One wave per (query, part): its hits, in candidate order (ascending id), to ids / dists.
 __global__ void __launch_bounds__(kWave) bf_range_compact_kernel(const BfRangeCompactArgs a)
 {
@@ -411,6 +396,21 @@ __global__ void __launch_bounds__(kWave) bf_range_compact_kernel(const BfRangeCo
 }
 
 // ---- host -----------------------------------------------------------------------------------------
+void launch_bf_range_compact(const BfRangeCompactArgs& cp, hipStream_t stream)
+{
+  hipLaunchKernelGGL(bf_range_compact_kernel, grid_for(static_cast<uint64_t>(cp.Nq) * cp.parts),
+                     dim3(kWave), 0, stream, cp);
+  GGNN_HIP_CHECK(hipGetLastError());
+}
+
+void launch_bf_range_take_lims(const uint32_t* flag, const uint64_t* from, uint32_t n, uint64_t* lims,
+                               hipStream_t stream)
+{
+  hipLaunchKernelGGL(bf_range_take_lims_kernel, dim3(std::min((n + 255) / 256, 1024u)), dim3(256), 0,
+                     stream, flag, from, n, lims);
+  GGNN_HIP_CHECK(hipGetLastError());
+}
+
 static int bf_range_filter_mode(const BfRangeLaunch& a)
 {
   return !a.filter_bits ? kBfNoFilter : a.filter_table.query_labels ? kBfLabels : kBfBits;
@@ -654,18 +654,14 @@ static void launch_bf_range_mfma_t(const BfRangeLaunch& a, hipStream_t stream)
     cp.capacity = a.capacity;
     cp.Nq = a.Nq;
     cp.parts = parts;
-    hipLaunchKernelGGL(bf_range_compact_kernel, grid_for(pairs), dim3(kWave), 0, stream, cp);
+    launch_bf_range_compact(cp, stream);
   }
-  GGNN_HIP_CHECK(hipGetLastError());
 
   // the scan passes, gated by the flag: they answer the call iff the candidates did not fit
   BfRangeLaunch fb = a;
   fb.lims = scan_lims;
   launch_bf_range_scan(fb, flag, stream);
-  hipLaunchKernelGGL(bf_range_take_lims_kernel,
-                     dim3(std::min((a.Nq + 1 + 255) / 256, 1024u)), dim3(256), 0, stream, flag,
-                     scan_lims, a.Nq + 1, a.lims);
-  GGNN_HIP_CHECK(hipGetLastError());
+  launch_bf_range_take_lims(flag, scan_lims, a.Nq + 1, a.lims, stream);
 }
 
 void launch_bf_range_query_mfma(const BfRangeLaunch& a, hipStream_t stream)

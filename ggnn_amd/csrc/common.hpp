@@ -321,7 +321,8 @@ struct BfRangeLaunch {
   // tile path (bf_range_mfma.hip): 1 if the candidate budget overflowed and the scan answered the
   // call, else 0 (device, optional); *matrix_path (host, optional): 1 = the float tile path was chosen,
   // 2 = the integer tile kernels (bf_range_i8.hip; fell_back: a radius >= 2^24 at D > 258 sent the
-  // call to the scan), 0 = the scan
+  // call to the scan), 3 = the 16-bit tile kernels (bf_range_f16.hip; fell_back: the budget, a
+  // subnormal or non-finite input, or a candidate outside the instruction model), 0 = the scan
   uint32_t* fell_back{nullptr};
   int* matrix_path{nullptr};
 };
@@ -336,6 +337,12 @@ size_t bf_range_tile_lds_bytes(uint32_t D, int fm);
 // (0: Nq >= 256 and N_base >= 65536, 1: no, 2: minima waived)
 bool bf_range_i8_supported(const BfRangeLaunch& a);
 size_t bf_range_i8_lds_bytes(uint32_t D, int fm);
+// and for the 16-bit tile kernels (bf_range_f16.hip), tried first: float16 / bfloat16, squared L2,
+// D % 8 == 0, D <= 4096, a bitset's bit offset a multiple of 32; hooks BF_RANGE_PATH (1: no; 2 alone does
+// not select them) and BF_RANGE_F16 (0: bfloat16 with Nq >= 10000 and N_base >= 1000000, 1: no, 2: type
+// and minima waived)
+bool bf_range_f16_supported(const BfRangeLaunch& a);
+size_t bf_range_f16_lds_bytes(uint32_t D, int fm);
 
 // Label index (label_index.hip): the label column in CSR form over the global base ids -- keys[n_keys]
 // the distinct labels ascending, offsets[n_keys + 1] uint32 positions (offsets[0] = 0, offsets[n_keys]

@@ -45,6 +45,7 @@ enum Hook {
   kHookBfRangeCand,     // BF_RANGE_CAND    0 auto | entries of the tile path's candidate buffer (bf_range_mfma.hip)
   kHookBfRangeI8,       // BF_RANGE_I8      0 auto | 1 never | 2 integer tile kernels whenever dtype / measure / D / filter allow (bf_range_i8.hip)
   kHookBfF16,           // BF_F16           0 auto | 1 never | 2 16-bit tile kernels whenever dtype / measure / D / k allow (bf_f16.hip)
+  kHookBfRangeF16,      // BF_RANGE_F16     0 auto | 1 never | 2 16-bit range tile kernels whenever dtype / measure / D / filter allow (bf_range_f16.hip)
   kHookCount
 };
 

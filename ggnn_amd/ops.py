@@ -390,11 +390,13 @@ def bf_range_query(base, query, radius, measure=EUCLIDEAN, capacity=None, filter
     (see bf_query_filtered_by), labels + query_labels (see bf_query_labeled).
     Float32 / float16 / bfloat16 calls with Nq >= 256 and N >= 4096 pre-select on the matrix cores and
     decide every hit exactly; uint8 / int8 calls under EUCLIDEAN with Nq >= 256 and N >= 65536 take
-    exact verdicts from the integer matrix cores; the scan kernels answer the rest -- the same bits.
+    exact verdicts from the integer matrix cores; bfloat16 calls under EUCLIDEAN with Nq >= 10000 and
+    N >= 1000000 pre-select on the 16-bit matrix cores; the scan kernels answer the rest -- the same bits.
     routed=True returns (lims, ids, dists, matrix_path, fell_back) instead: matrix_path 1 if the
-    (last) call chose the float tile kernels, 2 the integer ones; fell_back 1 if the scan kernels
-    answered after all (candidate buffer overflow; byte rows: a radius >= 2^24 at D > 258; one host
-    read)."""
+    (last) call chose the float tile kernels, 2 the integer ones, 3 the 16-bit ones; fell_back 1 if the
+    scan kernels answered after all (candidate buffer overflow; byte rows: a radius >= 2^24 at D > 258;
+    16-bit tiles: a subnormal or non-finite input, or a candidate outside the instruction model; one
+    host read)."""
     _need(base, name="base"), _need(query, base.dtype, "query")
     Nq, N = query.shape[0], base.shape[0]
     radii = range_radii(radius, Nq, base.device)

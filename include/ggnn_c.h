@@ -550,8 +550,9 @@ ggnn_status ggnn_last_bf_query_rescanned(const ggnn_t* h, uint32_t* n_rescanned)
  * ggnn_last_bf_query_rescanned covers the filtered calls as well. */
 ggnn_status ggnn_last_bf_query_matrix_path(const ggnn_t* h, int* out);
 /* *out = 1 if the last ggnn_bf_range_query* call chose the float tile kernels (matrix-core
- * pre-selection, exact hits), 2 if it chose the integer tile kernels of uint8 / int8 rows, else 0 (the
- * scan kernels; also before the first call).  Results are the same bits. */
+ * pre-selection, exact hits), 2 if it chose the integer tile kernels of uint8 / int8 rows, 3 if it
+ * chose the 16-bit tile kernels of float16 / bfloat16 rows (bf_range_f16.hip), else 0 (the scan
+ * kernels; also before the first call).  Results are the same bits. */
 ggnn_status ggnn_last_bf_range_matrix_path(const ggnn_t* h, int* out);
 /* tests: 1 if a range launch of this shape would take the tile kernels under the current hooks (host
  * logic only; filter: 0 none, 1 bitset / table, 2 labels), and the LDS bytes of a tile workgroup */
@@ -562,6 +563,11 @@ int ggnn_debug_bf_range_route(ggnn_dtype dtype, uint32_t D, uint32_t Nq, uint32_
 int ggnn_debug_bf_range_i8_route(ggnn_dtype dtype, ggnn_measure measure, uint32_t D, uint32_t Nq,
                                  uint32_t N_base, uint64_t capacity, int filter,
                                  uint32_t filter_bit_offset, uint64_t* tile_lds_bytes);
+/* tests: the same for the 16-bit tile kernels of float16 / bfloat16 rows (hooks BF_RANGE_PATH,
+ * BF_RANGE_F16) */
+int ggnn_debug_bf_range_f16_route(ggnn_dtype dtype, ggnn_measure measure, uint32_t D, uint32_t Nq,
+                                  uint32_t N_base, uint64_t capacity, int filter,
+                                  uint32_t filter_bit_offset, uint64_t* tile_lds_bytes);
 /* tests: 1 if an unfiltered (filtered = 0) or filtered bf_query launch of this shape would take the
  * 16-bit tile kernels (bf_f16.hip) under the current hooks (BF_F16, BF_SCAN); host logic only */
 int ggnn_debug_bf_f16_route(ggnn_dtype dtype, ggnn_measure measure, uint32_t D, uint32_t Nq,
@@ -711,6 +717,13 @@ void ggnn_set_log_level(int level);
  *                             multiple of 32 and Nq >= 256, N >= 65536 | 1 = never | 2 = whenever those
  *                             conditions hold, whatever Nq and N; BF_RANGE_PATH = 1 still means the scan
  *                             kernels always (same results; test hook)
+ *   BF_RANGE_F16        0     range search on float16 / bfloat16 rows: 0 = 16-bit tile kernels
+ *                             (bf_range_f16.hip) when the measure is squared L2, D % 8 == 0, D <= 4096, a
+ *                             bitset's bit offset is a multiple of 32, the rows are bfloat16 and Nq >=
+ *                             10000, N >= 1000000 | 1 = never (the float32-staged tiles or the scan) | 2 =
+ *                             whenever measure, D and filter allow, float16 included, whatever Nq and N;
+ *                             BF_RANGE_PATH = 1 still means the scan kernels always, BF_RANGE_PATH = 2
+ *                             alone does not select them (same results; test hook)
  *   BF_F16              0     bf_query on float16 / bfloat16 rows: 0 = 16-bit tile kernels (bf_f16.hip)
  *                             when the measure is squared L2, the call has no filter of any kind,
  *                             D % 8 == 0, D <= 4096, k + 8 <= 120 (k <= 110 at D <= 32: the lists of
@@ -898,7 +911,9 @@ ggnn_status ggnn_op_bf_range_query_labeled(const void* base, ggnn_dtype dtype, u
  * *fell_back (DEVICE memory, may be NULL) receives 1 if the tile path's candidate buffer overflowed
  * (float rows) or a radius >= 2^24 met D > 258 (byte rows) and the scan kernels answered, else 0;
  * *matrix_path (HOST, may be NULL) receives 1 if the call chose the float tile kernels
- * (bf_range_mfma.hip), 2 if it chose the integer tile kernels (bf_range_i8.hip), else 0. */
+ * (bf_range_mfma.hip), 2 if it chose the integer tile kernels (bf_range_i8.hip), 3 if it chose the
+ * 16-bit tile kernels (bf_range_f16.hip: *fell_back is then also 1 after a subnormal or non-finite
+ * input or a candidate outside the instruction model), else 0. */
 ggnn_status ggnn_op_bf_range_query_routed(const void* base, ggnn_dtype dtype, uint32_t N_base,
                                           uint32_t D, const void* query, uint32_t Nq,
                                           const float* radii, ggnn_measure measure,
