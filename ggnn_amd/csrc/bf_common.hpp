@@ -96,6 +96,36 @@ size_t bf_i8v2_lds_bytes();
 size_t bf_i8v2_exchange_ints(uint32_t Nq, uint32_t slices);
 uint32_t bf_i8v2_default_rank_mask(uint32_t KP, uint32_t slices);
 
+// bf_i8_wide.hip: the register-set kernel for uint8 / int8 rows of 128 < D <= 4096 bytes under
+// squared L2 (the file's header has the arithmetic contract).  Norms are int32: |x'|^2 <= 2^26.
+struct BfI8WideArgs {
+  const void* base;
+  const uint4* query_packed;  // the query set in operand order (bf_i8_wide_packed_words), flipped, zero past D
+  const int32_t* bnorm;       // [N_base] |b'|^2
+  const int32_t* qnorm;       // [Nq] |q'|^2
+  int32_t* part_ids;          // [slices][Nq][KP]
+  float* part_dists;          // [slices][Nq][KP]
+  uint32_t D, nch, Nq, N_base, slices, rows_per_slice;  // nch: 128-byte column chunks of a row
+  uint32_t* gthr;             // exchange area, as BfMfmaArgs::gthr
+  uint32_t rank_mask, refresh_every;
+  int32_t* seed;              // [Nq], as BfMfmaArgs::seed
+  uint32_t seeding;
+};
+// (bf_i8_wide_supported / bf_i8_wide_routes: common.hpp)
+size_t bf_i8_wide_packed_words(uint32_t qblocks, uint32_t D);  // 32-bit words of the packed query set
+// norms[r] = |x'|^2 of N rows (bf_range_i8.hip's norm kernel; scratch_word: any device word, cleared)
+void launch_bf_i8_row_norms(const void* rows, uint32_t N, uint32_t D, bool is_signed, int32_t* norms,
+                            uint32_t* scratch_word, hipStream_t stream);
+void launch_bf_i8_wide_pack(const void* query, uint32_t Nq, uint32_t D, bool is_signed,
+                            uint32_t qblocks, uint4* packed, hipStream_t stream);
+// the tile kernel for KP in {4, 10, 16} (m.slices x qblocks workgroups of 256 queries), after a seeding
+// launch over the first seed_rows rows when m.seed is set and there are several slices
+void launch_bf_i8_wide(const BfI8WideArgs& m, uint32_t KP, bool is_signed, uint32_t qblocks,
+                       uint32_t seed_rows, hipStream_t stream);
+// the 2^24 rule: queries whose K-th reported distance is >= 2^24 are appended to the rescan list
+void launch_bf_i8_wide_uncertified(const float* dists, uint32_t Nq, uint32_t K, uint32_t* rescan_list,
+                                   uint32_t* rescan_count, hipStream_t stream);
+
 // ---- the scan kernels' argument block and filter verdicts (bf_query.hip, bf_range.hip) ----------
 struct BfArgs {
   const void* base;

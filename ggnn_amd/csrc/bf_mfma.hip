@@ -1534,10 +1534,126 @@ void bf_center_rows(const float* base, uint32_t N_base, uint32_t D, const float*
                      dim3(256), 0, stream, query, n4, D, mean, q_shifted);
 }
 
+// the exact re-rank of a launch's candidate lists
+static void launch_bf_rerank(const BfLaunch& a, const BfRerankArgs& rr, hipStream_t stream)
+{
+  const size_t rr_lds = wave_lds_bytes(2 * rr.cap);
+#define GGNN_BF_RERANK(T, LPR, NCH)                                                                \
+  do {                                                                                             \
+    if (a.measure == GGNN_EUCLIDEAN)                                                               \
+      hipLaunchKernelGGL((bf_rerank_kernel<T, LPR, NCH, kL2>), grid_for(a.Nq), dim3(kWave), rr_lds, \
+                         stream, rr);                                                              \
+    else                                                                                           \
+      hipLaunchKernelGGL((bf_rerank_kernel<T, LPR, NCH, kCos>), grid_for(a.Nq), dim3(kWave),       \
+                         rr_lds, stream, rr);                                                      \
+  } while (0)
+  GGNN_DISPATCH_DIST(a.dtype, a.D, GGNN_BF_RERANK);
+#undef GGNN_BF_RERANK
+  GGNN_HIP_CHECK(hipGetLastError());
+}
+
+// uint8 / int8 rows wider than 128 bytes under squared L2, k <= 16, no filter (bf_i8_wide_routes):
+// int32 norms, the query set packed in operand order, the register-set kernel of bf_i8_wide.hip, the
+// exact re-rank, the 2^24 rule (bf_i8_wide.hip's header), the re-scan of what that rule left open
+static void launch_bf_query_i8_wide(const BfLaunch& a, hipStream_t stream)
+{
+  const bool is_signed = a.dtype == GGNN_I8;
+  const uint32_t KP = a.k_query <= 4 ? 4u : a.k_query <= 10 ? 10u : 16u;
+  const uint32_t qblocks = (a.Nq + 255) / 256;
+  // one round of resident workgroups (two per CU), as for bf_i8v2_kernel; hook BF_SLICES
+  uint32_t slices = std::max(1u, std::min(32u, 512u / std::max(1u, qblocks)));
+  if (const int64_t hs = hook(kHookBfSlices); hs > 0)
+    slices = static_cast<uint32_t>(std::clamp<int64_t>(hs, 1, 64));
+  uint32_t rows_per_slice = (a.N_base + slices - 1) / slices;
+  rows_per_slice = (rows_per_slice + kBfTileRows - 1) / kBfTileRows * kBfTileRows;
+  slices = (a.N_base + rows_per_slice - 1) / rows_per_slice;
+
+  // one scratch block: [row norms N][query norms Nq][rescan_count etc. 4][rescan_list Nq][part ids]
+  // [part dists][re-scan slices ids][re-scan slices dists][exchange area + seeds][packed queries]
+  auto pad4 = [](size_t words) { return (words + 3) / 4 * 4; };
+  uint32_t rescan_slices = 0;
+  const size_t n_b = pad4(a.N_base), n_q = pad4(a.Nq);
+  const size_t n_parts = pad4(static_cast<size_t>(slices) * a.Nq * KP);
+  const size_t n_rescan = pad4(bf_rescan_tmp_entries(a, &rescan_slices));
+  const size_t n_exch = pad4(bf_i8v2_exchange_ints(a.Nq, slices));
+  const size_t n_pack = bf_i8_wide_packed_words(qblocks, a.D);
+  const size_t words = n_b + n_q + 4 + n_q + 2 * n_parts + 2 * n_rescan + n_exch + n_q + n_pack;
+  ScratchGuard scratch{scratch_alloc(words * 4, stream), stream};
+  int32_t* bnorm = static_cast<int32_t*>(scratch.p);
+  int32_t* qnorm = bnorm + n_b;
+  uint32_t* flags = reinterpret_cast<uint32_t*>(qnorm + n_q);  // [1] rescan count [2] norm kernels' word
+  uint32_t* rescan_list = flags + 4;
+  int32_t* part_ids = reinterpret_cast<int32_t*>(rescan_list + n_q);
+  float* part_dists = reinterpret_cast<float*>(part_ids + n_parts);
+  int32_t* rescan_ids = reinterpret_cast<int32_t*>(part_dists + n_parts);
+  float* rescan_dists = reinterpret_cast<float*>(rescan_ids + n_rescan);
+  uint32_t* gthr = reinterpret_cast<uint32_t*>(rescan_dists + n_rescan);
+  uint4* packed = reinterpret_cast<uint4*>(gthr + n_exch + n_q);
+  GGNN_HIP_CHECK(hipMemsetAsync(flags, 0, 4 * sizeof(uint32_t), stream));
+  GGNN_HIP_CHECK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(gthr), 0x7fffffff, n_exch + n_q,
+                                   stream));  // "nothing published", "no seed"
+  launch_bf_i8_row_norms(a.base, a.N_base, a.D, is_signed, bnorm, flags + 2, stream);
+  launch_bf_i8_row_norms(a.query, a.Nq, a.D, is_signed, qnorm, flags + 2, stream);
+  launch_bf_i8_wide_pack(a.query, a.Nq, a.D, is_signed, qblocks, packed, stream);
+
+  BfI8WideArgs m{};
+  m.base = a.base;
+  m.query_packed = packed;
+  m.bnorm = bnorm;
+  m.qnorm = qnorm;
+  m.part_ids = part_ids;
+  m.part_dists = part_dists;
+  m.D = a.D;
+  m.nch = (a.D + 127) / 128;
+  m.Nq = a.Nq;
+  m.N_base = a.N_base;
+  m.slices = slices;
+  m.rows_per_slice = rows_per_slice;
+  // hooks BF_I8_NOSHARE, BF_I8_RANKS, BF_I8_REFRESH (counted in tiles here), BF_I8_SEED: as for
+  // bf_i8v2_kernel (launch_bf_query_mfma)
+  m.gthr = hook(kHookBfI8NoShare) ? nullptr : gthr;
+  const int64_t hr = hook(kHookBfI8Ranks);
+  m.rank_mask = hr >= 0 ? static_cast<uint32_t>(hr) & 31u : bf_i8v2_default_rank_mask(KP, slices);
+  if (slices <= 1)
+    m.rank_mask = 0;  // nothing to exchange
+  m.refresh_every = static_cast<uint32_t>(std::clamp<int64_t>(hook(kHookBfI8Refresh), 1, 1 << 20));
+  m.seed = reinterpret_cast<int32_t*>(gthr + n_exch);
+  const uint32_t seed_rows = static_cast<uint32_t>(
+      std::clamp<int64_t>(hook(kHookBfI8Seed), 0, static_cast<int64_t>(a.N_base)));
+  launch_bf_i8_wide(m, KP, is_signed, qblocks, seed_rows, stream);
+
+  BfRerankArgs rr{};
+  rr.base = a.base;
+  rr.query = a.query;
+  rr.part_ids = part_ids;
+  rr.part_dists = part_dists;
+  rr.rescan_count = flags + 1;
+  rr.rescan_list = rescan_list;
+  rr.ids = a.ids;
+  rr.dists = a.dists;
+  rr.D = a.D;
+  rr.Nq = a.Nq;
+  rr.K = a.k_query;
+  rr.KP = KP;
+  rr.slices = slices;
+  rr.cap = (slices * KP + 3) / 4 * 4;
+  rr.exact_arith = 1;  // integer selection: the re-rank certifies nothing; the 2^24 rule follows
+  launch_bf_rerank(a, rr, stream);
+  launch_bf_i8_wide_uncertified(a.dists, a.Nq, a.k_query, rescan_list, flags + 1, stream);
+  launch_bf_rescan(a, rescan_list, flags + 1, rescan_ids, rescan_dists, stream);
+  if (a.n_rescanned)
+    GGNN_HIP_CHECK(hipMemcpyAsync(a.n_rescanned, flags + 1, sizeof(uint32_t),
+                                  hipMemcpyDeviceToDevice, stream));
+}
+
 void launch_bf_query_mfma(const BfLaunch& a, hipStream_t stream)
 {
   check_vector_layout(a.base, a.D, a.dtype);
   check_vector_layout(a.query, a.D, a.dtype);
+  if (bf_i8_wide_routes(a)) {
+    launch_bf_query_i8_wide(a, stream);
+    return;
+  }
   // a few more candidates than K per slice: makes the certificate (top of this file) succeed for
   // all but near-degenerate queries; correctness does not depend on the value
   // uint8 + squared L2 with rows of up to 128 bytes: integer contraction on the i8 matrix path;
@@ -1752,8 +1868,6 @@ void launch_bf_query_mfma(const BfLaunch& a, hipStream_t stream)
   rr.slices = slices;
   rr.cap = (slices * KP + 3) / 4 * 4;
   rr.exact_arith = use_i8 ? 1 : 0;
-  const size_t rr_lds = wave_lds_bytes(2 * rr.cap);
-
 #define GGNN_BF_MFMA(T, MODE_)                                                                    \
   do {                                                                                            \
     hipLaunchKernelGGL((row_norms_kernel<T>), dim3(norm_grid(a.N_base)), dim3(256), 0, stream,   \
@@ -1876,18 +1990,7 @@ void launch_bf_query_mfma(const BfLaunch& a, hipStream_t stream)
   }
 #undef GGNN_BF_MFMA
   GGNN_HIP_CHECK(hipGetLastError());
-#define GGNN_BF_RERANK(T, LPR, NCH)                                                                \
-  do {                                                                                             \
-    if (a.measure == GGNN_EUCLIDEAN)                                                               \
-      hipLaunchKernelGGL((bf_rerank_kernel<T, LPR, NCH, kL2>), grid_for(a.Nq), dim3(kWave), rr_lds, \
-                         stream, rr);                                                              \
-    else                                                                                           \
-      hipLaunchKernelGGL((bf_rerank_kernel<T, LPR, NCH, kCos>), grid_for(a.Nq), dim3(kWave),       \
-                         rr_lds, stream, rr);                                                      \
-  } while (0)
-  GGNN_DISPATCH_DIST(a.dtype, a.D, GGNN_BF_RERANK);
-#undef GGNN_BF_RERANK
-  GGNN_HIP_CHECK(hipGetLastError());
+  launch_bf_rerank(a, rr, stream);
   // queries without a certificate: exact scan (usually none; the surplus blocks leave at once)
   if (!use_i8)
     launch_bf_rescan(a, rescan_list, flags + 1, rescan_ids, rescan_dists, stream);

@@ -612,6 +612,21 @@ static void launch_bf_range_i8_t(const BfRangeLaunch& a, hipStream_t stream)
   GGNN_HIP_CHECK(hipGetLastError());
 }
 
+// the int32 row norms alone (bf_common.hpp): shared with the wide-row kernel of bf_query
+void launch_bf_i8_row_norms(const void* rows, uint32_t N, uint32_t D, bool is_signed, int32_t* norms,
+                            uint32_t* scratch_word, hipStream_t stream)
+{
+  const dim3 grid(std::clamp((N + 15u) / 16u, 1u, 4096u));
+  const uint8_t* r = static_cast<const uint8_t*>(rows);
+  if (is_signed)
+    hipLaunchKernelGGL((bf_range_i8_norms_kernel<true>), grid, dim3(256), 0, stream, r, N, D, norms,
+                       scratch_word);
+  else
+    hipLaunchKernelGGL((bf_range_i8_norms_kernel<false>), grid, dim3(256), 0, stream, r, N, D, norms,
+                       scratch_word);
+  GGNN_HIP_CHECK(hipGetLastError());
+}
+
 void launch_bf_range_query_i8(const BfRangeLaunch& a, hipStream_t stream)
 {
   if (a.dtype == GGNN_I8)

@@ -291,6 +291,11 @@ void launch_bf_query(const BfLaunch& a, hipStream_t stream);
 // follow, or null
 bool bf_f16_supported(const BfLaunch& a);
 void bf_f16_set_ratio_sink(uint32_t* device_word);
+// host side of the wide-row integer kernel (bf_i8_wide.hip): the launch is an unfiltered uint8 / int8 launch under squared L2 with 128 < D <= 4096, D % 16 == 0, k <= 16,
+// Nq >= 256, N_base >= 4096 and hook BF_NO_I8 = 0
+bool bf_i8_wide_supported(const BfLaunch& a);
+// ... that launch_bf_query_mfma sends to the kernel under hook BF_I8_WIDE (0 auto | 1 never | 2 always)
+bool bf_i8_wide_routes(const BfLaunch& a);
 
 // Exact range search (bf_range.hip): every base row i that the filter admits and whose distance to
 // query n -- the float32 value launch_bf_query's scan kernel reports for the pair: squared L2 or

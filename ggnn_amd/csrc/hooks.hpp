@@ -46,6 +46,7 @@ enum Hook {
   kHookBfRangeI8,       // BF_RANGE_I8      0 auto | 1 never | 2 integer tile kernels whenever dtype / measure / D / filter allow (bf_range_i8.hip)
   kHookBfF16,           // BF_F16           0 auto | 1 never | 2 16-bit tile kernels whenever dtype / measure / D / k allow (bf_f16.hip)
   kHookBfRangeF16,      // BF_RANGE_F16     0 auto | 1 never | 2 16-bit range tile kernels whenever dtype / measure / D / filter allow (bf_range_f16.hip)
+  kHookBfI8Wide,        // BF_I8_WIDE       0 auto | 1 never | 2 wide-row integer kernel of bf_query whenever dtype / measure / D / k / shape allow (bf_i8_wide.hip)
   kHookCount
 };
 

@@ -136,7 +136,11 @@ ggnn_status ggnn_synchronize(ggnn_t* h);
 /* wait for the batches of one slot only (slots are taken modulo the number of streams, 4) */
 ggnn_status ggnn_synchronize_slot(ggnn_t* h, uint32_t slot);
 
-/* bfQuery ggnn.cuh:162-172, ggnn.cu:543-564 */
+/* bfQuery ggnn.cuh:162-172, ggnn.cu:543-564
+ * uint8 / int8 rows under squared L2 run on the integer matrix cores: rows of up to 128 bytes always
+ * (bf_i8.hip), wider rows (D % 16 == 0, D <= 4096, k_query <= 16) from 10000 queries x 1000000 rows on
+ * or under hook BF_I8_WIDE = 2 (bf_i8_wide.hip).  Exact either way: a query whose k-th distance is
+ * >= 2^24 is answered by the scan and counted by ggnn_last_bf_query_rescanned. */
 ggnn_status ggnn_bf_query(ggnn_t* h, const void* query, uint64_t Nq, uint32_t D,
                           ggnn_dtype dtype, ggnn_location location, int gpu_id, uint32_t k_gt,
                           ggnn_measure measure, int32_t* ids_out, float* dists_out,
@@ -572,6 +576,10 @@ int ggnn_debug_bf_range_f16_route(ggnn_dtype dtype, ggnn_measure measure, uint32
  * 16-bit tile kernels (bf_f16.hip) under the current hooks (BF_F16, BF_SCAN); host logic only */
 int ggnn_debug_bf_f16_route(ggnn_dtype dtype, ggnn_measure measure, uint32_t D, uint32_t Nq,
                             uint32_t N_base, uint32_t k_query, int filtered);
+/* tests: the same for the wide-row integer kernel of uint8 / int8 rows (bf_i8_wide.hip; hooks BF_I8_WIDE,
+ * BF_NO_I8, BF_SCAN) */
+int ggnn_debug_bf_i8_wide_route(ggnn_dtype dtype, ggnn_measure measure, uint32_t D, uint32_t Nq,
+                                uint32_t N_base, uint32_t k_query, int filtered);
 /* scripts/bf_f16_cm.py: a DEVICE word that the 16-bit tile path's re-rank raises (atomic max of float
  * bits) to the largest |d_e - d_dir| / ((2D+8) 2^-24 (|q|^2 + |x|^2)) over the candidates of the
  * launches that follow -- the evidence behind the certificate's model constant; NULL:
@@ -724,6 +732,12 @@ void ggnn_set_log_level(int level);
  *                             whenever measure, D and filter allow, float16 included, whatever Nq and N;
  *                             BF_RANGE_PATH = 1 still means the scan kernels always, BF_RANGE_PATH = 2
  *                             alone does not select them (same results; test hook)
+ *   BF_I8_WIDE          0     bf_query on uint8 / int8 rows wider than 128 bytes: 0 = the wide-row integer
+ *                             kernel (bf_i8_wide.hip) when the measure is squared L2, the call has no
+ *                             filter, D % 16 == 0, D <= 4096, k <= 16, BF_NO_I8 = 0 and Nq >= 10000,
+ *                             N >= 1000000 | 1 = never (the float32-staged tiles) | 2 = whenever those
+ *                             conditions hold with Nq >= 256, N >= 4096; BF_SCAN = 1 still means the scan
+ *                             (same results; test hook)
  *   BF_F16              0     bf_query on float16 / bfloat16 rows: 0 = 16-bit tile kernels (bf_f16.hip)
  *                             when the measure is squared L2, the call has no filter of any kind,
  *                             D % 8 == 0, D <= 4096, k + 8 <= 120 (k <= 110 at D <= 32: the lists of
