@@ -1298,7 +1298,9 @@ class GGNN:
     def last_bf_query_matrix_path(self):
         """1 if the last bf_query* call (filtered or not) ran the matrix-core tile kernel on every
         shard, 2 if it ran the 16-bit tile kernels (float16 / bfloat16 rows, squared L2, unfiltered),
-        else 0 (the scan kernels); results are bit-identical on either path"""
+        3 if it ran the filtered integer kernels (uint8 / int8 rows, squared L2, under a bitset,
+        filter ids or labels; hook BF_I8_FILTERED), else 0 (the scan kernels); results are
+        bit-identical on either path"""
         n = C.c_int()
         self._check(lib().ggnn_last_bf_query_matrix_path(self._h, C.byref(n)))
         return int(n.value)

@@ -126,6 +126,45 @@ void launch_bf_i8_wide(const BfI8WideArgs& m, uint32_t KP, bool is_signed, uint3
 void launch_bf_i8_wide_uncertified(const float* dists, uint32_t Nq, uint32_t K, uint32_t* rescan_list,
                                    uint32_t* rescan_count, hipStream_t stream);
 
+// bf_i8_filtered.hip: the filtered forms of the two register-set kernels (the file's header has the
+// design).  One argument block for both row regimes; norms are int32 as for the wide rows.
+//   kI8fBits    the call's one bitset, folded into the staged row norms
+//   kI8fTable   a filter table row per query, verdict per (query, row) on the hit path
+//   kI8fLabels  an int32 label per base row against one per query, verdict on the hit path
+constexpr int kI8fBits = 1, kI8fTable = 2, kI8fLabels = 3;
+struct BfI8FilteredArgs {
+  const void* base;
+  const void* query;          // D <= 128: the query rows (the operand stays in registers)
+  const uint4* query_packed;  // D > 128: the query set in operand order (launch_bf_i8_wide_pack)
+  const int32_t* bnorm;       // [N_base] |b'|^2
+  const int32_t* qnorm;       // [Nq] |q'|^2
+  int32_t* part_ids;          // [slices][Nq][KP]
+  float* part_dists;          // [slices][Nq][KP]
+  uint32_t D, nch, Nq, N_base, slices, rows_per_slice;
+  uint32_t flip;              // 0x80808080 for uint8 rows, 0 for int8
+  uint32_t* gthr;             // exchange area, as BfMfmaArgs::gthr
+  uint32_t rank_mask, refresh_every;
+  int32_t* seed;              // [Nq], as BfMfmaArgs::seed
+  uint32_t seeding;
+  const uint32_t* filter_bits;  // bitset / filter table / label column (BfLaunch)
+  uint32_t filter_bit_offset;   // bitsets: a multiple of 32
+  FilterTable filter_table;
+};
+// the kernels of one filter mode live in an object of their own (Makefile: bf_i8_filtered.hip once per
+// mode); nm: 32-column blocks of the resident operand (2 | 4), 0 = the streamed regime
+const void* bf_i8f_bits_kernel(int nm, uint32_t KP);
+const void* bf_i8f_table_kernel(int nm, uint32_t KP);
+const void* bf_i8f_labels_kernel(int nm, uint32_t KP);
+size_t bf_i8f_lds_bytes(int fm, bool wide);
+// the kernel of the launch for KP in {4, 10, 16} (m.slices x qblocks workgroups of 256 queries), after a
+// seeding launch over the first seed_rows rows when m.seed is set and there are several slices
+void launch_bf_i8_filtered(const BfI8FilteredArgs& m, int fm, uint32_t KP, uint32_t qblocks,
+                           uint32_t seed_rows, hipStream_t stream);
+// the 2^24 rule under a filter: queries whose K-th reported distance is finite and >= 2^24
+void launch_bf_i8_filtered_uncertified(const float* dists, uint32_t Nq, uint32_t K,
+                                       uint32_t* rescan_list, uint32_t* rescan_count,
+                                       hipStream_t stream);
+
 // ---- the scan kernels' argument block and filter verdicts (bf_query.hip, bf_range.hip) ----------
 struct BfArgs {
   const void* base;

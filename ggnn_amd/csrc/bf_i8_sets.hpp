@@ -100,4 +100,84 @@ GGNN_DEV int i8v2_qrow(int r, int h)
   return (r & 3) + 8 * (r >> 2) + 4 * h;  // query row of accumulator register r in half-wave h
 }
 
+// ---- the lane = query bookkeeping as functions (bf_i8_filtered.hip: both of its kernels) ------------
+// bf_i8v2_kernel and bf_i8w_kernel carry the same steps as lambdas; these are their bodies, word for word.
+// slot of query (lane & 31) of set (lane >> 5) in the offset block, which is kept in matrix order
+GGNN_DEV int i8_offset_slot(int lane)
+{
+  return (lane & 32) + 16 * ((lane >> 2) & 1) + (lane & 3) + 4 * ((lane & 31) >> 3);
+}
+// offsets of set s2 as the accumulators of half-wave h want them
+GGNN_DEV i32x16 i8_load_offsets(const int* hq_w, int s2, int h)
+{
+  const i32x4* p = reinterpret_cast<const i32x4*>(hq_w + s2 * 32 + 16 * h);
+  const i32x4 a0 = p[0], a1 = p[1], a2 = p[2], a3 = p[3];
+  return i32x16{a0[0], a0[1], a0[2], a0[3], a1[0], a1[1], a1[2], a1[3],
+                a2[0], a2[1], a2[2], a2[3], a3[0], a3[1], a3[2], a3[3]};
+}
+// applies the pending candidates of all 64 queries in lockstep: one sorted insertion per query and
+// iteration, all in registers; the pending counts are reset
+template <int KPT>
+GGNN_DEV void i8_apply_pending(int (&sd)[KPT], int (&si)[KPT], int qn_q, int* pc_w, const int* pd_w,
+                               const int* pi_w, int lane)
+{
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  const int cnt = min(pc_w[lane], kI8v2Pend);
+  pc_w[lane] = 0;
+  for (int i = 0; __any(i < cnt); ++i) {
+    const bool have = i < cnt;
+    // (an absent record is "infinity": it changes nothing)
+    const int rd = have ? qn_q - pd_w[i * 64 + lane] : 0x7fffffff;
+    const int rid = have ? pi_w[i * 64 + lane] : 0x7fffffff;
+    const unsigned long long rec =
+        (static_cast<unsigned long long>(static_cast<unsigned>(rd)) << 32) | static_cast<unsigned>(rid);
+    bool lt_prev = false;  // rec < entry k-1
+    int pd_ = 0, pi_ = 0;  // entry k-1 before this insertion
+#pragma unroll
+    for (int k = 0; k < KPT; ++k) {
+      const unsigned long long ek =
+          (static_cast<unsigned long long>(static_cast<unsigned>(sd[k])) << 32) | static_cast<unsigned>(si[k]);
+      const bool lt = rec < ek;
+      const int od = sd[k], oi = si[k];
+      sd[k] = lt_prev ? pd_ : (lt ? rd : od);
+      si[k] = lt_prev ? pi_ : (lt ? rid : oi);
+      lt_prev = lt;
+      pd_ = od;
+      pi_ = oi;
+    }
+  }
+}
+// publishes this slice's entries at the positions of rank_mask (single writer per word) and derives the
+// bound of the query from what all slices published: 0x7fffffff = none yet
+template <int KPT>
+GGNN_DEV int i8_exchange_bound(const int (&sd)[KPT], int* gl_q, int sl4, uint32_t slice, uint32_t rank_mask)
+{
+  constexpr int NR = i8_ranks<KPT>();
+  int bound = 0x7fffffff;
+  [&]<int... I>(std::integer_sequence<int, I...>) {
+    ((((rank_mask >> I) & 1u) ? __hip_atomic_store(gl_q + I * 4 * sl4 + slice, sd[i8_rank_pos<KPT>(I)],
+                                                   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+                              : (void)0),
+     ...);
+    ((bound = ((rank_mask >> I) & 1u)
+                  ? min(bound, i8_mth_smallest<(KPT + i8_rank_pos<KPT>(I)) / (i8_rank_pos<KPT>(I) + 1)>(
+                                   gl_q + I * 4 * sl4, sl4))
+                  : bound),
+     ...);
+  }(std::make_integer_sequence<int, NR>{});
+  return bound;
+}
+// a slice's set of one query leaves: unused slots as kEmptyKey / +inf
+template <int KPT>
+GGNN_DEV void i8_write_set(const int (&sd)[KPT], const int (&si)[KPT], int32_t* ids, float* dists)
+{
+#pragma unroll
+  for (int k = 0; k < KPT; ++k) {
+    const bool used = sd[k] != 0x7fffffff;
+    ids[k] = used ? si[k] : kEmptyKey;
+    dists[k] = used ? static_cast<float>(sd[k]) : inf_f();
+  }
+}
+
 }  // namespace ggnn_amd

@@ -451,12 +451,21 @@ void launch_bf_query(const BfLaunch& a_in, hipStream_t stream)
 
   // large batches: Q x B^T on the matrix cores (bf_mfma.hip); hook BF_SCAN = 1 forces the scan,
   // for filtered calls too (the A/B switch).  A filtered call keeps the scan
-  //   - at the shapes of the integer kernels (uint8 / int8, squared L2, D <= 128): they have no
-  //     filtered form
-  //   - on int8 rows at every shape: the filtered tile kernels are not instantiated for the type
+  //   - at the shapes of the integer kernels (uint8 / int8, squared L2, D <= 128), unless the filtered
+  //     integer kernels take it (below): the unfiltered ones have no filtered form
+  //   - on int8 rows at every shape, with the same exception: the filtered float tile kernels are not
+  //     instantiated for the type
   //   - under a bitset (per call or table) whose bit offset is not a multiple of 32: a tile's 32
   //     verdicts of a query are then not one word of its bitset (the engine's offsets are 0)
   //   (labels: N_base <= kMaxLabeledShardRows holds on both paths, required above)
+  // A filtered call on uint8 / int8 rows under squared L2 with k <= 16 has the filtered integer kernels
+  // (bf_i8_filtered.hip) where bf_i8_filtered_routes opens them: hook BF_I8_FILTERED, path 3
+  if (hook(kHookBfScan) != 1 && bf_i8_filtered_routes(a)) {
+    launch_bf_query_i8_filtered(a, stream);
+    if (a.matrix_path)
+      *a.matrix_path = 3;
+    return;
+  }
   bool force_scan = hook(kHookBfScan) == 1;
   if (a.filter_bits) {
     const bool bits = !a.filter_table.query_labels;

@@ -296,6 +296,13 @@ void bf_f16_set_ratio_sink(uint32_t* device_word);
 bool bf_i8_wide_supported(const BfLaunch& a);
 // ... that launch_bf_query_mfma sends to the kernel under hook BF_I8_WIDE (0 auto | 1 never | 2 always)
 bool bf_i8_wide_routes(const BfLaunch& a);
+// host side of the filtered integer kernels (bf_i8_filtered.hip): the launch is a uint8 / int8 launch
+// under squared L2 with a per-call bitset, a filter table or one label per query, D % 16 == 0, D <= 4096,
+// k <= 16, Nq >= 256, N_base >= 4096, a bitset offset that is a multiple of 32 and hook BF_NO_I8 = 0
+bool bf_i8_filtered_supported(const BfLaunch& a);
+// ... that launch_bf_query sends to them under hook BF_I8_FILTERED (0 auto | 1 never | 2 always)
+bool bf_i8_filtered_routes(const BfLaunch& a);
+void launch_bf_query_i8_filtered(const BfLaunch& a, hipStream_t stream);
 
 // Exact range search (bf_range.hip): every base row i that the filter admits and whose distance to
 // query n -- the float32 value launch_bf_query's scan kernel reports for the pair: squared L2 or

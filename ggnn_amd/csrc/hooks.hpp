@@ -47,6 +47,7 @@ enum Hook {
   kHookBfF16,           // BF_F16           0 auto | 1 never | 2 16-bit tile kernels whenever dtype / measure / D / k allow (bf_f16.hip)
   kHookBfRangeF16,      // BF_RANGE_F16     0 auto | 1 never | 2 16-bit range tile kernels whenever dtype / measure / D / filter allow (bf_range_f16.hip)
   kHookBfI8Wide,        // BF_I8_WIDE       0 auto | 1 never | 2 wide-row integer kernel of bf_query whenever dtype / measure / D / k / shape allow (bf_i8_wide.hip)
+  kHookBfI8Filtered,    // BF_I8_FILTERED   0 auto | 1 never | 2 filtered integer kernels of bf_query whenever dtype / measure / D / k / filter allow (bf_i8_filtered.hip)
   kHookCount
 };
 

@@ -200,7 +200,8 @@ def bf_query_filtered(base, query, k_query, filter_bits, measure=EUCLIDEAN, filt
     """the exact k nearest among the rows the bitset allows (row i: bit i + filter_bit_offset);
     slots beyond the number of allowed rows are (-1, +inf).
     rescanned=True: returns (ids, dists, rescanned, matrix_path) -- how many queries the
-    matrix-core path handed to the scan, and 1 if the launch ran the tile kernels at all (0: scan)"""
+    matrix-core path handed to the scan, and 1 if the launch ran the tile kernels at all, 3 if it ran
+    the filtered integer kernels of uint8 / int8 rows (hook BF_I8_FILTERED), 0: the scan"""
     _need(base, name="base"), _need(query, base.dtype, "query")
     _need(filter_bits, torch.int32, "filter_bits")
     if filter_bits.numel() * 32 < filter_bit_offset + base.shape[0]:

@@ -548,7 +548,9 @@ ggnn_status ggnn_last_query_parts(const ggnn_t* h, uint32_t* parts);
 ggnn_status ggnn_last_bf_query_rescanned(const ggnn_t* h, uint32_t* n_rescanned);
 /* *out = 1 if the last ggnn_bf_query* call of the handle (filtered or not) ran the matrix-core
  * tile kernel on every shard, 2 if it ran the 16-bit tile kernels (float16 / bfloat16 rows, squared
- * L2, no filter: bf_f16.hip, hook BF_F16), else 0 (the scan kernels; also before the first call and after a
+ * L2, no filter: bf_f16.hip, hook BF_F16), 3 if it ran the filtered integer kernels (uint8 / int8 rows,
+ * squared L2, a bitset, filter ids or labels: bf_i8_filtered.hip, hook BF_I8_FILTERED), else 0 (the scan
+ * kernels; also before the first call and after a
  * call without queries).  Results are bit-identical on either path: this getter is how a caller
  * or a test tells which one ran.  out == NULL: GGNN_INVALID_ARGUMENT.
  * ggnn_last_bf_query_rescanned covers the filtered calls as well. */
@@ -738,6 +740,14 @@ void ggnn_set_log_level(int level);
  *                             N >= 1000000 | 1 = never (the float32-staged tiles) | 2 = whenever those
  *                             conditions hold with Nq >= 256, N >= 4096; BF_SCAN = 1 still means the scan
  *                             (same results; test hook)
+ *   BF_I8_FILTERED      0     filtered bf_query (per-call bitset, filter ids, one label per query) on
+ *                             uint8 / int8 rows: 0 = the filtered integer kernels (bf_i8_filtered.hip)
+ *                             when the measure is squared L2, D % 16 == 0, D <= 4096, k <= 16, a bitset's
+ *                             bit offset is a multiple of 32, BF_NO_I8 = 0 and Nq >= 10000, N >= 1000000
+ *                             (the shape class measured) | 1 = never (the scan, or the
+ *                             float32-staged filtered tiles for uint8 rows wider than 128 bytes) | 2 =
+ *                             whenever those conditions hold with Nq >= 256, N >= 4096; BF_SCAN = 1
+ *                             still means the scan (same results; test hook)
  *   BF_F16              0     bf_query on float16 / bfloat16 rows: 0 = 16-bit tile kernels (bf_f16.hip)
  *                             when the measure is squared L2, the call has no filter of any kind,
  *                             D % 8 == 0, D <= 4096, k + 8 <= 120 (k <= 110 at D <= 32: the lists of
@@ -1102,7 +1112,8 @@ ggnn_status ggnn_op_bf_query_labeled_mask(const void* base, ggnn_dtype dtype, ui
  * ggnn_op_bf_query_certified): *n_rescanned (DEVICE memory, may be NULL) receives the number of
  * queries the matrix-core pre-selection could not certify and the filtered scan answered instead;
  * *matrix_path (HOST memory, may be NULL) is set before the call returns to 1 if the launch ran
- * the tile kernels and to 0 if it ran the scan. */
+ * the tile kernels, to 3 if it ran the filtered integer kernels of uint8 / int8 rows
+ * (bf_i8_filtered.hip, hook BF_I8_FILTERED) and to 0 if it ran the scan. */
 ggnn_status ggnn_op_bf_query_filtered_certified(const void* base, ggnn_dtype dtype,
                                                 uint32_t N_base, uint32_t D, const void* query,
                                                 uint32_t Nq, uint32_t k_query,

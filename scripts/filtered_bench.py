@@ -30,7 +30,7 @@ query labels drawn uniformly.  Kernel ms of the mixed batch through `query_label
 T-row table (`query_filtered_by`), alternating, every repeat listed; recall@10 of the labelled
 call against `bf_query_labeled`; resident bytes per GPU of both forms.
 
-    python scripts/filtered_bench.py --bf [--tenants 16] [--big-table 1024]
+    python scripts/filtered_bench.py --bf [--tenants 16] [--big-table 1024] [--dtype uint8|int8]
 
 The filtered brute force alone (no graph is built): on one handle, alternating per repeat, the
 time of each call under hook BF_SCAN = 1 (the scan kernels) and without it (the matrix-core tile
@@ -86,6 +86,7 @@ def main():
     ap.add_argument("--labels", action="store_true")
     ap.add_argument("--label-tenants", type=int, nargs="+", default=[16, 1024])
     ap.add_argument("--bf", action="store_true")
+    ap.add_argument("--dtype", choices=["float32", "uint8", "int8"], default="float32")
     ap.add_argument("--label-sets", action="store_true")
     ap.add_argument("--ranges", action="store_true")
     ap.add_argument("--masks", action="store_true")
@@ -94,6 +95,12 @@ def main():
     centres = rs.normal(size=(256, a.d)).astype(np.float32) * 2
     base = centres[rs.integers(0, 256, a.n)] + rs.normal(size=(a.n, a.d)).astype(np.float32)
     query = centres[rs.integers(0, 256, a.queries)] + rs.normal(size=(a.queries, a.d)).astype(np.float32)
+    if a.dtype != "float32":
+        # scalar-quantised rows: the same clusters on a byte grid (uint8 0 .. 255, int8 the same bytes - 128)
+        lo, hi = min(base.min(), query.min()), max(base.max(), query.max())
+        shift = 0 if a.dtype == "uint8" else 128
+        base, query = (np.rint((x - lo) * (255.0 / (hi - lo))).astype(np.int16) - shift for x in (base, query))
+        base, query = base.astype(a.dtype), query.astype(a.dtype)
     g = ggnn.GGNN()
     g.set_base(torch.from_numpy(base).cuda())
     q = torch.from_numpy(query).cuda()
@@ -155,19 +162,25 @@ def main():
 
 
 def brute_force(a, g, q):
-    """scan against matrix path of the filtered brute force, alternating per repeat"""
+    """scan against matrix path of the filtered brute force, alternating per repeat.  --dtype uint8 / int8:
+    the routing without the filtered integer kernels (BF_I8_FILTERED = 1, reported as scan_ms whichever
+    path that is) against those kernels (BF_I8_FILTERED = 2, matrix_ms)"""
     from ggnn_amd import _lib
     rs = np.random.default_rng(3)
+    a_side, b_side = ({"BF_SCAN": 1}, {}) if a.dtype == "float32" else \
+        ({"BF_I8_FILTERED": 1}, {"BF_I8_FILTERED": 2})
 
     def ab(name, call, **extra):
         scan, matrix = [], []
         for _ in range(a.reps):
-            with _lib.hooks(BF_SCAN=1):
+            with _lib.hooks(**a_side):
                 call()
+                a_path = g.last_bf_query_matrix_path()
             scan.append(round(g.last_timing_ms()["bf_query_ms"], 3))
-            call()
+            with _lib.hooks(**b_side):
+                call()
             matrix.append(round(g.last_timing_ms()["bf_query_ms"], 3))
-        print(json.dumps({"bf": name, **extra, "scan_ms": scan, "matrix_ms": matrix,
+        print(json.dumps({"bf": name, **extra, "scan_ms": scan, "scan_path": a_path, "matrix_ms": matrix,
                           "matrix_path": g.last_bf_query_matrix_path(),
                           "rescanned": g.last_bf_query_rescanned()}), flush=True)
 
