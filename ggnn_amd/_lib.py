@@ -231,6 +231,11 @@ SIGNATURES = {
     "ggnn_op_bf_query_labeled_certified": (_int, [_vp, _int, _u32, _u32, _vp, _u32, _u32, _int,
                                                   _vp, _vp, _vp, _u64, _vp, _u32, _vp,
                                                   C.POINTER(C.c_int), _vp]),
+    # the label-set / -range / -mask calls + (n_rescanned, matrix_path) before the stream
+    **{"ggnn_op_bf_query_labeled_%s_certified" % family:
+       (_int, [_vp, _int, _u32, _u32, _vp, _u32, _u32, _int, _vp, _vp, _vp, _u64, _vp, _u32, _vp,
+               _u32, _u64, _vp, _u32, _vp, C.POINTER(C.c_int), _vp])
+       for family in ("in", "range", "mask")},
     # range search: ..., radii, measure, capacity, lims, ids, dists, ...
     "ggnn_bf_range_query": (_int, [_vp, _vp, _u64, _u32, _int, _int, _int, _vp, _int, _u64, _vp, _vp,
                                    _vp, _int]),

@@ -780,8 +780,9 @@ class GGNN:
     def bf_query_labeled_in(self, query, k_gt=100, measure=DistanceMeasure.Euclidean,
                             label_sets=None, filter_ids=None):
         """Extension: the exact `k_gt` nearest among the base vectors `label_sets` and `filter_ids`
-        admit (see `query_labeled_in`); slots beyond their number are (-1, +inf).  Always the scan
-        kernels.  `label_sets=None` is `bf_query_filtered_by`; both `None` is `bf_query`."""
+        admit (see `query_labeled_in`); slots beyond their number are (-1, +inf).  Large batches
+        run the tile kernels under a predicate stage, the rest the scan kernels (hook BF_LABEL_TILES;
+        `last_bf_query_matrix_path()` says which), same bits.  `label_sets=None` is `bf_query_filtered_by`; both `None` is `bf_query`."""
         if label_sets is None:
             return self.bf_query_filtered_by(query, k_gt, measure, filter_ids=filter_ids)
         t = _as_tensor(query, what="query")
@@ -818,8 +819,9 @@ class GGNN:
                                label_ranges=None, filter_ids=None):
         """Extension: the exact `k_gt` nearest among the base vectors `label_ranges` and
         `filter_ids` admit (see `query_labeled_range`); slots beyond their number are (-1, +inf).
-        Always the scan kernels.  `label_ranges=None` is `bf_query_filtered_by`; both `None` is
-        `bf_query`."""
+        Large batches run the tile kernels under a predicate stage, the rest the scan kernels (hook
+        BF_LABEL_TILES; `last_bf_query_matrix_path()` says which), same bits.  `label_ranges=None`
+        is `bf_query_filtered_by`; both `None` is `bf_query`."""
         if label_ranges is None:
             return self.bf_query_filtered_by(query, k_gt, measure, filter_ids=filter_ids)
         t = _as_tensor(query, what="query")
@@ -856,8 +858,9 @@ class GGNN:
     def bf_query_labeled_mask(self, query, k_gt=100, measure=DistanceMeasure.Euclidean,
                               label_masks=None, filter_ids=None):
         """Extension: the exact `k_gt` nearest among the base vectors `label_masks` and `filter_ids`
-        admit (see `query_labeled_mask`); slots beyond their number are (-1, +inf).  Always the scan
-        kernels.  `label_masks=None` is `bf_query_filtered_by`; both `None` is `bf_query`."""
+        admit (see `query_labeled_mask`); slots beyond their number are (-1, +inf).  Large batches
+        run the tile kernels under a predicate stage, the rest the scan kernels (hook BF_LABEL_TILES;
+        `last_bf_query_matrix_path()` says which), same bits.  `label_masks=None` is `bf_query_filtered_by`; both `None` is `bf_query`."""
         if label_masks is None:
             return self.bf_query_filtered_by(query, k_gt, measure, filter_ids=filter_ids)
         t = _as_tensor(query, what="query")

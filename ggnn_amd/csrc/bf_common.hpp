@@ -37,27 +37,53 @@ struct BfMfmaArgs {
 };
 
 // Filter mode of bf_mfma_kernel (template parameter FM).  The filtered instantiations live in
-// translation units of their own (bf_mfma_bits.hip, bf_mfma_labels.hip); the unfiltered kernels
-// keep their argument block.
+// translation units of their own (bf_mfma_bits.hip, bf_mfma_labels.hip, bf_mfma_pred.hip); the
+// unfiltered kernels keep their argument block.
 //   kBfBits    a bitset row per query: the call's one bitset for every query, or the row of the
 //              filter table that the query's filter id names
 //   kBfLabels  an int32 label per base row against one per query
-constexpr int kBfNoFilter = 0, kBfBits = 1, kBfLabels = 2;
+//   kBfPredicate  a predicate on the int32 label of a base row -- a label set, label ranges or label
+//              masks per query (LabelSetSpec / LabelRangeSpec / LabelMaskSpec) --, optionally ANDed
+//              with the row of the filter table that the query's filter id names
+constexpr int kBfNoFilter = 0, kBfBits = 1, kBfLabels = 2, kBfPredicate = 3;
 struct BfMfmaFilteredArgs : BfMfmaArgs {
   const uint32_t* filter_bits;  // bitset / filter table / label column (BfLaunch)
   uint32_t filter_bit_offset;   // kBfBits: a multiple of 32
   FilterTable filter_table;
 };
+// kBfPredicate: one record of kBfPredWords words per query, made by bf_pred_prep_kernel (bf_mfma.hip)
+// from the user's spec once per launch -- what the wave constructors of LabelSetFilter,
+// LabelRangeFilter and LabelMaskFilter (traversal.hpp) make once per wave:
+//   sets    w[0..8) the eight labels (a narrow set padded with its first entry)
+//   ranges  w[0..4) lo, w[4..8) span = hi - lo (an empty interval replaced by the first non-empty one)
+//   masks   w[0..3) / w[3..6) the two clauses (mask, value, any), a single clause repeated
+//   w[8]    kBfPredWildcard: the set holds a -1 (every label passes);  kBfPredClosed: every interval
+//           is empty (no row passes)
+// The family is uniform over the launch (pred_family).  The filter table is filter_bits /
+// filter_table of the base struct (ids null: no table), a multiple of 32 as the bit offset.
+constexpr uint32_t kBfPredWords = 9;
+constexpr uint32_t kBfPredWildcard = 1u, kBfPredClosed = 2u;
+constexpr uint32_t kBfPredSets = 0, kBfPredRanges = 1, kBfPredMasks = 2;
+struct BfMfmaPredArgs : BfMfmaFilteredArgs {
+  const int32_t* pred_labels;    // the label column at the first global id of this base
+  const uint32_t* pred_records;  // [Nq][kBfPredWords]
+  uint32_t pred_family;          // kBfPredSets | kBfPredRanges | kBfPredMasks
+};
 template <int FM>
-using BfMfmaArgsOf = std::conditional_t<FM != kBfNoFilter, BfMfmaFilteredArgs, BfMfmaArgs>;
+using BfMfmaArgsOf =
+    std::conditional_t<FM == kBfPredicate, BfMfmaPredArgs,
+                       std::conditional_t<FM != kBfNoFilter, BfMfmaFilteredArgs, BfMfmaArgs>>;
 // LDS words behind the thresholds (single chunk) / the group norms (chunked) of a filtered kernel
 //   kBfBits    verdict words of the block's 128 queries: [2][128], chunked [2][T][128]
 //   kBfLabels  128 query labels; chunked: + [2][T][32] row labels beside the group norms
+//   kBfPredicate  the verdict words of kBfBits, then the 128 predicate records of the block
 constexpr uint32_t bf_filter_lds_words(int fm, uint32_t T)
 {
   return fm == kBfBits     ? 2u * T * kBfQueriesPerBlock
          : fm == kBfLabels ? kBfQueriesPerBlock + (T > 1 ? 2u * T * kBfTileRows : 0u)
-                           : 0u;
+         : fm == kBfPredicate
+             ? 2u * T * kBfQueriesPerBlock + kBfPredWords * kBfQueriesPerBlock
+             : 0u;
 }
 // The filtered SINGLE-CHUNK kernels exist with the list length as a compile-time constant only
 // (KPC = 18: k <= 10, shorter lists are rounded up -- any list longer than k is exact).  With a
@@ -75,6 +101,7 @@ constexpr bool bf_filtered_runs_chunked(uint32_t D, uint32_t k_query)
 // the filtered tile kernel of a launch (defined in the filtered translation units)
 const void* bf_mfma_bits_kernel(ggnn_dtype dtype, ggnn_measure measure, int T, int NU, int KPC);
 const void* bf_mfma_labels_kernel(ggnn_dtype dtype, ggnn_measure measure, int T, int NU, int KPC);
+const void* bf_mfma_pred_kernel(ggnn_dtype dtype, ggnn_measure measure, int T, int NU, int KPC);
 
 // bf_mfma.hip: the shift of float32 squared L2 -- mean[D] = column mean of (a sample of) the base,
 // q_shifted = fl(query - mean); partial is kBfMeanBlocks x D floats of scratch

@@ -35,7 +35,8 @@
 //   uint8 rows on the i8 path: every quantity is an exact integer < 2^24, a left-out row is
 //   preceded by KP > K rows of its own slice in exact (distance, index) order: nothing to check.
 //
-// Under a filter (FM = kBfBits / kBfLabels: a bitset row or a label per query, FilterStage below)
+// Under a filter (FM = kBfBits / kBfLabels / kBfPredicate: a bitset row, a label or a label
+// predicate per query, FilterStage below)
 //   A (query, row) pair the filter denies gets d_e = +inf before the threshold ballot, nothing
 //   else changes: the lists keep the KP smallest ALLOWED (d_e, index).  The certificate holds as
 //   it stands:
@@ -48,6 +49,11 @@
 //       launch_bf_rescan forwards the launch's filter with the query list, and a re-scanned query
 //       picks its filter by its real index qlist[i], not by its position i).
 //   Filtered launches that keep the scan: launch_bf_query (bf_query.hip).
+//   FM = kBfPredicate (label sets, label ranges, label masks, with or without a filter table) makes
+//   the same verdict word as kBfBits, inside the kernel, from the label column and the query's record:
+//   a denied pair gets d_e = +inf at the same place, so every point above holds unchanged, and the
+//   queries without a certificate go to the scan kernels of their family with the query list
+//   (bf_query_labelset.hip, bf_query_labelrange.hip, bf_query_labelmask.hip through launch_bf_rescan).
 #include <cstdlib>
 
 #include "bf_common.hpp"
@@ -773,6 +779,133 @@ GGNN_DEV bool bf_label_denied(int32_t ql, int32_t row_label)
 {
   return ql != -1 && ql != row_label;
 }
+// kBfPredicate: the verdict word of kBfBits, made inside the kernel from the label column.  One stage
+// for label sets, label ranges and label masks: the family is uniform over the launch, a switch in
+// the staging code, outside the MFMA chain.
+//   open   thread t < 128 copies the record of query t of the block (BfMfmaPredArgs, bf_common.hpp)
+//          to LDS, behind the verdict words -- nine words a thread would otherwise hold across the
+//          MFMA chain --, and every thread takes the filter id of query t & 127
+//   load   the label of tile row t & 31 and, from the table row the id names, the word of the tile,
+//          with the tile's own loads (unconditional, clamped to the last row, like the norm)
+//   store  the two halves of the workgroup evaluate 16 of the tile's 32 rows each for query t & 127:
+//          the label of row i comes out of lane i of `lab` as a wave-uniform scalar (v_readlane: the
+//          half is wave-uniform), is compared against the thread's record with the chains of
+//          denied_lanes() / passes() (traversal.hpp), and the 16 verdicts ANDed with the thread's
+//          half of the table word are one 16-bit store into the verdict word.  No atomic, and no
+//          barrier beyond the tile's own.
+// Labels, bounds and masks are compared, never used as an index; a filter id forms an address only
+// after the unsigned compare against the table's size.
+template <>
+struct FilterStage<kBfPredicate> {
+  // Across the MFMA chain a thread holds three registers, as many as under kBfBits: the filter id
+  // (the row pointer is formed again at every load -- a 64-bit pointer held instead made the f32
+  // T = 3 and NU = 16 kernels spill), the table word and the label.
+  int32_t fid;       // filter id of query threadIdx.x & 127 (with a table)
+  uint32_t w;        // its row's word of the tile (no table: all ones)
+  int32_t lab;       // label of tile row threadIdx.x & 31
+  uint32_t family;   // (launch-uniform)
+  uint32_t rec_off;  // words from the verdict area to the records (a constant of the kernel)
+  GGNN_DEV void open(const BfMfmaPredArgs& a, uint32_t qblock, uint32_t* filt, uint32_t rec_off_)
+  {
+    const uint32_t ql = threadIdx.x & 127u;
+    // (padding queries read the predicate of the last query: nothing ever enters their lists)
+    const uint32_t q = min(qblock * kBfQueriesPerBlock + ql, a.Nq - 1);
+    family = a.pred_family;
+    rec_off = rec_off_;
+    if (threadIdx.x < (uint32_t)kBfQueriesPerBlock) {
+#pragma unroll
+      for (uint32_t k = 0; k < kBfPredWords; ++k)
+        filt[rec_off + ql * kBfPredWords + k] =
+            a.pred_records[static_cast<size_t>(q) * kBfPredWords + k];
+    }
+    fid = -1;
+    if (a.filter_table.ids)
+      fid = a.filter_table.ids[q];
+  }
+  // (row0 >= end: a group's padding tile re-reads the last row)
+  GGNN_DEV void load(const BfMfmaPredArgs& a, uint32_t row0, uint32_t end)
+  {
+    lab = a.pred_labels[min(row0 + (threadIdx.x & 31u), end - 1)];
+    w = ~0u;
+    const FilterTable& t = a.filter_table;
+    if (t.ids) {
+      // the row as bf_thread_filter_row() picks it: an UNSIGNED compare, the all-ones row for -1,
+      // the all-zero row for every other id outside the table
+      const uint32_t* c = t.consts + (fid == -1 ? 0u : t.words);
+      const uint32_t* row =
+          static_cast<uint32_t>(fid) < t.num_filters
+              ? a.filter_bits + static_cast<size_t>(static_cast<uint32_t>(fid)) * t.words
+              : c;
+      w = row[(min(row0, end - 1) + a.filter_bit_offset) >> 5];
+    }
+  }
+  // the 16 verdicts of this thread's query for tile rows [16 half, 16 half + 16)
+  GGNN_DEV uint32_t verdicts(const uint32_t* filt, const uint32_t half) const
+  {
+    // (the opaque zero keeps the record reads at the store, as in TileStage<float>::store_shifted:
+    // hoisted out of the tile loop they are nine registers held across the MFMA chain)
+    uint32_t opaque = 0;
+    asm volatile("" : "+v"(opaque));
+    const uint32_t* rec = filt + opaque + rec_off + (threadIdx.x & 127u) * kBfPredWords;
+    uint32_t r[kBfPredWords];
+#pragma unroll
+    for (uint32_t k = 0; k < kBfPredWords; ++k)
+      r[k] = rec[k];
+    // (the row loops stay rolled: unrolled, the scalars of the read lanes and of the compare chains
+    // cost the f32 kernels at NU = 16 and T = 3 a private segment)
+    uint32_t bits = 0u;
+    if (family == kBfPredSets) {
+      const bool wildcard = (r[8] & kBfPredWildcard) != 0u;
+#pragma unroll 1
+      for (int i = 0; i < 16; ++i) {
+        const uint32_t s = static_cast<uint32_t>(
+            __builtin_amdgcn_readlane(lab, static_cast<int>(16u * half) + i));
+        bool one = wildcard;
+#pragma unroll
+        for (uint32_t j = 0; j < kMaxLabelSet; ++j)
+          one = one | (s == r[j]);
+        bits |= one ? 1u << i : 0u;
+      }
+    }
+    else if (family == kBfPredRanges) {
+#pragma unroll 1
+      for (int i = 0; i < 16; ++i) {
+        const uint32_t s = static_cast<uint32_t>(
+            __builtin_amdgcn_readlane(lab, static_cast<int>(16u * half) + i));
+        bool none = true;
+#pragma unroll
+        for (uint32_t j = 0; j < kMaxLabelRanges; ++j)
+          none = none & ((s - r[j]) > r[kMaxLabelRanges + j]);
+        bits |= none ? 0u : 1u << i;
+      }
+    }
+    else {
+#pragma unroll 1
+      for (int i = 0; i < 16; ++i) {
+        const uint32_t s = static_cast<uint32_t>(
+            __builtin_amdgcn_readlane(lab, static_cast<int>(16u * half) + i));
+        bool one = false;
+#pragma unroll
+        for (uint32_t j = 0; j < kMaxLabelMasks; ++j)
+          one = one | (((s & r[3 * j]) == r[3 * j + 1]) &
+                       (((s & r[3 * j + 2]) != 0u) | (r[3 * j + 2] == 0u)));
+        bits |= one ? 1u << i : 0u;
+      }
+    }
+    bits = (r[8] & kBfPredClosed) ? 0u : bits;
+    return bits & (w >> (16u * half));
+  }
+  GGNN_DEV void store_group(uint32_t* filt, uint32_t slot) const
+  {
+    const uint32_t half = __builtin_amdgcn_readfirstlane(threadIdx.x >> 7);
+    reinterpret_cast<uint16_t*>(filt)[(slot * kBfQueriesPerBlock + (threadIdx.x & 127u)) * 2u + half] =
+        static_cast<uint16_t>(verdicts(filt, half));
+  }
+  GGNN_DEV void store_single(float*, uint32_t, uint32_t, uint32_t* filt, uint32_t buf) const
+  {
+    store_group(filt, buf);
+  }
+};
 
 #ifdef GGNN_BF_SHARED_ONLY
 }  // namespace ggnn_amd
@@ -897,7 +1030,11 @@ __global__ void __launch_bounds__(256)
             qi < a.Nq ? a.filter_table.query_labels[qi] : -1;
     }
   }
-  fstage.open(a, qblock);
+  // (kBfPredicate: the block's records go behind the verdict words)
+  if constexpr (FM == kBfPredicate)
+    fstage.open(a, qblock, filt_lds, 2 * T * kBfQueriesPerBlock);
+  else
+    fstage.open(a, qblock);
   __syncthreads();
   const uint32_t ntiles = (end > begin) ? (end - begin + kBfTileRows - 1) / kBfTileRows : 0;
   if (ntiles) {
@@ -972,7 +1109,7 @@ __global__ void __launch_bounds__(256)
         dd[4 * g + 2] = bf_expand<MODE>(acc[4 * g + 2], qn4.z, bn, jvalid);
         dd[4 * g + 3] = bf_expand<MODE>(acc[4 * g + 3], qn4.w, bn, jvalid);
         // the verdicts of the lane's four query rows of this group, read like qn4 / th4
-        if constexpr (FM == kBfBits) {
+        if constexpr (FM == kBfBits || FM == kBfPredicate) {
           const uint4 fw4 = *reinterpret_cast<const uint4*>(
               filt_lds + (tt & 1) * kBfQueriesPerBlock + wave * 32 + 8 * g + 4 * h);
           dd[4 * g + 0] = ((fw4.x >> j) & 1u) ? dd[4 * g + 0] : inf_f();
@@ -1132,7 +1269,7 @@ __global__ void __launch_bounds__(256)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         dd[r] = bf_expand<MODE>(acc[t][r], qn2[r], bn, jvalid);
-        if constexpr (FM == kBfBits) {
+        if constexpr (FM == kBfBits || FM == kBfPredicate) {
           const uint32_t fw = filt_lds[(((g0 / T) & 1) * T + t) * kBfQueriesPerBlock + wave * 32 +
                                        (r & 3) + 8 * (r >> 2) + 4 * h];
           dd[r] = ((fw >> j) & 1u) ? dd[r] : inf_f();
@@ -1431,7 +1568,8 @@ __global__ void __launch_bounds__(kWave) bf_rerank_kernel(const BfRerankArgs a)
 }
 
 #ifdef GGNN_BF_FILTER_TU
-// ---- the filtered instantiations of this translation unit (bf_mfma_bits.hip, bf_mfma_labels.hip) --
+// ---- the filtered instantiations of this translation unit (bf_mfma_bits.hip, bf_mfma_labels.hip,
+// bf_mfma_pred.hip) ----------------------------------------------------------------------------------
 template <typename BaseT, int MODE>
 static const void* bf_filtered_kernel_of(int T, int NU, int KPC)
 {
@@ -1453,6 +1591,8 @@ static const void* bf_filtered_kernel_of(int T, int NU, int KPC)
 }
 #if GGNN_BF_FILTER_TU == 1
 const void* bf_mfma_bits_kernel(ggnn_dtype dtype, ggnn_measure measure, int T, int NU, int KPC)
+#elif GGNN_BF_FILTER_TU == 3
+const void* bf_mfma_pred_kernel(ggnn_dtype dtype, ggnn_measure measure, int T, int NU, int KPC)
 #else
 const void* bf_mfma_labels_kernel(ggnn_dtype dtype, ggnn_measure measure, int T, int NU, int KPC)
 #endif
@@ -1479,10 +1619,122 @@ const void* bf_mfma_labels_kernel(ggnn_dtype dtype, ggnn_measure measure, int T,
 
 }  // namespace ggnn_amd
 #else  // GGNN_BF_FILTER_TU
+// ---- the records of FilterStage<kBfPredicate> ----------------------------------------------------
+// One thread per query does once what the constructors of LabelSetFilter, LabelRangeFilter and
+// LabelMaskFilter (traversal.hpp) do once per wave; the record layout is BfMfmaPredArgs's
+// (bf_common.hpp).  Every value read here is stored or compared, none forms an address.
+struct BfPredPrepArgs {
+  LabelSetSpec sets;
+  LabelRangeSpec ranges;
+  LabelMaskSpec masks;
+  uint32_t family, Nq;
+  uint32_t* records;  // [Nq][kBfPredWords]
+};
+__global__ void __launch_bounds__(256) bf_pred_prep_kernel(const BfPredPrepArgs a)
+{
+  const uint32_t n = blockIdx.x * 256 + threadIdx.x;
+  if (n >= a.Nq)
+    return;
+  uint32_t w[kBfPredWords];
+#pragma unroll
+  for (uint32_t k = 0; k < kBfPredWords; ++k)
+    w[k] = 0u;
+  if (a.family == kBfPredSets) {
+    // a narrow set is padded with its first entry; an entry -1 admits every label
+    const int32_t* set = a.sets.sets + static_cast<size_t>(n) * a.sets.width;
+    bool wildcard = false;
+#pragma unroll
+    for (uint32_t j = 0; j < kMaxLabelSet; ++j) {
+      const int32_t L = set[j < a.sets.width ? j : 0u];
+      wildcard = wildcard || L == -1;
+      w[j] = static_cast<uint32_t>(L);
+    }
+    w[8] = wildcard ? kBfPredWildcard : 0u;
+  }
+  else if (a.family == kBfPredRanges) {
+    // lo and span = hi - lo; an empty interval (lo > hi) and the padding of a short list become the
+    // first non-empty interval; a query whose intervals are all empty is closed
+    const int32_t* r = a.ranges.ranges + static_cast<size_t>(n) * a.ranges.n_ranges * 2;
+    bool valid[kMaxLabelRanges];
+    bool any = false;
+    uint32_t lo0 = 0u, span0 = 0u;
+#pragma unroll
+    for (uint32_t j = 0; j < kMaxLabelRanges; ++j) {
+      const uint32_t jj = j < a.ranges.n_ranges ? j : 0u;
+      const int32_t l = r[2 * jj], h = r[2 * jj + 1];
+      valid[j] = l <= h;
+      w[j] = static_cast<uint32_t>(l);
+      w[kMaxLabelRanges + j] = static_cast<uint32_t>(h) - static_cast<uint32_t>(l);
+      if (valid[j] && !any) {
+        lo0 = w[j];
+        span0 = w[kMaxLabelRanges + j];
+        any = true;
+      }
+    }
+#pragma unroll
+    for (uint32_t j = 0; j < kMaxLabelRanges; ++j) {
+      w[j] = valid[j] ? w[j] : lo0;
+      w[kMaxLabelRanges + j] = valid[j] ? w[kMaxLabelRanges + j] : span0;
+    }
+    w[8] = any ? 0u : kBfPredClosed;
+  }
+  else {
+    // (mask, value, any) as given -- value is never pre-masked --, a single clause repeated
+    const int32_t* c = a.masks.masks + static_cast<size_t>(n) * a.masks.n_masks * 3;
+#pragma unroll
+    for (uint32_t j = 0; j < kMaxLabelMasks; ++j) {
+      const uint32_t jj = j < a.masks.n_masks ? j : 0u;
+#pragma unroll
+      for (uint32_t e = 0; e < 3; ++e)
+        w[3 * j + e] = static_cast<uint32_t>(c[3 * jj + e]);
+    }
+  }
+#pragma unroll
+  for (uint32_t k = 0; k < kBfPredWords; ++k)
+    a.records[static_cast<size_t>(n) * kBfPredWords + k] = w[k];
+}
+
 // ---- host ---------------------------------------------------------------------------------------
+static bool bf_has_predicate(const BfLaunch& a)
+{
+  return a.label_sets.labels || a.label_ranges.labels || a.label_masks.labels;
+}
 static int bf_filter_mode(const BfLaunch& a)
 {
+  if (bf_has_predicate(a))
+    return kBfPredicate;
   return !a.filter_bits ? kBfNoFilter : a.filter_table.query_labels ? kBfLabels : kBfBits;
+}
+
+// A launch under a label predicate (label sets, label ranges or label masks) that the float tile
+// kernels answer.  Hook BF_LABEL_TILES: 1 never (the scan kernels of bf_query_labelset.hip,
+// bf_query_labelrange.hip, bf_query_labelmask.hip: every such launch before these kernels), 2 whenever the launch is
+// supported, 0 auto -- batches of at least 10000 queries over at least 1M rows, the class measured
+// against the scan; smaller launches keep the scan.  A launch that breaks a rule of
+// its spec goes to its scan launcher, which reports it.  (The table's bit offset is a multiple of 32,
+// as under kBfBits; without a table the offset places the label window only and may be anything.)
+bool bf_mfma_uses_i8(const BfLaunch& a);
+bool bf_mfma_supported(const BfLaunch& a);
+bool bf_label_tiles_routes(const BfLaunch& a)
+{
+  const int64_t mode = hook(kHookBfLabelTiles);
+  if (mode == 1 || hook(kHookBfScan) == 1 || !bf_has_predicate(a))
+    return false;
+  const LabelSetSpec& s = a.label_sets;
+  const LabelRangeSpec& r = a.label_ranges;
+  const LabelMaskSpec& m = a.label_masks;
+  const bool spec_ok = m.labels   ? m.masks && m.n_masks >= 1 && m.n_masks <= kMaxLabelMasks
+                       : r.labels ? r.ranges && r.n_ranges >= 1 && r.n_ranges <= kMaxLabelRanges
+                                  : s.sets && s.width >= 1 && s.width <= kMaxLabelSet;
+  const FilterTable& t = a.filter_table;
+  // filter ids come with their table (ids without one keep the scan and its constant words)
+  const bool table_ok = !t.ids || (a.filter_bits && t.words && t.num_filters);
+  if (!spec_ok || !table_ok || t.query_labels || a.dtype == GGNN_I8 || bf_mfma_uses_i8(a) ||
+      (t.ids && a.filter_bit_offset % 32 != 0) || a.N_base > kMaxLabeledShardRows ||
+      static_cast<uint64_t>(a.filter_bit_offset) + a.N_base > 0xffffffffull || a.k_query < 1 ||
+      !bf_mfma_supported(a))
+    return false;
+  return mode == 2 || (a.Nq >= 10000 && a.N_base >= 1000000);
 }
 
 // uint8 / int8 + squared L2 with rows of up to 128 bytes: the integer kernels (no filtered form)
@@ -1756,7 +2008,8 @@ void launch_bf_query_mfma(const BfLaunch& a, hipStream_t stream)
 {
   check_vector_layout(a.base, a.D, a.dtype);
   check_vector_layout(a.query, a.D, a.dtype);
-  if (bf_i8_wide_routes(a)) {
+  // (a label predicate without a table has no filter_bits: not an unfiltered launch all the same)
+  if (!bf_has_predicate(a) && bf_i8_wide_routes(a)) {
     launch_bf_query_i8_wide(a, stream);
     return;
   }
@@ -1852,8 +2105,10 @@ void launch_bf_query_mfma(const BfLaunch& a, hipStream_t stream)
   // chunked float kernel: the query set once more, in operand order (QueryWindow)
   const uint32_t pack_chunks = (!use_i8 && chunked) ? (a.D + 127) / 128 : 0;
   const size_t n_qpack = static_cast<size_t>(qblocks) * kBfQueriesPerBlock * pack_chunks * 128;
+  // kBfPredicate: one record per query (bf_pred_prep_kernel)
+  const size_t n_pred = fm == kBfPredicate ? pad4(static_cast<size_t>(a.Nq) * kBfPredWords) : 0;
   const size_t words = n_norms + n_mean + n_partial + 4 + n_list + 2 * n_parts + 2 * n_rescan +
-                       pad4(n_qshift) + n_gthr + n_qpack;
+                       pad4(n_qshift) + n_gthr + n_qpack + n_pred;
   float* scratch = static_cast<float*>(scratch_alloc(words * 4, stream));
   float* bnorm = scratch;
   float* qnorm = bnorm + a.N_base;
@@ -1868,6 +2123,7 @@ void launch_bf_query_mfma(const BfLaunch& a, hipStream_t stream)
   float* q_shifted = rescan_dists + n_rescan;
   uint32_t* gthr = reinterpret_cast<uint32_t*>(q_shifted + pad4(n_qshift));
   float* q_packed = reinterpret_cast<float*>(gthr + n_gthr);
+  uint32_t* pred_records = reinterpret_cast<uint32_t*>(q_packed + n_qpack);
   GGNN_HIP_CHECK(hipMemsetAsync(flags, 0, 4 * sizeof(uint32_t), stream));
   if (use_i8v2)  // "nothing published"
     GGNN_HIP_CHECK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(gthr), 0x7fffffff, n_gthr,
@@ -1954,7 +2210,33 @@ void launch_bf_query_mfma(const BfLaunch& a, hipStream_t stream)
   const void* f_kern = fm == kBfBits ? bf_mfma_bits_kernel(a.dtype, a.measure, tiles_per_group, f_nu, f_kpc)
                        : fm == kBfLabels
                            ? bf_mfma_labels_kernel(a.dtype, a.measure, tiles_per_group, f_nu, f_kpc)
+                       : fm == kBfPredicate
+                           ? bf_mfma_pred_kernel(a.dtype, a.measure, tiles_per_group, f_nu, f_kpc)
                            : nullptr;
+  // kBfPredicate: the records of the launch's family, the label window, and the two constant rows
+  // of a table that brings none (made in stream-ordered scratch, as launch_bf_query makes them)
+  BfMfmaPredArgs mp{};
+  ScratchGuard pred_consts{fm == kBfPredicate ? filter_consts_scratch(a.filter_table, stream) : nullptr,
+                           stream};
+  if (fm == kBfPredicate) {
+    static_cast<BfMfmaFilteredArgs&>(mp) = mf;
+    if (pred_consts.p)
+      mp.filter_table.consts = static_cast<const uint32_t*>(pred_consts.p);
+    BfPredPrepArgs pp{};
+    pp.sets = a.label_sets;
+    pp.ranges = a.label_ranges;
+    pp.masks = a.label_masks;
+    pp.family = a.label_masks.labels ? kBfPredMasks : a.label_ranges.labels ? kBfPredRanges : kBfPredSets;
+    pp.Nq = a.Nq;
+    pp.records = pred_records;
+    hipLaunchKernelGGL(bf_pred_prep_kernel, dim3((a.Nq + 255) / 256), dim3(256), 0, stream, pp);
+    const int32_t* column = a.label_masks.labels    ? a.label_masks.labels
+                            : a.label_ranges.labels ? a.label_ranges.labels
+                                                    : a.label_sets.labels;
+    mp.pred_labels = column + a.filter_bit_offset;
+    mp.pred_records = pred_records;
+    mp.pred_family = pp.family;
+  }
 
   BfRerankArgs rr{};
   rr.base = a.base;
@@ -1996,7 +2278,9 @@ void launch_bf_query_mfma(const BfLaunch& a, hipStream_t stream)
     if (lds > 64 * 1024)                                                                          \
       GGNN_HIP_CHECK(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize,        \
                                          static_cast<int>(lds)));                                 \
-    void* kargs[] = {f_kern ? static_cast<void*>(&mf) : static_cast<void*>(&m)};                 \
+    void* kargs[] = {fm == kBfPredicate ? static_cast<void*>(&mp)                                 \
+                     : f_kern           ? static_cast<void*>(&mf)                                 \
+                                        : static_cast<void*>(&m)};                                \
     const dim3 grid = equal_ranges ? dim3(nblocks) : dim3(qblocks, slices);                       \
     GGNN_HIP_CHECK(hipLaunchKernel(kern, grid, dim3(256), kargs, lds, stream));                   \
   } while (0)

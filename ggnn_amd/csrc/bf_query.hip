@@ -338,6 +338,17 @@ bool bf_mfma_uses_i8(const BfLaunch& a);
 void launch_bf_query_labelset(const BfLaunch& a, hipStream_t stream);  // bf_query_labelset.hip
 void launch_bf_query_labelrange(const BfLaunch& a, hipStream_t stream);  // bf_query_labelrange.hip
 void launch_bf_query_labelmask(const BfLaunch& a, hipStream_t stream);  // bf_query_labelmask.hip
+// ... and their scans of the subset qlist[0, *qcount) in given slices (tmp_*: [slices x Nq x K])
+void launch_bf_scan_labelset(const BfLaunch& a, uint32_t slices, uint32_t rows_per_slice,
+                             const uint32_t* qlist, const uint32_t* qcount, int32_t* tmp_ids,
+                             float* tmp_dists, hipStream_t stream);
+void launch_bf_scan_labelrange(const BfLaunch& a, uint32_t slices, uint32_t rows_per_slice,
+                               const uint32_t* qlist, const uint32_t* qcount, int32_t* tmp_ids,
+                               float* tmp_dists, hipStream_t stream);
+void launch_bf_scan_labelmask(const BfLaunch& a, uint32_t slices, uint32_t rows_per_slice,
+                              const uint32_t* qlist, const uint32_t* qcount, int32_t* tmp_ids,
+                              float* tmp_dists, hipStream_t stream);
+bool bf_label_tiles_routes(const BfLaunch& a);  // bf_mfma.hip
 void launch_bf_query_mfma(const BfLaunch& a, hipStream_t stream);
 void launch_bf_query_f16(const BfLaunch& a, hipStream_t stream);  // bf_f16.hip
 
@@ -409,7 +420,15 @@ void launch_bf_rescan(const BfLaunch& a, const uint32_t* qlist, const uint32_t* 
   uint32_t slices = 0, rows = 0;
   (void)bf_rescan_tmp_entries(a, &slices);
   bf_slice_rows(a.N_base, slices, rows);
-  launch_bf_scan(a, slices, rows, qlist, qcount, tmp_ids, tmp_dists, stream);
+  // a launch under a label predicate: the scan of its family, each query under its own predicate
+  if (a.label_masks.labels)
+    launch_bf_scan_labelmask(a, slices, rows, qlist, qcount, tmp_ids, tmp_dists, stream);
+  else if (a.label_ranges.labels)
+    launch_bf_scan_labelrange(a, slices, rows, qlist, qcount, tmp_ids, tmp_dists, stream);
+  else if (a.label_sets.labels)
+    launch_bf_scan_labelset(a, slices, rows, qlist, qcount, tmp_ids, tmp_dists, stream);
+  else
+    launch_bf_scan(a, slices, rows, qlist, qcount, tmp_ids, tmp_dists, stream);
 }
 
 void launch_bf_query(const BfLaunch& a_in, hipStream_t stream)
@@ -420,7 +439,16 @@ void launch_bf_query(const BfLaunch& a_in, hipStream_t stream)
     *a_in.matrix_path = 0;
   if (a_in.Nq == 0)
     return;
-  // label masks, label ranges, label sets: scan kernels of their own, no matrix-core form
+  // label masks, label ranges, label sets: large batches run the float tile kernels under a
+  // predicate stage (bf_mfma.hip: FilterStage<kBfPredicate>; bf_label_tiles_routes says which, hook
+  // BF_LABEL_TILES); scan kernels of their own answer the rest, and the queries the tile kernels
+  // could not certify
+  if (bf_label_tiles_routes(a_in)) {
+    launch_bf_query_mfma(a_in, stream);
+    if (a_in.matrix_path)
+      *a_in.matrix_path = 1;
+    return;
+  }
   if (a_in.label_masks.labels) {
     launch_bf_query_labelmask(a_in, stream);
     return;

@@ -5,8 +5,9 @@
 //
 // Kernel templates of their own -- the scan of bf_query_kernel / bf_query_lds_kernel word for word,
 // with TWO coalesced words per batch of 64 rows in front of the rows: the row's label and its word of
-// the bitset.  A denied row's distance becomes +inf before the ballot.  There is no matrix-core form:
-// every label-mask call scans.
+// the bitset.  A denied row's distance becomes +inf before the ballot.  Large batches run the
+// float tile kernels instead (bf_mfma.hip: FilterStage<kBfPredicate>, hook BF_LABEL_TILES); this scan
+// answers the rest, and the queries those kernels could not certify (qlist).
 #include <cstdlib>
 
 #include "hooks.hpp"
@@ -24,6 +25,10 @@ struct BfLabelMaskArgs {
   uint32_t filter_bit_offset;   // first global id of this base, in the table and in the column
   FilterTable filter_table;
   LabelMaskSpec mask;
+  // optional subset, as in BfArgs: only the queries qlist[0, *qcount) are scanned (device memory;
+  // the grid is sized for all Nq queries and the surplus blocks leave at once)
+  const uint32_t* qlist;
+  const uint32_t* qcount;
 };
 
 // the predicate of one (query, slice) wave: scalar, set up once (LabelMaskFilter's constructor)
@@ -95,8 +100,14 @@ __global__ void __launch_bounds__(kWave) bf_query_labelmask_kernel(const BfLabel
   const uint32_t bid = block_linear_index();
   if (bid >= a.Nq * a.slices)
     return;
-  const uint32_t n = bid / a.slices;
+  uint32_t n = bid / a.slices;
   const uint32_t slice = bid % a.slices;
+  // (a listed query picks its clauses and its filter id by its real index, like its row and its output)
+  if (a.qlist) {
+    if (n >= *a.qcount)
+      return;
+    n = a.qlist[n];
+  }
   const BaseT* base = static_cast<const BaseT*>(a.base);
   const BaseT* query = static_cast<const BaseT*>(a.query);
 
@@ -159,8 +170,13 @@ __global__ void __launch_bounds__(kWave) bf_query_labelmask_lds_kernel(const BfL
   const uint32_t bid = block_linear_index();
   if (bid >= a.Nq * a.slices)
     return;
-  const uint32_t n = bid / a.slices;
+  uint32_t n = bid / a.slices;
   const uint32_t slice = bid % a.slices;
+  if (a.qlist) {
+    if (n >= *a.qcount)
+      return;
+    n = a.qlist[n];
+  }
   const BaseT* base = static_cast<const BaseT*>(a.base);
   DE de;
   de.template load_query<MODE>(base, a.D,
@@ -234,6 +250,50 @@ static void launch_bf_labelmask_r(const BfLabelMaskArgs& args, hipStream_t strea
 
 void bf_slice_rows(uint32_t N_base, uint32_t& slices, uint32_t& rows_per_slice);
 
+// the scan of all queries (qlist == nullptr) or of the subset qlist[0, *qcount) -- the queries the
+// tile kernels of bf_mfma.hip could not certify (launch_bf_rescan, bf_query.hip); slices > 1 needs
+// tmp_ids / tmp_dists of [slices x Nq x K] entries
+void launch_bf_scan_labelmask(const BfLaunch& a, uint32_t slices, uint32_t rows_per_slice,
+                              const uint32_t* qlist, const uint32_t* qcount, int32_t* tmp_ids,
+                              float* tmp_dists, hipStream_t stream)
+{
+  BfLabelMaskArgs args{};
+  args.base = a.base;
+  args.query = a.query;
+  args.D = a.D;
+  args.Nq = a.Nq;
+  args.N_base = a.N_base;
+  args.K = a.k_query;
+  args.slices = slices;
+  args.rows_per_slice = rows_per_slice;
+  args.filter_bits = a.filter_bits;
+  args.filter_bit_offset = a.filter_bit_offset;
+  args.filter_table = a.filter_table;
+  args.mask = a.label_masks;
+  args.qlist = qlist;
+  args.qcount = qcount;
+  args.ids = slices > 1 ? tmp_ids : a.ids;
+  args.dists = slices > 1 ? tmp_dists : a.dists;
+
+#define GGNN_LAUNCH_BF(T, LPR, NCH)                            \
+  do {                                                         \
+    if (a.measure == GGNN_EUCLIDEAN)                           \
+      launch_bf_labelmask_r<T, LPR, NCH, kL2>(args, stream);    \
+    else                                                       \
+      launch_bf_labelmask_r<T, LPR, NCH, kCos>(args, stream);   \
+  } while (0)
+  if (dtype_is_16bit(a.dtype))
+    GGNN_DISPATCH_DIST_16(a.dtype, a.D, GGNN_LAUNCH_BF);
+  else
+    GGNN_DISPATCH_DIST_32_8(a.dtype, a.D, GGNN_LAUNCH_BF);
+#undef GGNN_LAUNCH_BF
+  GGNN_HIP_CHECK(hipGetLastError());
+  if (slices > 1)
+    // slices are in ascending base order, so "lower part first" on ties keeps Q2
+    launch_merge_results_subset(a.Nq, a.k_query, slices, a.k_query, 0, tmp_ids, tmp_dists, a.ids,
+                                a.dists, qlist, qcount, stream);
+}
+
 // launch_bf_query (bf_query.hip) of a launch with label masks
 void launch_bf_query_labelmask(const BfLaunch& a, hipStream_t stream)
 {
@@ -273,41 +333,9 @@ void launch_bf_query_labelmask(const BfLaunch& a, hipStream_t stream)
     tmp_dists = reinterpret_cast<float*>(tmp_ids + part);
   }
 
-  BfLabelMaskArgs args{};
-  args.base = a.base;
-  args.query = a.query;
-  args.D = a.D;
-  args.Nq = a.Nq;
-  args.N_base = a.N_base;
-  args.K = a.k_query;
-  args.slices = slices;
-  args.rows_per_slice = rows_per_slice;
-  args.filter_bits = a.filter_bits;
-  args.filter_bit_offset = a.filter_bit_offset;
-  args.filter_table = a.filter_table;
-  args.mask = mask;
-  args.ids = slices > 1 ? tmp_ids : a.ids;
-  args.dists = slices > 1 ? tmp_dists : a.dists;
-
-#define GGNN_LAUNCH_BF(T, LPR, NCH)                            \
-  do {                                                         \
-    if (a.measure == GGNN_EUCLIDEAN)                           \
-      launch_bf_labelmask_r<T, LPR, NCH, kL2>(args, stream);    \
-    else                                                       \
-      launch_bf_labelmask_r<T, LPR, NCH, kCos>(args, stream);   \
-  } while (0)
-  if (dtype_is_16bit(a.dtype))
-    GGNN_DISPATCH_DIST_16(a.dtype, a.D, GGNN_LAUNCH_BF);
-  else
-    GGNN_DISPATCH_DIST_32_8(a.dtype, a.D, GGNN_LAUNCH_BF);
-#undef GGNN_LAUNCH_BF
-  GGNN_HIP_CHECK(hipGetLastError());
-  if (slices > 1) {
-    // slices are in ascending base order, so "lower part first" on ties keeps Q2
-    launch_merge_results_subset(a.Nq, a.k_query, slices, a.k_query, 0, tmp_ids, tmp_dists, a.ids,
-                                a.dists, nullptr, nullptr, stream);
+  launch_bf_scan_labelmask(a, slices, rows_per_slice, nullptr, nullptr, tmp_ids, tmp_dists, stream);
+  if (slices > 1)
     GGNN_HIP_CHECK(hipFreeAsync(tmp_ids, stream));
-  }
 }
 
 }  // namespace ggnn_amd

@@ -274,11 +274,12 @@ struct BfLaunch {
   // kernels of bf_f16.hip, 0 if it ran the scan -- decided on the host before anything is enqueued;
   // results are bit-identical either way
   int* matrix_path{nullptr};
-  // label-set filters (labels != nullptr: see LabelSetSpec); always the scan
+  // label-set, label-range and label-mask filters (labels != nullptr: see LabelSetSpec,
+  // LabelRangeSpec, LabelMaskSpec): the float tile kernels under a predicate stage where
+  // bf_label_tiles_routes (bf_mfma.hip, hook BF_LABEL_TILES) opens them -- matrix_path 1 --, else the
+  // scan kernels of the family
   LabelSetSpec label_sets{};
-  // label-range filters (labels != nullptr: see LabelRangeSpec); always the scan
   LabelRangeSpec label_ranges{};
-  // label-mask filters (labels != nullptr: see LabelMaskSpec); always the scan
   LabelMaskSpec label_masks{};
 };
 void launch_bf_query(const BfLaunch& a, hipStream_t stream);

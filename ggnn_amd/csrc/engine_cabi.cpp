@@ -1547,6 +1547,55 @@ ggnn_status ggnn_op_bf_query_labeled_mask(const void* base, ggnn_dtype dtype, ui
   });
 }
 
+// the certified twins of the three calls above: + n_rescanned (device) and matrix_path (host)
+ggnn_status ggnn_op_bf_query_labeled_in_certified(
+    const void* base, ggnn_dtype dtype, uint32_t N_base, uint32_t D, const void* query, uint32_t Nq,
+    uint32_t k_query, ggnn_measure measure, int32_t* ids, float* dists, const int32_t* labels,
+    uint64_t n_labels, const int32_t* query_label_sets, uint32_t set_width,
+    const uint32_t* filter_table, uint32_t num_filters, uint64_t n_bits, const int32_t* filter_ids,
+    uint32_t filter_bit_offset, uint32_t* n_rescanned, int* matrix_path, void* stream)
+{
+  return guarded(nullptr, [&] {
+    BfLaunch b{base, query, dtype, N_base, D, Nq, k_query, measure, ids, dists, n_rescanned};
+    b.matrix_path = matrix_path;
+    seam_label_sets(b, labels, n_labels, query_label_sets, set_width, filter_table, num_filters,
+                    n_bits, filter_ids, filter_bit_offset, N_base);
+    launch_bf_query(b, static_cast<hipStream_t>(stream));
+  });
+}
+
+ggnn_status ggnn_op_bf_query_labeled_range_certified(
+    const void* base, ggnn_dtype dtype, uint32_t N_base, uint32_t D, const void* query, uint32_t Nq,
+    uint32_t k_query, ggnn_measure measure, int32_t* ids, float* dists, const int32_t* labels,
+    uint64_t n_labels, const int32_t* query_label_ranges, uint32_t n_ranges,
+    const uint32_t* filter_table, uint32_t num_filters, uint64_t n_bits, const int32_t* filter_ids,
+    uint32_t filter_bit_offset, uint32_t* n_rescanned, int* matrix_path, void* stream)
+{
+  return guarded(nullptr, [&] {
+    BfLaunch b{base, query, dtype, N_base, D, Nq, k_query, measure, ids, dists, n_rescanned};
+    b.matrix_path = matrix_path;
+    seam_label_ranges(b, labels, n_labels, query_label_ranges, n_ranges, filter_table, num_filters,
+                      n_bits, filter_ids, filter_bit_offset, N_base);
+    launch_bf_query(b, static_cast<hipStream_t>(stream));
+  });
+}
+
+ggnn_status ggnn_op_bf_query_labeled_mask_certified(
+    const void* base, ggnn_dtype dtype, uint32_t N_base, uint32_t D, const void* query, uint32_t Nq,
+    uint32_t k_query, ggnn_measure measure, int32_t* ids, float* dists, const int32_t* labels,
+    uint64_t n_labels, const int32_t* query_label_masks, uint32_t n_masks,
+    const uint32_t* filter_table, uint32_t num_filters, uint64_t n_bits, const int32_t* filter_ids,
+    uint32_t filter_bit_offset, uint32_t* n_rescanned, int* matrix_path, void* stream)
+{
+  return guarded(nullptr, [&] {
+    BfLaunch b{base, query, dtype, N_base, D, Nq, k_query, measure, ids, dists, n_rescanned};
+    b.matrix_path = matrix_path;
+    seam_label_masks(b, labels, n_labels, query_label_masks, n_masks, filter_table, num_filters,
+                     n_bits, filter_ids, filter_bit_offset, N_base);
+    launch_bf_query(b, static_cast<hipStream_t>(stream));
+  });
+}
+
 ggnn_status ggnn_op_pack_filters(const uint8_t* masks, uint32_t num_filters, uint64_t N,
                                  uint32_t* words, void* stream)
 {

@@ -602,14 +602,21 @@ def query_labeled_in(base, query, graph0, start, nn1_stats, k_query, tau_query, 
 
 
 def bf_query_labeled_in(base, query, k_query, labels, label_sets, filter_table=None,
-                        filter_ids=None, measure=EUCLIDEAN, bit_offset=0):
-    """`bf_query_filtered` under label sets (see query_labeled_in); always the scan kernels"""
+                        filter_ids=None, measure=EUCLIDEAN, bit_offset=0, rescanned=False):
+    """`bf_query_filtered` under label sets (see query_labeled_in): large batches run the float tile
+    kernels under a predicate stage, the rest the scan kernels (hook BF_LABEL_TILES), same bits.
+    rescanned=True: returns (ids, dists, rescanned, matrix_path) as bf_query_labeled does."""
     _need(base, name="base"), _need(query, base.dtype, "query")
     Nq = query.shape[0]
     tail = _need_label_sets(labels, label_sets, filter_table, filter_ids, Nq,
                             bit_offset + base.shape[0])
     ids = torch.empty((Nq, k_query), dtype=torch.int32, device=base.device)
     dists = torch.empty((Nq, k_query), dtype=torch.float32, device=base.device)
+    if rescanned:
+        return (ids, dists) + _certified(
+            lib().ggnn_op_bf_query_labeled_in_certified, base, _ptr(base), _dtype_code(base),
+            base.shape[0], base.shape[1], _ptr(query), Nq, k_query, measure, _ptr(ids), _ptr(dists),
+            *tail, bit_offset)
     check(lib().ggnn_op_bf_query_labeled_in(
         _ptr(base), _dtype_code(base), base.shape[0], base.shape[1], _ptr(query), Nq, k_query,
         measure, _ptr(ids), _ptr(dists), *tail, bit_offset, _stream()))
@@ -668,14 +675,21 @@ def query_labeled_range(base, query, graph0, start, nn1_stats, k_query, tau_quer
 
 
 def bf_query_labeled_range(base, query, k_query, labels, label_ranges, filter_table=None,
-                           filter_ids=None, measure=EUCLIDEAN, bit_offset=0):
-    """`bf_query_filtered` under label ranges (see query_labeled_range); always the scan kernels"""
+                           filter_ids=None, measure=EUCLIDEAN, bit_offset=0, rescanned=False):
+    """`bf_query_filtered` under label ranges (see query_labeled_range): large batches run the float
+    tile kernels under a predicate stage, the rest the scan kernels (hook BF_LABEL_TILES), same bits.
+    rescanned=True: returns (ids, dists, rescanned, matrix_path) as bf_query_labeled does."""
     _need(base, name="base"), _need(query, base.dtype, "query")
     Nq = query.shape[0]
     tail = _need_label_ranges(labels, label_ranges, filter_table, filter_ids, Nq,
                               bit_offset + base.shape[0])
     ids = torch.empty((Nq, k_query), dtype=torch.int32, device=base.device)
     dists = torch.empty((Nq, k_query), dtype=torch.float32, device=base.device)
+    if rescanned:
+        return (ids, dists) + _certified(
+            lib().ggnn_op_bf_query_labeled_range_certified, base, _ptr(base), _dtype_code(base),
+            base.shape[0], base.shape[1], _ptr(query), Nq, k_query, measure, _ptr(ids), _ptr(dists),
+            *tail, bit_offset)
     check(lib().ggnn_op_bf_query_labeled_range(
         _ptr(base), _dtype_code(base), base.shape[0], base.shape[1], _ptr(query), Nq, k_query,
         measure, _ptr(ids), _ptr(dists), *tail, bit_offset, _stream()))
@@ -833,14 +847,21 @@ def query_labeled_mask(base, query, graph0, start, nn1_stats, k_query, tau_query
 
 
 def bf_query_labeled_mask(base, query, k_query, labels, label_masks, filter_table=None,
-                          filter_ids=None, measure=EUCLIDEAN, bit_offset=0):
-    """`bf_query_filtered` under label masks (see query_labeled_mask); always the scan kernels"""
+                          filter_ids=None, measure=EUCLIDEAN, bit_offset=0, rescanned=False):
+    """`bf_query_filtered` under label masks (see query_labeled_mask): large batches run the float
+    tile kernels under a predicate stage, the rest the scan kernels (hook BF_LABEL_TILES), same bits.
+    rescanned=True: returns (ids, dists, rescanned, matrix_path) as bf_query_labeled does."""
     _need(base, name="base"), _need(query, base.dtype, "query")
     Nq = query.shape[0]
     tail = _need_label_masks(labels, label_masks, filter_table, filter_ids, Nq,
                              bit_offset + base.shape[0])
     ids = torch.empty((Nq, k_query), dtype=torch.int32, device=base.device)
     dists = torch.empty((Nq, k_query), dtype=torch.float32, device=base.device)
+    if rescanned:
+        return (ids, dists) + _certified(
+            lib().ggnn_op_bf_query_labeled_mask_certified, base, _ptr(base), _dtype_code(base),
+            base.shape[0], base.shape[1], _ptr(query), Nq, k_query, measure, _ptr(ids), _ptr(dists),
+            *tail, bit_offset)
     check(lib().ggnn_op_bf_query_labeled_mask(
         _ptr(base), _dtype_code(base), base.shape[0], base.shape[1], _ptr(query), Nq, k_query,
         measure, _ptr(ids), _ptr(dists), *tail, bit_offset, _stream()))

@@ -365,9 +365,10 @@ ggnn_status ggnn_label_index_build(const int32_t* labels, uint64_t n, int32_t* k
  * null set array and host-resident ids outside [-1, num_filters); GGNN_INVALID_STATE without
  * labels, and with ids but no filter table; GGNN_UNSUPPORTED on an int8 base and for shards of more
  * than 2^30 vectors.  Everything else is ggnn_query / ggnn_bf_query.  ggnn_bf_query_labeled_in
- * always runs the scan kernels: ggnn_last_bf_query_matrix_path reports 0.
+ * runs the float tile kernels under a predicate stage in large batches (hook BF_LABEL_TILES;
+ * ggnn_last_bf_query_matrix_path reports 1) and the scan kernels otherwise (0), same bits.
  * What remains: at most 8 labels per query (numeric predicates: the label ranges below), int32
- * labels only, no int8 rows, no matrix-core path. */
+ * labels only, no int8 rows. */
 #define GGNN_MAX_LABEL_SET 8
 ggnn_status ggnn_query_labeled_in(ggnn_t* h, const void* query, uint64_t Nq, uint32_t D,
                                   ggnn_dtype dtype, ggnn_location location, int gpu_id,
@@ -418,10 +419,11 @@ ggnn_status ggnn_query_async_labeled_in(ggnn_t* h, const void* query, uint64_t N
  * read on the host).  GGNN_INVALID_ARGUMENT for n_ranges outside [1, 4], a null range array and
  * host-resident ids outside [-1, num_filters); GGNN_INVALID_STATE without labels, and with ids but
  * no filter table; GGNN_UNSUPPORTED on an int8 base and for shards of more than 2^30 vectors.
- * Everything else is ggnn_query / ggnn_bf_query.  ggnn_bf_query_labeled_range always runs the scan
- * kernels: ggnn_last_bf_query_matrix_path reports 0.
+ * Everything else is ggnn_query / ggnn_bf_query.  ggnn_bf_query_labeled_range runs the float tile
+ * kernels under a predicate stage in large batches (hook BF_LABEL_TILES;
+ * ggnn_last_bf_query_matrix_path reports 1) and the scan kernels otherwise (0), same bits.
  * What remains: at most 4 intervals per query, one int32 column (float32 attributes: map them to
- * int32 in order first), closed intervals only, no int8 rows, no matrix-core path. */
+ * int32 in order first), closed intervals only, no int8 rows. */
 #define GGNN_MAX_LABEL_RANGES 4
 ggnn_status ggnn_query_labeled_range(ggnn_t* h, const void* query, uint64_t Nq, uint32_t D,
                                      ggnn_dtype dtype, ggnn_location location, int gpu_id,
@@ -473,9 +475,10 @@ ggnn_status ggnn_query_async_labeled_range(ggnn_t* h, const void* query, uint64_
  * read on the host).  GGNN_INVALID_ARGUMENT for n_masks outside [1, 2], a null clause array and
  * host-resident ids outside [-1, num_filters); GGNN_INVALID_STATE without labels, and with ids but
  * no filter table; GGNN_UNSUPPORTED on an int8 base and for shards of more than 2^30 vectors.
- * Everything else is ggnn_query / ggnn_bf_query.  ggnn_bf_query_labeled_mask always runs the scan
- * kernels: ggnn_last_bf_query_matrix_path reports 0.
- * What remains: at most 2 clauses per query, one int32 column, no int8 rows, no matrix-core path. */
+ * Everything else is ggnn_query / ggnn_bf_query.  ggnn_bf_query_labeled_mask runs the float tile
+ * kernels under a predicate stage in large batches (hook BF_LABEL_TILES;
+ * ggnn_last_bf_query_matrix_path reports 1) and the scan kernels otherwise (0), same bits.
+ * What remains: at most 2 clauses per query, one int32 column, no int8 rows. */
 #define GGNN_MAX_LABEL_MASKS 2
 ggnn_status ggnn_query_labeled_mask(ggnn_t* h, const void* query, uint64_t Nq, uint32_t D,
                                     ggnn_dtype dtype, ggnn_location location, int gpu_id,
@@ -748,7 +751,15 @@ void ggnn_set_log_level(int level);
  *                             float32-staged filtered tiles for uint8 rows wider than 128 bytes) | 2 =
  *                             whenever those conditions hold with Nq >= 256, N >= 4096; BF_SCAN = 1
  *                             still means the scan (same results; test hook)
- *   BF_F16              0     bf_query on float16 / bfloat16 rows: 0 = 16-bit tile kernels (bf_f16.hip)
+ *   BF_LABEL_TILES      0     bf_query under label sets, label ranges or label masks (with or without
+ *                             filter ids): 0 = the float tile kernels with a predicate stage
+ *                             (bf_mfma_pred.hip) when the rows are float32 / float16 / bfloat16 / uint8
+ *                             outside the integer kernels' shapes (uint8 under squared L2 at D <= 128
+ *                             keeps the scan), k + 8 <= 120, filter ids come with a table whose bit
+ *                             offset is a multiple of 32, and Nq >= 10000, N >= 1000000 | 1 = never
+ *                             (the scan kernels) | 2 = whenever those conditions hold with Nq >= 256,
+ *                             N >= 4096; BF_SCAN = 1 still means the scan (same results; test hook)
+ *   BF_F16              0    bf_query on float16 / bfloat16 rows: 0 = 16-bit tile kernels (bf_f16.hip)
  *                             when the measure is squared L2, the call has no filter of any kind,
  *                             D % 8 == 0, D <= 4096, k + 8 <= 120 (k <= 110 at D <= 32: the lists of
  *                             a workgroup must fit its LDS) and the rows are bfloat16 with
@@ -1029,7 +1040,8 @@ ggnn_status ggnn_op_label_spans_classify(const uint32_t* totals, uint32_t Nq, ui
  * [0, num_filters): bit i + filter_bit_offset of row f, anything else: none.  filter_ids may be
  * NULL (labels only) and so may filter_table with num_filters == 0 (then an id is -1 or admits
  * nothing); n_bits >= filter_bit_offset + N_base when there is a table.  No int8 rows
- * (GGNN_UNSUPPORTED); ggnn_op_bf_query_labeled_in always runs the scan kernels. */
+ * (GGNN_UNSUPPORTED); ggnn_op_bf_query_labeled_in runs the float tile kernels under a predicate
+ * stage in large batches and the scan kernels otherwise (hook BF_LABEL_TILES), same bits. */
 ggnn_status ggnn_op_query_labeled_in(const void* base, ggnn_dtype dtype, uint32_t N_base,
                                      uint32_t D, const uint8_t* codes, const float* params,
                                      const void* query, uint32_t Nq, const int32_t* graph0,
@@ -1056,7 +1068,8 @@ ggnn_status ggnn_op_bf_query_labeled_in(const void* base, ggnn_dtype dtype, uint
  * GGNN_MAX_LABEL_RANGES; local id i may be given to query n iff lo <= labels[i + filter_bit_offset]
  * <= hi (signed) for one of its pairs AND filter_ids[n] admits it, as above.  lo > hi is an empty
  * interval and there is no wildcard value (see ggnn_query_labeled_range).  No int8 rows
- * (GGNN_UNSUPPORTED); ggnn_op_bf_query_labeled_range always runs the scan kernels. */
+ * (GGNN_UNSUPPORTED); ggnn_op_bf_query_labeled_range runs the float tile kernels under a predicate
+ * stage in large batches and the scan kernels otherwise (hook BF_LABEL_TILES), same bits. */
 ggnn_status ggnn_op_query_labeled_range(const void* base, ggnn_dtype dtype, uint32_t N_base,
                                         uint32_t D, const uint8_t* codes, const float* params,
                                         const void* query, uint32_t Nq, const int32_t* graph0,
@@ -1084,8 +1097,9 @@ ggnn_status ggnn_op_bf_query_labeled_range(const void* base, ggnn_dtype dtype, u
  * GGNN_MAX_LABEL_MASKS; local id i may be given to query n iff L = labels[i + filter_bit_offset] has
  * (L & mask) == value and (any == 0 or (L & any) != 0) for one of its triples AND filter_ids[n] admits
  * it, as above.  value is never pre-masked and there is no wildcard value (see
- * ggnn_query_labeled_mask).  No int8 rows (GGNN_UNSUPPORTED); ggnn_op_bf_query_labeled_mask always
- * runs the scan kernels. */
+ * ggnn_query_labeled_mask).  No int8 rows (GGNN_UNSUPPORTED); ggnn_op_bf_query_labeled_mask runs
+ * the float tile kernels under a predicate stage in large batches and the scan kernels otherwise
+ * (hook BF_LABEL_TILES), same bits. */
 ggnn_status ggnn_op_query_labeled_mask(const void* base, ggnn_dtype dtype, uint32_t N_base,
                                        uint32_t D, const uint8_t* codes, const float* params,
                                        const void* query, uint32_t Nq, const int32_t* graph0,
@@ -1133,6 +1147,27 @@ ggnn_status ggnn_op_bf_query_labeled_certified(const void* base, ggnn_dtype dtyp
                                                uint64_t n_labels, const int32_t* query_labels,
                                                uint32_t filter_bit_offset, uint32_t* n_rescanned,
                                                int* matrix_path, void* stream);
+/* ggnn_op_bf_query_labeled_in, _labeled_range and _labeled_mask, reporting how they ran: the same
+ * arguments plus n_rescanned and matrix_path as above (1: the float tile kernels under the predicate
+ * stage, hook BF_LABEL_TILES; 0: the scan kernels of the family). */
+ggnn_status ggnn_op_bf_query_labeled_in_certified(
+    const void* base, ggnn_dtype dtype, uint32_t N_base, uint32_t D, const void* query, uint32_t Nq,
+    uint32_t k_query, ggnn_measure measure, int32_t* ids, float* dists, const int32_t* labels,
+    uint64_t n_labels, const int32_t* query_label_sets, uint32_t set_width,
+    const uint32_t* filter_table, uint32_t num_filters, uint64_t n_bits, const int32_t* filter_ids,
+    uint32_t filter_bit_offset, uint32_t* n_rescanned, int* matrix_path, void* stream);
+ggnn_status ggnn_op_bf_query_labeled_range_certified(
+    const void* base, ggnn_dtype dtype, uint32_t N_base, uint32_t D, const void* query, uint32_t Nq,
+    uint32_t k_query, ggnn_measure measure, int32_t* ids, float* dists, const int32_t* labels,
+    uint64_t n_labels, const int32_t* query_label_ranges, uint32_t n_ranges,
+    const uint32_t* filter_table, uint32_t num_filters, uint64_t n_bits, const int32_t* filter_ids,
+    uint32_t filter_bit_offset, uint32_t* n_rescanned, int* matrix_path, void* stream);
+ggnn_status ggnn_op_bf_query_labeled_mask_certified(
+    const void* base, ggnn_dtype dtype, uint32_t N_base, uint32_t D, const void* query, uint32_t Nq,
+    uint32_t k_query, ggnn_measure measure, int32_t* ids, float* dists, const int32_t* labels,
+    uint64_t n_labels, const int32_t* query_label_masks, uint32_t n_masks,
+    const uint32_t* filter_table, uint32_t num_filters, uint64_t n_bits, const int32_t* filter_ids,
+    uint32_t filter_bit_offset, uint32_t* n_rescanned, int* matrix_path, void* stream);
 /* [num_filters x N] byte masks (non-zero: allowed) -> [num_filters x ceil(N / 32)] bitset words,
  * padding bits zero; both in device memory.  A table made from a label column on the GPU needs
  * no host round trip. */

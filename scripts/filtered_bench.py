@@ -170,14 +170,14 @@ def brute_force(a, g, q):
     a_side, b_side = ({"BF_SCAN": 1}, {}) if a.dtype == "float32" else \
         ({"BF_I8_FILTERED": 1}, {"BF_I8_FILTERED": 2})
 
-    def ab(name, call, **extra):
+    def ab(name, call, sides=(a_side, b_side), **extra):
         scan, matrix = [], []
         for _ in range(a.reps):
-            with _lib.hooks(**a_side):
+            with _lib.hooks(**sides[0]):
                 call()
                 a_path = g.last_bf_query_matrix_path()
             scan.append(round(g.last_timing_ms()["bf_query_ms"], 3))
-            with _lib.hooks(**b_side):
+            with _lib.hooks(**sides[1]):
                 call()
             matrix.append(round(g.last_timing_ms()["bf_query_ms"], 3))
         print(json.dumps({"bf": name, **extra, "scan_ms": scan, "scan_path": a_path, "matrix_ms": matrix,
@@ -200,6 +200,28 @@ def brute_force(a, g, q):
         g.set_filters(torch.from_numpy(words))
         ab("table", lambda: g.bf_query_filtered_by(q, a.k, filter_ids=ids), rows=T)
         g.set_filters(None)
+    if a.dtype == "int8":
+        return
+    # label predicates: the scan (BF_LABEL_TILES = 1) against the tile kernels under the predicate
+    # stage (2); every query admits about a third of the rows, with and without a 50 % table row
+    pred = ({"BF_LABEL_TILES": 1}, {"BF_LABEL_TILES": 2})
+    g.set_labels(rs.integers(0, 24, a.n).astype(np.int32))
+    first = rs.integers(0, 17, a.queries).astype(np.int32)
+    sets = torch.from_numpy((first[:, None] + np.arange(8, dtype=np.int32)[None, :])).cuda()
+    ranges = torch.from_numpy(np.stack([first, first + 7], 1)[:, None, :].repeat(4, 1)).cuda()
+    masks = torch.from_numpy(np.stack([np.full_like(first, 0x18), (first % 3) * 8, np.zeros_like(first)],
+                                      1)[:, None, :].repeat(2, 1)).cuda()
+    g.set_filters(torch.from_numpy(np.stack([ggnn.pack_filter(rs.random(a.n) < 0.5).numpy()])))
+    for fids in (None, torch.zeros(a.queries, dtype=torch.int32).cuda()):
+        tab = fids is not None
+        ab("label sets", lambda: g.bf_query_labeled_in(q, a.k, label_sets=sets, filter_ids=fids),
+           pred, table=tab)
+        ab("label ranges", lambda: g.bf_query_labeled_range(q, a.k, label_ranges=ranges, filter_ids=fids),
+           pred, table=tab)
+        ab("label masks", lambda: g.bf_query_labeled_mask(q, a.k, label_masks=masks, filter_ids=fids),
+           pred, table=tab)
+    g.set_filters(None)
+    g.set_labels(None)
 
 
 def mixed(a, g, q):
