@@ -267,6 +267,7 @@ SIGNATURES = {
                                              C.POINTER(_u64)]),
     "ggnn_debug_bf_f16_route": (_int, [_int, _int, _u32, _u32, _u32, _u32, _int]),
     "ggnn_debug_bf_i8_wide_route": (_int, [_int, _int, _u32, _u32, _u32, _u32, _int]),
+    "ggnn_debug_bf_i8_cos_route": (_int, [_int, _int, _u32, _u32, _u32, _u32, _int]),
     "ggnn_debug_bf_f16_ratio_sink": (None, [_vp]),
     "ggnn_last_exchange": (C.c_char_p, [_vp]),
     "ggnn_op_top": (_int, [_vp, _int, _u32, _int, _u32, _vp, _u32, _u32, _u32, _u32, _vp, _vp,

@@ -153,6 +153,36 @@ void launch_bf_i8_wide(const BfI8WideArgs& m, uint32_t KP, bool is_signed, uint3
 void launch_bf_i8_wide_uncertified(const float* dists, uint32_t Nq, uint32_t K, uint32_t* rescan_list,
                                    uint32_t* rescan_count, hipStream_t stream);
 
+// bf_i8_cos.hip: the register-set kernel for uint8 / int8 rows of 16 <= D <= 4096 bytes under cosine
+// (the file's header has the arithmetic contract).  Side data of a row or a query, one 16-byte record:
+//   x  float bits of 1 / sqrtf((float)y), 0 for a zero row
+//   y  sum x^2 of the row as stored (uint8: 0..255, int8: -128..127), <= 255^2 * 4096 < 2^31
+//   z  uint8: 128 * sum (x - 128), the row's term of the true dot product; int8: 0
+struct BfI8CosArgs {
+  const void* base;
+  const uint4* query_packed;  // as BfI8WideArgs::query_packed
+  const int4* brec;           // [N_base] records of the base rows
+  const int4* qrec;           // [Nq] records of the queries
+  int32_t* part_ids;          // [slices][Nq][KP]
+  float* part_dists;          // [slices][Nq][KP] the scan's values
+  uint32_t D, nch, Nq, N_base, slices, rows_per_slice;
+  uint32_t* gthr;             // exchange area, as BfMfmaArgs::gthr (float bits of values)
+  uint32_t rank_mask, refresh_every;
+  int32_t* seed;              // [Nq], as BfMfmaArgs::seed (float bits)
+  uint32_t seeding;
+};
+// (bf_i8_cos_supported / bf_i8_cos_routes: common.hpp)
+// records of N rows; norm_max (device word, cleared by the caller, or null): receives the largest y
+void launch_bf_i8_cos_records(const void* rows, uint32_t N, uint32_t D, bool is_signed, int4* rec,
+                              uint32_t* norm_max, hipStream_t stream);
+// the tile kernel for KP in {4, 10, 16}, after a seeding launch as for launch_bf_i8_wide
+void launch_bf_i8_cos(const BfI8CosArgs& m, uint32_t KP, bool is_signed, uint32_t qblocks,
+                      uint32_t seed_rows, hipStream_t stream);
+// the 2^24 rule under cosine: a query with sum q^2 >= 2^24 is appended to the rescan list, and every
+// query when *norm_max >= 2^24
+void launch_bf_i8_cos_uncertified(const int4* qrec, const uint32_t* norm_max, uint32_t Nq,
+                                  uint32_t* rescan_list, uint32_t* rescan_count, hipStream_t stream);
+
 // bf_i8_filtered.hip: the filtered forms of the two register-set kernels (the file's header has the
 // design).  One argument block for both row regimes; norms are int32 as for the wide rows.
 //   kI8fBits    the call's one bitset, folded into the staged row norms

@@ -1898,6 +1898,101 @@ static void launch_bf_query_i8_wide(const BfLaunch& a, hipStream_t stream)
                                   hipMemcpyDeviceToDevice, stream));
 }
 
+// uint8 / int8 rows under cosine, k <= 16, no filter (bf_i8_cos_routes): launch_bf_query_i8_wide's
+// sequence and scratch layout around the kernels of bf_i8_cos.hip -- 16-byte records of the rows and the
+// queries in place of the int32 norms, the exact re-rank, the 2^24 rule on the norms (the file's header),
+// the re-scan of what that rule left open
+static void launch_bf_query_i8_cos(const BfLaunch& a, hipStream_t stream)
+{
+  const bool is_signed = a.dtype == GGNN_I8;
+  const uint32_t KP = a.k_query <= 4 ? 4u : a.k_query <= 10 ? 10u : 16u;
+  const uint32_t qblocks = (a.Nq + 255) / 256;
+  // one round of resident workgroups (two per CU); hook BF_SLICES
+  uint32_t slices = std::max(1u, std::min(32u, 512u / std::max(1u, qblocks)));
+  if (const int64_t hs = hook(kHookBfSlices); hs > 0)
+    slices = static_cast<uint32_t>(std::clamp<int64_t>(hs, 1, 64));
+  uint32_t rows_per_slice = (a.N_base + slices - 1) / slices;
+  rows_per_slice = (rows_per_slice + kBfTileRows - 1) / kBfTileRows * kBfTileRows;
+  slices = (a.N_base + rows_per_slice - 1) / rows_per_slice;
+
+  // one scratch block: [row records 4 N][query records 4 Nq][rescan_count etc. 4][rescan_list Nq]
+  // [part ids][part dists][re-scan slices ids][re-scan slices dists][exchange area + seeds][packed queries]
+  auto pad4 = [](size_t words) { return (words + 3) / 4 * 4; };
+  uint32_t rescan_slices = 0;
+  const size_t n_b = 4 * static_cast<size_t>(a.N_base), n_qr = 4 * static_cast<size_t>(a.Nq);
+  const size_t n_q = pad4(a.Nq);
+  const size_t n_parts = pad4(static_cast<size_t>(slices) * a.Nq * KP);
+  const size_t n_rescan = pad4(bf_rescan_tmp_entries(a, &rescan_slices));
+  const size_t n_exch = pad4(bf_i8v2_exchange_ints(a.Nq, slices));
+  const size_t n_pack = bf_i8_wide_packed_words(qblocks, a.D);
+  const size_t words = n_b + n_qr + 4 + n_q + 2 * n_parts + 2 * n_rescan + n_exch + n_q + n_pack;
+  ScratchGuard scratch{scratch_alloc(words * 4, stream), stream};
+  int4* brec = static_cast<int4*>(scratch.p);
+  int4* qrec = brec + a.N_base;
+  uint32_t* flags = reinterpret_cast<uint32_t*>(qrec + a.Nq);  // [1] rescan count [2] largest row norm
+  uint32_t* rescan_list = flags + 4;
+  int32_t* part_ids = reinterpret_cast<int32_t*>(rescan_list + n_q);
+  float* part_dists = reinterpret_cast<float*>(part_ids + n_parts);
+  int32_t* rescan_ids = reinterpret_cast<int32_t*>(part_dists + n_parts);
+  float* rescan_dists = reinterpret_cast<float*>(rescan_ids + n_rescan);
+  uint32_t* gthr = reinterpret_cast<uint32_t*>(rescan_dists + n_rescan);
+  uint4* packed = reinterpret_cast<uint4*>(gthr + n_exch + n_q);
+  GGNN_HIP_CHECK(hipMemsetAsync(flags, 0, 4 * sizeof(uint32_t), stream));
+  GGNN_HIP_CHECK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(gthr), 0x7fffffff, n_exch + n_q,
+                                   stream));  // "nothing published", "no seed"
+  launch_bf_i8_cos_records(a.base, a.N_base, a.D, is_signed, brec, flags + 2, stream);
+  launch_bf_i8_cos_records(a.query, a.Nq, a.D, is_signed, qrec, nullptr, stream);
+  launch_bf_i8_wide_pack(a.query, a.Nq, a.D, is_signed, qblocks, packed, stream);
+
+  BfI8CosArgs m{};
+  m.base = a.base;
+  m.query_packed = packed;
+  m.brec = brec;
+  m.qrec = qrec;
+  m.part_ids = part_ids;
+  m.part_dists = part_dists;
+  m.D = a.D;
+  m.nch = (a.D + 127) / 128;
+  m.Nq = a.Nq;
+  m.N_base = a.N_base;
+  m.slices = slices;
+  m.rows_per_slice = rows_per_slice;
+  // hooks BF_I8_NOSHARE, BF_I8_RANKS, BF_I8_REFRESH (counted in tiles), BF_I8_SEED: as for bf_i8w_kernel
+  m.gthr = hook(kHookBfI8NoShare) ? nullptr : gthr;
+  const int64_t hr = hook(kHookBfI8Ranks);
+  m.rank_mask = hr >= 0 ? static_cast<uint32_t>(hr) & 31u : bf_i8v2_default_rank_mask(KP, slices);
+  if (slices <= 1)
+    m.rank_mask = 0;  // nothing to exchange
+  m.refresh_every = static_cast<uint32_t>(std::clamp<int64_t>(hook(kHookBfI8Refresh), 1, 1 << 20));
+  m.seed = reinterpret_cast<int32_t*>(gthr + n_exch);
+  const uint32_t seed_rows = static_cast<uint32_t>(
+      std::clamp<int64_t>(hook(kHookBfI8Seed), 0, static_cast<int64_t>(a.N_base)));
+  launch_bf_i8_cos(m, KP, is_signed, qblocks, seed_rows, stream);
+
+  BfRerankArgs rr{};
+  rr.base = a.base;
+  rr.query = a.query;
+  rr.part_ids = part_ids;
+  rr.part_dists = part_dists;
+  rr.rescan_count = flags + 1;
+  rr.rescan_list = rescan_list;
+  rr.ids = a.ids;
+  rr.dists = a.dists;
+  rr.D = a.D;
+  rr.Nq = a.Nq;
+  rr.K = a.k_query;
+  rr.KP = KP;
+  rr.slices = slices;
+  rr.cap = (slices * KP + 3) / 4 * 4;
+  rr.exact_arith = 1;  // exact selection: the re-rank certifies nothing; the 2^24 rule follows
+  launch_bf_rerank(a, rr, stream);
+  launch_bf_i8_cos_uncertified(qrec, flags + 2, a.Nq, rescan_list, flags + 1, stream);
+  launch_bf_rescan(a, rescan_list, flags + 1, rescan_ids, rescan_dists, stream);
+  if (a.n_rescanned)
+    GGNN_HIP_CHECK(hipMemcpyAsync(a.n_rescanned, flags + 1, sizeof(uint32_t),
+                                  hipMemcpyDeviceToDevice, stream));
+}
+
 // uint8 / int8 rows under squared L2, k <= 16, with a bitset, a filter table or labels
 // (bf_i8_filtered_routes): launch_bf_query_i8_wide's sequence around the kernels of bf_i8_filtered.hip, in
 // both row regimes.  The sets hold admitted rows only, so the re-rank needs no filter; the re-scan of what
@@ -2011,6 +2106,10 @@ void launch_bf_query_mfma(const BfLaunch& a, hipStream_t stream)
   // (a label predicate without a table has no filter_bits: not an unfiltered launch all the same)
   if (!bf_has_predicate(a) && bf_i8_wide_routes(a)) {
     launch_bf_query_i8_wide(a, stream);
+    return;
+  }
+  if (bf_i8_cos_routes(a)) {
+    launch_bf_query_i8_cos(a, stream);
     return;
   }
   // a few more candidates than K per slice: makes the certificate (top of this file) succeed for

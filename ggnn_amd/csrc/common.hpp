@@ -297,6 +297,12 @@ void bf_f16_set_ratio_sink(uint32_t* device_word);
 bool bf_i8_wide_supported(const BfLaunch& a);
 // ... that launch_bf_query_mfma sends to the kernel under hook BF_I8_WIDE (0 auto | 1 never | 2 always)
 bool bf_i8_wide_routes(const BfLaunch& a);
+// host side of the integer cosine kernel (bf_i8_cos.hip): the launch is an unfiltered uint8 / int8 launch
+// under cosine with no label predicate, 16 <= D <= 4096, D % 16 == 0, k <= 16, Nq >= 256, N_base >= 4096
+// and hook BF_NO_I8 = 0
+bool bf_i8_cos_supported(const BfLaunch& a);
+// ... that launch_bf_query_mfma sends to the kernel under hook BF_I8_COS (0 auto | 1 never | 2 always)
+bool bf_i8_cos_routes(const BfLaunch& a);
 // host side of the filtered integer kernels (bf_i8_filtered.hip): the launch is a uint8 / int8 launch
 // under squared L2 with a per-call bitset, a filter table or one label per query, D % 16 == 0, D <= 4096,
 // k <= 16, Nq >= 256, N_base >= 4096, a bitset offset that is a multiple of 32 and hook BF_NO_I8 = 0

@@ -1038,6 +1038,17 @@ int ggnn_debug_bf_i8_wide_route(ggnn_dtype dtype, ggnn_measure measure, uint32_t
   return hook(kHookBfScan) != 1 && bf_i8_wide_routes(b) ? 1 : 0;
 }
 
+// tests: would a bf_query launch of this shape take the integer cosine kernel (bf_i8_cos.hip)?
+int ggnn_debug_bf_i8_cos_route(ggnn_dtype dtype, ggnn_measure measure, uint32_t D, uint32_t Nq,
+                               uint32_t N_base, uint32_t k_query, int filtered)
+{
+  static const uint32_t word = 0;
+  BfLaunch b{};
+  b.dtype = dtype, b.measure = measure, b.D = D, b.Nq = Nq, b.N_base = N_base, b.k_query = k_query;
+  b.filter_bits = filtered ? &word : nullptr;
+  return hook(kHookBfScan) != 1 && bf_i8_cos_routes(b) ? 1 : 0;
+}
+
 void ggnn_debug_bf_f16_ratio_sink(uint32_t* device_word)
 {
   bf_f16_set_ratio_sink(device_word);

@@ -140,7 +140,9 @@ ggnn_status ggnn_synchronize_slot(ggnn_t* h, uint32_t slot);
  * uint8 / int8 rows under squared L2 run on the integer matrix cores: rows of up to 128 bytes always
  * (bf_i8.hip), wider rows (D % 16 == 0, D <= 4096, k_query <= 16) from 10000 queries x 1000000 rows on
  * or under hook BF_I8_WIDE = 2 (bf_i8_wide.hip).  Exact either way: a query whose k-th distance is
- * >= 2^24 is answered by the scan and counted by ggnn_last_bf_query_rescanned. */
+ * >= 2^24 is answered by the scan and counted by ggnn_last_bf_query_rescanned.  Under cosine they have
+ * an integer kernel as well (bf_i8_cos.hip, hook BF_I8_COS), exact in the same way: queries are
+ * re-scanned when a squared norm reaches 2^24. */
 ggnn_status ggnn_bf_query(ggnn_t* h, const void* query, uint64_t Nq, uint32_t D,
                           ggnn_dtype dtype, ggnn_location location, int gpu_id, uint32_t k_gt,
                           ggnn_measure measure, int32_t* ids_out, float* dists_out,
@@ -585,6 +587,10 @@ int ggnn_debug_bf_f16_route(ggnn_dtype dtype, ggnn_measure measure, uint32_t D, 
  * BF_NO_I8, BF_SCAN) */
 int ggnn_debug_bf_i8_wide_route(ggnn_dtype dtype, ggnn_measure measure, uint32_t D, uint32_t Nq,
                                 uint32_t N_base, uint32_t k_query, int filtered);
+/* tests: the same for the integer cosine kernel of uint8 / int8 rows (bf_i8_cos.hip; hooks BF_I8_COS,
+ * BF_NO_I8, BF_SCAN) */
+int ggnn_debug_bf_i8_cos_route(ggnn_dtype dtype, ggnn_measure measure, uint32_t D, uint32_t Nq,
+                               uint32_t N_base, uint32_t k_query, int filtered);
 /* scripts/bf_f16_cm.py: a DEVICE word that the 16-bit tile path's re-rank raises (atomic max of float
  * bits) to the largest |d_e - d_dir| / ((2D+8) 2^-24 (|q|^2 + |x|^2)) over the candidates of the
  * launches that follow -- the evidence behind the certificate's model constant; NULL:
@@ -743,7 +749,13 @@ void ggnn_set_log_level(int level);
  *                             N >= 1000000 | 1 = never (the float32-staged tiles) | 2 = whenever those
  *                             conditions hold with Nq >= 256, N >= 4096; BF_SCAN = 1 still means the scan
  *                             (same results; test hook)
- *   BF_I8_FILTERED      0     filtered bf_query (per-call bitset, filter ids, one label per query) on
+ *   BF_I8_COS           0     bf_query on uint8 / int8 rows under cosine: 0 = the integer cosine kernel
+ *                             (bf_i8_cos.hip) when the call has no filter and no label predicate,
+ *                             16 <= D <= 4096, D % 16 == 0, k <= 16, BF_NO_I8 = 0 and Nq >= 10000,
+ *                             N >= 1000000 | 1 = never (the float32-staged tiles) | 2 = whenever those
+ *                             conditions hold with Nq >= 256, N >= 4096; BF_SCAN = 1 still means the scan
+ *                             (same results; test hook)
+ *   BF_I8_FILTERED      0    filtered bf_query (per-call bitset, filter ids, one label per query) on
  *                             uint8 / int8 rows: 0 = the filtered integer kernels (bf_i8_filtered.hip)
  *                             when the measure is squared L2, D % 16 == 0, D <= 4096, k <= 16, a bitset's
  *                             bit offset is a multiple of 32, BF_NO_I8 = 0 and Nq >= 10000, N >= 1000000
