@@ -263,6 +263,8 @@ SIGNATURES = {
                                          C.POINTER(_u64)]),
     "ggnn_debug_bf_range_i8_route": (_int, [_int, _int, _u32, _u32, _u32, _u64, _int, _u32,
                                             C.POINTER(_u64)]),
+    "ggnn_debug_bf_range_i8_cos_route": (_int, [_int, _int, _u32, _u32, _u32, _u64, _int, _u32,
+                                                C.POINTER(_u64)]),
     "ggnn_debug_bf_range_f16_route": (_int, [_int, _int, _u32, _u32, _u32, _u64, _int, _u32,
                                              C.POINTER(_u64)]),
     "ggnn_debug_bf_f16_route": (_int, [_int, _int, _u32, _u32, _u32, _u32, _int]),

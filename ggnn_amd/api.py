@@ -1311,7 +1311,7 @@ class GGNN:
     def last_bf_range_matrix_path(self):
         """1 if the last bf_range_query* call chose the float tile kernels (matrix-core pre-selection,
         every hit decided exactly), 2 if it chose the integer tile kernels of uint8 / int8 rows
-        (squared L2, exact verdicts), 3 if it chose the 16-bit tile kernels of float16 / bfloat16 rows
+        (squared L2 or cosine, exact verdicts), 3 if it chose the 16-bit tile kernels of float16 / bfloat16 rows
         (squared L2), else 0 (the scan kernels); the same bits on every path"""
         n = C.c_int()
         self._check(lib().ggnn_last_bf_range_matrix_path(self._h, C.byref(n)))

@@ -338,6 +338,12 @@ void launch_bf_range_query_mfma(const BfRangeLaunch& a, hipStream_t stream);
 // bf_range_i8.hip: uint8 / int8 rows under squared L2 on the integer matrix cores, exact verdicts
 // (a launch that bf_range_i8_supported admits)
 void launch_bf_range_query_i8(const BfRangeLaunch& a, hipStream_t stream);
+// its last pass (bf_range_i8_take_lims_kernel): lims[0, n) = from[0, n) if *flag != 0
+void launch_bf_range_i8_take_lims(const uint32_t* flag, const uint64_t* from, uint32_t n, uint64_t* lims,
+                                  hipStream_t stream);
+// bf_range_i8_cos.hip: uint8 / int8 rows under cosine on the integer matrix cores, exact verdicts
+// (a launch that bf_range_i8_cos_supported admits)
+void launch_bf_range_query_i8_cos(const BfRangeLaunch& a, hipStream_t stream);
 // bf_range_f16.hip: float16 / bfloat16 rows under squared L2 on the 16-bit matrix cores, tile
 // pre-selection and exact hits (a launch that bf_range_f16_supported admits)
 void launch_bf_range_query_f16(const BfRangeLaunch& a, hipStream_t stream);

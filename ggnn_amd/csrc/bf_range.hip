@@ -12,7 +12,8 @@
 //           A wave leaves at once when lims[Nq] exceeds the capacity: ids / dists stay untouched.
 // Count and fill are one kernel body with one `if constexpr`: they cannot disagree.
 // Calls that suit the tile kernels go to bf_range_mfma.hip (float rows), bf_range_f16.hip (16-bit rows,
-// squared L2, large batches) or bf_range_i8.hip (byte rows, squared L2) -- launch_bf_range_query
+// squared L2, large batches), bf_range_i8.hip (byte rows, squared L2) or bf_range_i8_cos.hip (byte rows,
+// cosine) -- launch_bf_range_query
 // routes; those paths enqueue these passes behind themselves with a gate word, as their fallback
 // (launch_bf_range_scan).
 #include <algorithm>
@@ -270,6 +271,13 @@ void launch_bf_range_query(const BfRangeLaunch& a_in, hipStream_t stream)
     if (a.matrix_path)
       *a.matrix_path = 2;
     launch_bf_range_query_i8(a, stream);
+  }
+  // byte rows under cosine: the exact integer dot, a float pre-test, the scan's expression
+  // (bf_range_i8_cos.hip)
+  else if (bf_range_i8_cos_supported(a)) {
+    if (a.matrix_path)
+      *a.matrix_path = 2;
+    launch_bf_range_query_i8_cos(a, stream);
   }
   else
     launch_bf_range_scan(a, nullptr, stream);

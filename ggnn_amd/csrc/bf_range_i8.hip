@@ -607,8 +607,15 @@ static void launch_bf_range_i8_t(const BfRangeLaunch& a, hipStream_t stream)
   BfRangeLaunch fb = a;
   fb.lims = scan_lims;
   launch_bf_range_scan(fb, flag, stream);
-  hipLaunchKernelGGL(bf_range_i8_take_lims_kernel, dim3(std::min((a.Nq + 1 + 255) / 256, 1024u)),
-                     dim3(256), 0, stream, flag, scan_lims, a.Nq + 1, a.lims);
+  launch_bf_range_i8_take_lims(flag, scan_lims, a.Nq + 1, a.lims, stream);
+}
+
+// (bf_common.hpp: shared with bf_range_i8_cos.hip)
+void launch_bf_range_i8_take_lims(const uint32_t* flag, const uint64_t* from, uint32_t n, uint64_t* lims,
+                                  hipStream_t stream)
+{
+  hipLaunchKernelGGL(bf_range_i8_take_lims_kernel, dim3(std::min((n + 255) / 256, 1024u)), dim3(256), 0,
+                     stream, flag, from, n, lims);
   GGNN_HIP_CHECK(hipGetLastError());
 }
 

@@ -321,8 +321,8 @@ void launch_bf_query_i8_filtered(const BfLaunch& a, hipStream_t stream);
 // (filter_table.query_labels) -- BfLaunch's rules.
 // Float rows in large batches are pre-selected on the matrix cores and every hit decided exactly
 // (bf_range_mfma.hip, bf_range_mfma_supported); uint8 / int8 rows under squared L2 in large batches
-// are decided on the integer matrix cores (bf_range_i8.hip, bf_range_i8_supported); the scan kernels
-// answer the rest.  Same bits.
+// are decided on the integer matrix cores (bf_range_i8.hip, bf_range_i8_supported), under cosine by
+// bf_range_i8_cos.hip (bf_range_i8_cos_supported); the scan kernels answer the rest.  Same bits.
 struct BfRangeLaunch {
   const void* base;
   const void* query;
@@ -340,7 +340,7 @@ struct BfRangeLaunch {
   // tile path (bf_range_mfma.hip): 1 if the candidate budget overflowed and the scan answered the
   // call, else 0 (device, optional); *matrix_path (host, optional): 1 = the float tile path was chosen,
   // 2 = the integer tile kernels (bf_range_i8.hip; fell_back: a radius >= 2^24 at D > 258 sent the
-  // call to the scan), 3 = the 16-bit tile kernels (bf_range_f16.hip; fell_back: the budget, a
+  // call to the scan -- bf_range_i8_cos.hip under cosine; fell_back: a squared norm >= 2^24 did), 3 = the 16-bit tile kernels (bf_range_f16.hip; fell_back: the budget, a
   // subnormal or non-finite input, or a candidate outside the instruction model), 0 = the scan
   uint32_t* fell_back{nullptr};
   int* matrix_path{nullptr};
@@ -356,6 +356,12 @@ size_t bf_range_tile_lds_bytes(uint32_t D, int fm);
 // (0: Nq >= 256 and N_base >= 65536, 1: no, 2: minima waived)
 bool bf_range_i8_supported(const BfRangeLaunch& a);
 size_t bf_range_i8_lds_bytes(uint32_t D, int fm);
+// and for the integer cosine tile kernels (bf_range_i8_cos.hip), tried after it: uint8 / int8, cosine,
+// 16 <= D <= 4096, D % 16 == 0, a bitset's bit offset a multiple of 32; hooks BF_RANGE_PATH (1: no) and
+// BF_RANGE_I8_COS (0: unfiltered calls with Nq >= 1024 and N_base >= 65536, 1: no, 2: whenever the above
+// holds)
+bool bf_range_i8_cos_supported(const BfRangeLaunch& a);
+size_t bf_range_i8_cos_lds_bytes(uint32_t D, int fm);
 // and for the 16-bit tile kernels (bf_range_f16.hip), tried first: float16 / bfloat16, squared L2,
 // D % 8 == 0, D <= 4096, a bitset's bit offset a multiple of 32; hooks BF_RANGE_PATH (1: no; 2 alone does
 // not select them) and BF_RANGE_F16 (0: bfloat16 with Nq >= 10000 and N_base >= 1000000, 1: no, 2: type

@@ -999,6 +999,23 @@ int ggnn_debug_bf_range_i8_route(ggnn_dtype dtype, ggnn_measure measure, uint32_
   return bf_range_i8_supported(b) ? 1 : 0;
 }
 
+// and for the integer cosine tile kernels of byte rows (bf_range_i8_cos.hip)
+int ggnn_debug_bf_range_i8_cos_route(ggnn_dtype dtype, ggnn_measure measure, uint32_t D, uint32_t Nq,
+                                     uint32_t N_base, uint64_t capacity, int filter,
+                                     uint32_t filter_bit_offset, uint64_t* tile_lds_bytes)
+{
+  static const uint32_t word = 0;
+  static const int32_t label = 0;
+  BfRangeLaunch b{};
+  b.dtype = dtype, b.measure = measure, b.D = D, b.Nq = Nq, b.N_base = N_base, b.capacity = capacity;
+  b.filter_bits = filter ? &word : nullptr;
+  b.filter_bit_offset = filter_bit_offset;
+  b.filter_table.query_labels = filter == 2 ? &label : nullptr;
+  if (tile_lds_bytes)
+    *tile_lds_bytes = bf_range_i8_cos_lds_bytes(D, filter);
+  return bf_range_i8_cos_supported(b) ? 1 : 0;
+}
+
 // and for the 16-bit tile kernels of float16 / bfloat16 rows (bf_range_f16.hip)
 int ggnn_debug_bf_range_f16_route(ggnn_dtype dtype, ggnn_measure measure, uint32_t D, uint32_t Nq,
                                   uint32_t N_base, uint64_t capacity, int filter,

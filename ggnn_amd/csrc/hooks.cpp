@@ -24,7 +24,7 @@ constexpr Entry kTable[kHookCount] = {
     {"BF_RANGE_SLICES", 0}, {"BF_RANGE_PATH", 0}, {"BF_RANGE_CAND", 0},
     {"BF_RANGE_I8", 0},   {"BF_F16", 0},        {"BF_RANGE_F16", 0},
     {"BF_I8_WIDE", 0},    {"BF_I8_FILTERED", 0}, {"BF_LABEL_TILES", 0},
-    {"BF_I8_COS", 0},
+    {"BF_I8_COS", 0},     {"BF_RANGE_I8_COS", 0},
 };
 std::atomic<bool> g_set[kHookCount];
 std::atomic<int64_t> g_value[kHookCount];

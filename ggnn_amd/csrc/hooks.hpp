@@ -50,6 +50,7 @@ enum Hook {
   kHookBfI8Filtered,    // BF_I8_FILTERED   0 auto | 1 never | 2 filtered integer kernels of bf_query whenever dtype / measure / D / k / filter allow (bf_i8_filtered.hip)
   kHookBfLabelTiles,    // BF_LABEL_TILES   0 auto | 1 never | 2 float tile kernels for bf_query under label sets / ranges / masks whenever dtype / D / k / shape allow (bf_mfma_pred.hip)
   kHookBfI8Cos,         // BF_I8_COS        0 auto | 1 never | 2 integer cosine kernel of bf_query whenever dtype / measure / D / k / shape allow (bf_i8_cos.hip)
+  kHookBfRangeI8Cos,    // BF_RANGE_I8_COS  0 auto | 1 never | 2 integer cosine tile kernels of the range search whenever dtype / measure / D / filter allow (bf_range_i8_cos.hip)
   kHookCount
 };
 

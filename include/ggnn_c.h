@@ -297,8 +297,12 @@ ggnn_status ggnn_query_async_labeled(ggnn_t* h, const void* query, uint64_t Nq, 
  * matrix cores and decide every hit exactly; uint8 / int8 calls with Nq >= 256 and N >= 65536 under
  * squared L2 (D a multiple of 16) take their verdicts from the integer matrix cores, where a pair's distance is an
  * exact integer (a radius >= 2^24 at D > 258 sends the whole call to the scan kernels).  Same bits as
- * the scan kernels, which answer every other call -- byte rows under cosine among them (hooks
- * BF_RANGE_PATH, BF_RANGE_I8, BF_RANGE_SLICES, BF_RANGE_CAND): ggnn_last_bf_range_matrix_path. */
+ * the scan kernels, which answer every other call.  uint8 / int8 calls under cosine (16 <= D <= 4096, D a
+ * multiple of 16) have integer tile kernels as well (bf_range_i8_cos.hip, hook BF_RANGE_I8_COS): the
+ * exact integer dot product, a conservative float pre-test and the scan's own expression on what passes
+ * it; a squared norm >= 2^24 in the base or in a query that can have hits sends the whole call to the
+ * scan kernels (hooks BF_RANGE_PATH, BF_RANGE_I8, BF_RANGE_I8_COS, BF_RANGE_SLICES, BF_RANGE_CAND):
+ * ggnn_last_bf_range_matrix_path. */
 ggnn_status ggnn_bf_range_query(ggnn_t* h, const void* query, uint64_t Nq, uint32_t D,
                                 ggnn_dtype dtype, ggnn_location location, int gpu_id,
                                 const float* radii, ggnn_measure measure, uint64_t capacity,
@@ -574,6 +578,11 @@ int ggnn_debug_bf_range_route(ggnn_dtype dtype, uint32_t D, uint32_t Nq, uint32_
 int ggnn_debug_bf_range_i8_route(ggnn_dtype dtype, ggnn_measure measure, uint32_t D, uint32_t Nq,
                                  uint32_t N_base, uint64_t capacity, int filter,
                                  uint32_t filter_bit_offset, uint64_t* tile_lds_bytes);
+/* tests: the same for the integer cosine tile kernels of uint8 / int8 rows (hooks BF_RANGE_PATH,
+ * BF_RANGE_I8_COS) */
+int ggnn_debug_bf_range_i8_cos_route(ggnn_dtype dtype, ggnn_measure measure, uint32_t D, uint32_t Nq,
+                                     uint32_t N_base, uint64_t capacity, int filter,
+                                     uint32_t filter_bit_offset, uint64_t* tile_lds_bytes);
 /* tests: the same for the 16-bit tile kernels of float16 / bfloat16 rows (hooks BF_RANGE_PATH,
  * BF_RANGE_F16) */
 int ggnn_debug_bf_range_f16_route(ggnn_dtype dtype, ggnn_measure measure, uint32_t D, uint32_t Nq,
@@ -755,6 +764,13 @@ void ggnn_set_log_level(int level);
  *                             N >= 1000000 | 1 = never (the float32-staged tiles) | 2 = whenever those
  *                             conditions hold with Nq >= 256, N >= 4096; BF_SCAN = 1 still means the scan
  *                             (same results; test hook)
+ *   BF_RANGE_I8_COS     0     range search on uint8 / int8 rows under cosine: 0 = the integer cosine tile
+ *                             kernels (bf_range_i8_cos.hip) when 16 <= D <= 4096, D % 16 == 0, the call has
+ *                             no filter and Nq >= 1024, N >= 65536 (the shape classes measured, DESIGN.md
+ *                             4.6) | 1 = never (the scan) | 2 = whenever D allows, also under a bitset
+ *                             (bit offset a multiple of 32), a filter table or labels, whatever Nq and N;
+ *                             BF_RANGE_PATH = 1 still means the scan kernels always (same results; test
+ *                             hook)
  *   BF_I8_FILTERED      0    filtered bf_query (per-call bitset, filter ids, one label per query) on
  *                             uint8 / int8 rows: 0 = the filtered integer kernels (bf_i8_filtered.hip)
  *                             when the measure is squared L2, D % 16 == 0, D <= 4096, k <= 16, a bitset's
@@ -956,9 +972,11 @@ ggnn_status ggnn_op_bf_range_query_labeled(const void* base, ggnn_dtype dtype, u
 /* ggnn_op_bf_range_query with the union of the filter arguments (at most one of filter_bits,
  * filter_ids, query_labels non-NULL; the others as in the call of that name), and where it ran:
  * *fell_back (DEVICE memory, may be NULL) receives 1 if the tile path's candidate buffer overflowed
- * (float rows) or a radius >= 2^24 met D > 258 (byte rows) and the scan kernels answered, else 0;
+ * (float rows), a radius >= 2^24 met D > 258 (byte rows, squared L2) or a squared norm reached 2^24
+ * (byte rows, cosine) and the scan kernels answered, else 0;
  * *matrix_path (HOST, may be NULL) receives 1 if the call chose the float tile kernels
- * (bf_range_mfma.hip), 2 if it chose the integer tile kernels (bf_range_i8.hip), 3 if it chose the
+ * (bf_range_mfma.hip), 2 if it chose the integer tile kernels (bf_range_i8.hip, under cosine
+ * bf_range_i8_cos.hip), 3 if it chose the
  * 16-bit tile kernels (bf_range_f16.hip: *fell_back is then also 1 after a subnormal or non-finite
  * input or a candidate outside the instruction model), else 0. */
 ggnn_status ggnn_op_bf_range_query_routed(const void* base, ggnn_dtype dtype, uint32_t N_base,

@@ -1,6 +1,6 @@
 """Times the exact range search beside the K-best scan of the same shape, on one GPU:
 
-    python scripts/bf_range_bench.py [--reps 5] [--out FILE.json] [--dtype uint8|int8]
+    python scripts/bf_range_bench.py [--reps 5] [--out FILE.json] [--dtype uint8|int8] [--measure l2|cosine]
 
 Shapes: 10k x 1M x 128 float32 and uint8, 100 x 1M x 128 float32, 10k x 1M x 960 float32 cosine, and a
 sweep around the routing minima of the tile path (Nq 256 / 1024, N 4096 / 65536).  Per shape, with the radius of every
@@ -12,6 +12,8 @@ the tile kernels (`mfma_k10`).  The range calls run under BF_RANGE_PATH = 1 (the
 Byte rows alternate hook BF_RANGE_I8 = 1 (the scan) and = 2 (the integer tile kernels, exact verdicts)
 instead.  --dtype uint8|int8 runs the byte-row sweep: 10k x 1M x 128 and the four shapes around the
 routing minima, integer data over the full value range; the radii are pair distances, so integers.
+--dtype uint8|int8 --measure cosine runs the same sweep under cosine, with 10k x 1M x 768 behind it, hook
+BF_RANGE_I8_COS = 1 (the scan) against = 2 (the integer cosine tile kernels, bf_range_i8_cos.hip).
 --dtype f16|bf16 runs the 16-bit sweep on N(0,1) rows: 10k x 1M x 128 and x 960 and the four small shapes,
 hook BF_RANGE_F16 = 1 (the float32-staged tiles where BF_RANGE_PATH's minima admit the shape, else the
 scan) against = 2 (the 16-bit tile kernels); `path_fell_back` records (matrix_path, fell_back) of each.
@@ -34,9 +36,10 @@ BYTE = {"uint8": "u8", "int8": "i8"}
 HALF = {"f16": torch.float16, "bf16": torch.bfloat16}
 
 
-def byte_shapes(t):
-    return [(t, 10_000, 1_000_000, 128, 0)] + [(t, Nq, N, 128, 0) for Nq in (256, 1024)
-                                                for N in (4096, 65536)]
+def byte_shapes(t, measure=0):
+    return [(t, 10_000, 1_000_000, 128, measure)] + \
+           [(t, Nq, N, 128, measure) for Nq in (256, 1024) for N in (4096, 65536)] + \
+           ([(t, 10_000, 1_000_000, 768, 1)] if measure else [])
 
 
 def half_shapes(t):
@@ -64,10 +67,11 @@ def main():
     ap.add_argument("--out")
     ap.add_argument("--shapes", type=int, nargs="*")
     ap.add_argument("--dtype", choices=sorted(BYTE) + sorted(HALF))
+    ap.add_argument("--measure", choices=["l2", "cosine"], default="l2", help="byte-row sweep only")
     ap.add_argument("--no-kbest", action="store_true", help="skip the bf_query columns")
     args = ap.parse_args()
     shapes = (half_shapes(args.dtype) if args.dtype in HALF
-              else byte_shapes(BYTE[args.dtype]) if args.dtype else SHAPES)
+              else byte_shapes(BYTE[args.dtype], int(args.measure == "cosine")) if args.dtype else SHAPES)
     lines = []
     for si in (args.shapes if args.shapes is not None else range(len(shapes))):
         dtype, Nq, N, D, measure = shapes[si]
@@ -98,6 +102,7 @@ def main():
                     torch.empty(t, dtype=torch.float32, device="cuda")) for k, t in totals.items()}
         ms = {"scan_k10": [], "mfma_k10": []}
         hook = ("BF_RANGE_I8" if dtype in ("u8", "i8") and measure == 0
+                else "BF_RANGE_I8_COS" if dtype in ("u8", "i8")
                 else "BF_RANGE_F16" if dtype in HALF else "BF_RANGE_PATH")
         paths = {"": 1, "tile_": 2}
         fell = {}
@@ -115,7 +120,7 @@ def main():
                 # 16-bit tiles, BF_RANGE_PATH as it is by default
                 with _lib.hooks(**{hook: path}):
                     for k, r in radii.items():
-                        if rep < 0 and dtype in HALF:   # which path ran, and whether the scan answered
+                        if rep < 0 and (dtype in HALF or hook == "BF_RANGE_I8_COS"):   # which path ran, and whether the scan answered
                             fell[f"{pre}r{k}"] = ops.bf_range_query(base, query, r, measure, out=bufs[k],
                                                                     routed=True)[3:]
                         got[f"{pre}count_r{k}"] = timed(
